@@ -14,10 +14,20 @@ runs 2L forward + 2(L-1) backward SpMMs over nnz(A_hat) stored entries and that 
 time.  Layer-1 results are NOT cached; one of the backward SpMMs (the top layer's, whose operand is non-zero on the B
 batch rows only) visits just the entries whose neighbour is a batch row -- exact, but fewer gathers than nnz, so the
 figure is reference-equivalent work per second, not executed gathers (`spmm_edges_executed_per_step` has those).
-`epoch_time_s` is the other half of BASELINE.json's metric.  `roofline` prices the profile's dominant kernel (the
-forward SpMM with the fused Hadamard epilogue) from HIP events recorded around every launch during a second pass over
-the same steps, `roofline_plain` the plain forward SpMM; `cpu_baseline` times the reference's torch-CPU op sequence
-(oracle/torch_cpu_path.py, kind "port") on the host cores for a few steps of the same workload.
+`epoch_time_s` is the other half of BASELINE.json's metric.
+
+A plain run sets up, spins up and warms up, times the K steps and prints the line.  `--full` adds every other figure
+after the timed steps: `long_run` (a longer timed region), `lazy_top`, the per-kernel times, `roofline` (the profile's
+dominant kernel, the forward SpMM with the fused Hadamard epilogue, priced from HIP events recorded around every launch
+during a second pass over the same steps), `roofline_plain` (the plain forward SpMM), the multi-GPU exchange figures and
+`cpu_baseline` (the reference's torch-CPU op sequence, oracle/torch_cpu_path.py, kind "port", on the host cores for a
+few steps of the same workload).
+
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32 / float64, 64 MB at most):
+the loss, the embeddings in node order (a fixed seeded sample of rows on graphs too large for the budget, their ids in
+embedding_rows.npy), the updated parameters and the weight gradients; for `--workload diffusion` a fixed seeded sample of
+the diffusion profiles.  The same arguments give the same inputs on every run: the training done by the time-based
+spin-up is rolled back before the warm-up.
 
 `python bench.py --gpus N` without a torch.distributed environment starts its own N ranks (one per GPU, RCCL) before
 anything touches the GPU and relays rank 0's line.
@@ -45,6 +55,27 @@ GATHER_CEILING = {("whole_graph", 128): {"TBs": 19.42, "source": "profiles/r05_g
                   ("whole_graph_pathway", 256): {"TBs": 19.02, "source": "profiles/r05_gather_ceiling.txt: 1,012 MB of gathers in 53.2 us"}}
 XGMI_LINK_GBS = 153.0        # one xGMI link, one direction (7 links per GPU, one per peer in an 8-GPU node)
 COLLECTIVE_TIMEOUT_S = 300.0 # a stream that does not drain for this long = a peer stopped taking part: abort and exit non-zero
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all arrays together
+DUMP_SAMPLE_BYTES = 48 << 20 # the largest output is sampled down to this when it does not fit
+
+
+def dump_sample(count, item_bytes, seed=0):
+    """None when `count` items of `item_bytes` fit DUMP_SAMPLE_BYTES, else a fixed seeded sample of item ids in ascending order"""
+    keep = DUMP_SAMPLE_BYTES // item_bytes
+    if count <= keep:
+        return None
+    return np.sort(np.random.RandomState(seed).choice(count, keep, replace=False))
+
+
+def save_outputs(out_dir, arrays):
+    """--dump-outputs: every array as <out_dir>/<name>.npy"""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs, more than {DUMP_LIMIT_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def spmm_bytes(nnz, n, d, extra_rows=0):
@@ -155,6 +186,21 @@ def bench_diffusion(args, rank, world, local_rank):
     if not bool(((sums - 1).abs() < 1e-9).all()):
         raise SystemExit("a diffusion profile does not sum to 1")
     n, nnz = prob.n, int(prob.mt.nnz)
+    if args.dump_outputs:
+        # a fixed seeded sample of all start nodes; every rank contributes the sampled columns it owns (its slice of di)
+        pick = dump_sample(len(di), 8 * n)
+        pick = np.arange(len(di)) if pick is None else pick
+        lo = sum(len(s) for s in np.array_split(di, world)[:rank])
+        mine_pick = pick[(pick >= lo) & (pick < lo + len(mine))] - lo
+        part = (x[:, torch.from_numpy(mine_pick).to(x.device)].t().cpu().numpy(), it[mine_pick])
+        parts = [part]
+        if world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, part)
+        if rank == 0:
+            save_outputs(args.dump_outputs, {"profiles": np.concatenate([p[0] for p in parts]).astype(np.float64),
+                                             "profile_start_nodes": di[pick].astype(np.float64),
+                                             "iterations": np.concatenate([p[1] for p in parts]).astype(np.float64)})
     out = {"metric": "diffusion_profiles_per_s", "value": len(di) * args.steps / elapsed, "unit": "profiles/s", "n_gpus": world,
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
            "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
@@ -162,7 +208,7 @@ def bench_diffusion(args, rank, world, local_rank):
            "config": {"workload": f"diffusion profiles of the whole_graph stand-in: N={n}, nnz(M')={nnz}, {len(di)} start nodes "
                                   f"(all drugs and indications), alpha={alpha}, tol={tol}; {int(it.max())} power iterations",
                       "parallelism": "single" if world == 1 else f"start nodes split over {world} ranks, no collective"}}
-    if rank == 0:
+    if rank == 0 and args.full:
         y = torch.empty_like(x)
         for _ in range(3):
             eng.spmm(x, y)
@@ -190,6 +236,7 @@ def bench_diffusion(args, rank, world, local_rank):
             out["cpu_baseline"] = {"value": 1.0 / t_cpu, "unit": "profiles/s", "cores": 1, "kind": "port",
                                    "sample": f"{len(pick)} of the {len(di)} start nodes, one scipy power iteration each "
                                              f"(oracle/diffusion_oracle.py), max |device - oracle| = {worst:.1e}"}
+    if rank == 0:
         emit(out)
 
 
@@ -200,20 +247,28 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="whole_graph")
     ap.add_argument("--hidden-units", type=int, default=None)
-    ap.add_argument("--cache-layer1", action="store_true", help="also report the step time with layer-1 SpMMs cached")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure everything else: long_run, lazy_top, per-kernel "
+                    "times and rooflines, the multi-GPU exchange figures, the CPU baseline (off: a plain run times the K steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy "
+                    "(float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--cache-layer1", action="store_true", help="also report the step time with layer-1 SpMMs cached (with --full)")
     ap.add_argument("--no-lazy-top", dest="lazy_top", action="store_false", help="do not also time gss_plan_step_lazy (the top layer on the "
-                    "batch rows only: the same loss, gradients and parameters bit for bit; reported as `lazy_top`, never part of `value`)")
+                    "batch rows only: the same loss, gradients and parameters bit for bit; reported as `lazy_top`, never part of `value`) "
+                    "with --full")
     ap.add_argument("--pipeline", action="store_true", help="cross-step layer-1 software pipelining on a second HIP stream "
                                                              "(measured: no gain, off by default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="no CPU baseline in a --full run")
     ap.add_argument("--cpu-steps", type=int, default=20, help="timed steps of the CPU baseline (~0.5 s each at config 2)")
-    ap.add_argument("--min-time", type=float, default=0.5, help="after the K timed steps of the contract, keep stepping until this many "
-                    "seconds have been timed and report that steadier figure as `long_run` (0 = off)")
+    ap.add_argument("--min-time", type=float, default=0.5, help="with --full: after the K timed steps of the contract, keep stepping until "
+                    "this many seconds have been timed and report that steadier figure as `long_run` (0 = off)")
     ap.add_argument("--spinup-time", type=float, default=0.3, help="seconds of untimed steps BEFORE the W warm-up steps, to bring the GPU to "
-                    "its working clocks (a 5-step warm-up is 1.6 ms at this size); reported as spinup_steps")
+                    "its working clocks (a 5-step warm-up is 1.6 ms at this size); reported as spinup_steps.  The parameters and "
+                    "optimizer state they train are rolled back before the warm-up")
     ap.add_argument("--set", action="append", default=[], metavar="KNOB=VALUE", help="gss_debug_set_option before anything runs (A/B runs of "
                     "a kernel variant, e.g. --set gemm_variant=3); listed in the JSON line as `knobs`")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)          # never returns
@@ -372,9 +427,11 @@ def main():
         return out.cpu().numpy().reshape(world, -1)
 
     # spin-up: untimed steps on the warm-up batches until the clocks have settled (the same count on every rank: the step is a
-    # collective), then the contract's W warm-up steps and K timed steps
+    # collective), then the contract's W warm-up steps and K timed steps.  How many spin-up steps run depends on timing, so the
+    # parameters and Adam state they leave are rolled back to the initial ones: the W + K steps compute the same on every run
     spinup_steps = 0
     if args.spinup_time > 0 and args.warmup > 0:
+        initial_state = engine.state_dict()
         run(0, args.warmup)
         barrier()
         t_ = time.perf_counter()
@@ -389,6 +446,8 @@ def main():
         for _ in range(reps):
             run(0, args.warmup)
         spinup_steps = (2 + reps) * args.warmup
+        barrier()
+        engine.load_state_dict(initial_state)
     run(0, args.warmup)
     barrier()
     t0 = time.perf_counter()
@@ -399,10 +458,27 @@ def main():
     loss_end = float(engine.loss.item())
     if not np.isfinite(loss_end):
         raise SystemExit(f"non-finite loss {loss_end} after the timed steps")
+    if args.dump_outputs:
+        # what a caller of the step receives after the last timed step: its loss, the embeddings of its forward pass (node order), the
+        # parameters Adam left and the weight gradients it applied
+        emb = engine.gather_embeddings()          # a collective on a sharded plan: every rank takes part
+        if rank == 0:
+            rows = dump_sample(emb.shape[0], 4 * emb.shape[1])
+            arrays = {"loss": engine.loss.detach().cpu().numpy().reshape(1)}
+            if rows is None:
+                arrays["embeddings"] = emb.cpu().numpy()
+            else:
+                arrays["embeddings"] = emb[torch.from_numpy(rows).to(emb.device)].cpu().numpy()
+                arrays["embedding_rows"] = rows.astype(np.float64)
+            for k, name in enumerate(("W1", "b1", "W2", "b2")):
+                arrays[name] = engine.params[k].detach().cpu().numpy()
+                arrays["grad_" + name] = engine.grads[k].detach().cpu().numpy()
+            save_outputs(args.dump_outputs, arrays)
+        del emb
     # the contract's K steps are a few milliseconds at this size; a longer region over the same batches gives a figure
     # that can be tracked from round to round
     long_run = None
-    if args.min_time > 0:
+    if args.full and args.min_time > 0:
         reps = int(np.ceil(args.min_time / max(elapsed, 1e-6)))
         reps = max(1, min(reps, 100000))
         barrier()
@@ -414,7 +490,7 @@ def main():
         long_run = {"steps": reps * args.steps, "seconds": el2, "ms_per_step": el2 / (reps * args.steps) * 1e3}
 
     lazy_top = None
-    if args.lazy_top and world == 1 and hasattr(engine, "step_lazy"):
+    if args.full and args.lazy_top and world == 1 and hasattr(engine, "step_lazy"):
         try:
             # opt-in extra: the same steps through gss_plan_step_lazy (NOT the reported value: the reference's step computes all N rows of
             # the top layer; this one computes the B rows anything reads).  Same batches, timed the same way.
@@ -491,6 +567,24 @@ def main():
     if long_run:
         out["long_run"] = long_run
         out["long_run"]["edges_per_s"] = spmm_per_step * nnz / (long_run["ms_per_step"] * 1e-3)
+
+    def finish():
+        if rank == 0:
+            emit(out)
+        if job_comm is not None:
+            job_comm.sync(COLLECTIVE_TIMEOUT_S)
+        if dist.is_initialized():
+            dist.destroy_process_group()
+
+    if not args.full:
+        if sharded:
+            out["rccl_ranks"] = job_comm.count()
+            if host_backend:
+                out["rehearsal"] = True
+        if halo_info is not None:
+            out["shard"] = halo_info
+        finish()
+        return
 
     # ---- roofline leg: HIP events around every kernel class over the same steps, on every rank ----
     # An event pair around a launch also brackets the gap the marker packets open between kernels, so the bracketed times sum to
@@ -793,12 +887,7 @@ def main():
                                "thread_sweep_s_per_step": {str(k): v for k, v in sweep.items()},
                                "spmm_kernel_edges_per_s": nnz / t_spmm, "host_cpus": host_cpus}
 
-    if rank == 0:
-        emit(out)
-    if job_comm is not None:
-        job_comm.sync(COLLECTIVE_TIMEOUT_S)
-    if dist.is_initialized():
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

@@ -478,7 +478,7 @@ def test_two_rccl_ranks_bench_line_is_complete():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--spinup-time", "0.05",
-                        "--min-time", "0"], capture_output=True, text=True, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"), timeout=900)
+                        "--min-time", "0", "--full"], capture_output=True, text=True, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"), timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["rccl_ranks"] == 2
@@ -534,7 +534,7 @@ def test_multi_process_bench_on_one_gpu_host_staged_backend():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--spinup-time", "0",
-                        "--min-time", "0"], capture_output=True, text=True,
+                        "--min-time", "0", "--full"], capture_output=True, text=True,
                        env=dict(_host_env(), GSS_OPTIONS="lazy_halo=1", GSS_LOCAL_TRANSPOSE="0"), timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -557,7 +557,7 @@ def test_multi_process_bench_on_one_gpu_host_staged_backend():
     assert abs(line["config"]["final_loss"] - one["config"]["final_loss"]) <= T.SPREAD_LOSS_REL * 10 * abs(one["config"]["final_loss"])
     # the defaults: 3 collectives per step (M_1's boundary rows, the batch rows, the weight gradients)
     r3 = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--spinup-time", "0",
-                         "--min-time", "0"], capture_output=True, text=True, env=_host_env(), timeout=900)
+                         "--min-time", "0", "--full"], capture_output=True, text=True, env=_host_env(), timeout=900)
     assert r3.returncode == 0, r3.stderr[-3000:]
     l3 = json.loads([l for l in r3.stdout.splitlines() if l.startswith("{")][-1])
     assert l3["collectives_per_step"]["total"] == 3.0, l3["collectives_per_step"]
@@ -621,7 +621,7 @@ def test_bench_sharded_path_over_rccl_single_rank(tmp_path):
     env = dict(os.environ, GSS_FORCE_SHARDED="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--no-cpu-baseline",
-           "--spinup-time", "0", "--min-time", "0"]     # (both runs must take the SAME number of steps: no time-based spin-up / long run)
+           "--spinup-time", "0", "--min-time", "0", "--full"]     # (both runs must take the SAME number of steps: no time-based spin-up / long run)
     out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]

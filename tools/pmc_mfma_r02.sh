@@ -5,4 +5,4 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 W=${1:-whole_graph}
 T=${2:-r02_mfma}
-PMC_FILTER=kernel bash $R/tools/pmc_run.sh $T "SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA GRBM_GUI_ACTIVE" bench.py --workload $W --steps 5 --warmup 2 --no-cpu-baseline --min-time 0 --spinup-time 0
+PMC_FILTER=kernel bash $R/tools/pmc_run.sh $T "SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA GRBM_GUI_ACTIVE" bench.py --full --workload $W --steps 5 --warmup 2 --no-cpu-baseline --min-time 0 --spinup-time 0

@@ -9,9 +9,9 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 export GRAFT_REPO_ROOT=$R
 O=$R/gpurun_out/r04; mkdir -p $O
-python3 $R/bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+python3 $R/bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
 cd /tmp; export TMPDIR=/tmp
-rm -rf $O/prof; timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-lazy-top > $O/bench_under_rocprof.json 2> $O/rocprof.err; echo "rocprof full rc=$?"
+rm -rf $O/prof; timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-lazy-top > $O/bench_under_rocprof.json 2> $O/rocprof.err; echo "rocprof full rc=$?"
 cp $(find $O/prof -name "*kernel_stats.csv" | head -1) $O/kernel_stats.csv
 rm -rf $O/prof_lazy; timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_lazy -- python3 $R/tools/lazy_only_prof.py > $O/lazy_only.txt 2> $O/rocprof_lazy.err; echo "rocprof lazy rc=$?"
 cp $(find $O/prof_lazy -name "*kernel_stats.csv" | head -1) $O/lazy_kernel_stats.csv

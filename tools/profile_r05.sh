@@ -20,12 +20,12 @@ pmc() {    # <case tag> <workload> <mode> <d>
 }
 for part in $parts; do
   case $part in
-    c2) python3 $R/bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
-        prof bench $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-lazy-top
+    c2) python3 $R/bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+        prof bench $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-lazy-top
         prof lazy $R/tools/lazy_only_prof.py ;;
     c2pmc) pmc wg_fwd1 whole_graph fwd1 128; pmc wg_plain whole_graph plain 128 ;;
-    c3) python3 $R/bench.py --workload whole_graph_pathway --no-cpu-baseline > $O/bench_config3.json 2> $O/bench_config3.err; echo "bench config3 rc=$?"
-        prof config3 $R/bench.py --workload whole_graph_pathway --steps 20 --warmup 5 --no-cpu-baseline --no-lazy-top ;;
+    c3) python3 $R/bench.py --full --workload whole_graph_pathway --no-cpu-baseline > $O/bench_config3.json 2> $O/bench_config3.err; echo "bench config3 rc=$?"
+        prof config3 $R/bench.py --full --workload whole_graph_pathway --steps 20 --warmup 5 --no-cpu-baseline --no-lazy-top ;;
     c3pmc) pmc wgp_fwd1 whole_graph_pathway fwd1 256; pmc wgp_plain whole_graph_pathway plain 256 ;;
   esac
 done

@@ -16,19 +16,19 @@ prof() {   # <name> <program and args...>: rocprofv3 --kernel-trace --stats, the
 }
 pmc_step() {    # <tag> <workload>: counters of full steps
   for grp in "${GROUPS_[@]}"; do
-    PMC_TIMEOUT=400 bash $R/tools/pmc_run.sh "r06_$1_$(echo $grp | cut -d' ' -f1)" "$grp" bench.py --workload $2 --steps 5 --warmup 2 --spinup-time 0 --min-time 0 --no-cpu-baseline --no-lazy-top | grep -v "^$" | tail -4
+    PMC_TIMEOUT=400 bash $R/tools/pmc_run.sh "r06_$1_$(echo $grp | cut -d' ' -f1)" "$grp" bench.py --full --workload $2 --steps 5 --warmup 2 --spinup-time 0 --min-time 0 --no-cpu-baseline --no-lazy-top | grep -v "^$" | tail -4
     find $R/gpurun_out/pmc/r06_$1_$(echo $grp | cut -d' ' -f1) -name "*agent_info.csv" -delete
   done
 }
 for part in $parts; do
   case $part in
-    c2) python3 $R/bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
-        prof bench $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-lazy-top ;;
+    c2) python3 $R/bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+        prof bench $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-lazy-top ;;
     c2pmc) pmc_step c2 whole_graph; python3 $R/tools/pmc_pack_r06.py | tail -5 ;;
-    c3) python3 $R/bench.py --workload whole_graph_pathway --no-cpu-baseline > $O/bench_config3.json 2> $O/bench_config3.err; echo "bench config3 rc=$?"
-        prof config3 $R/bench.py --workload whole_graph_pathway --steps 20 --warmup 5 --no-cpu-baseline --no-lazy-top ;;
+    c3) python3 $R/bench.py --full --workload whole_graph_pathway --no-cpu-baseline > $O/bench_config3.json 2> $O/bench_config3.err; echo "bench config3 rc=$?"
+        prof config3 $R/bench.py --full --workload whole_graph_pathway --steps 20 --warmup 5 --no-cpu-baseline --no-lazy-top ;;
     c3pmc) pmc_step c3 whole_graph_pathway; python3 $R/tools/pmc_pack_r06.py | tail -7 ;;
-    c5) python3 $R/bench.py --workload rmat:10000000:200000000 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_rmat_10M_200M.json 2> $O/bench_rmat.err; echo "bench rmat rc=$?" ;;
+    c5) python3 $R/bench.py --full --workload rmat:10000000:200000000 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_rmat_10M_200M.json 2> $O/bench_rmat.err; echo "bench rmat rc=$?" ;;
     c5pmc) pmc_step c5 rmat:10000000:200000000
            for grp in "${GROUPS_[@]}"; do
              t=$(echo $grp | cut -d' ' -f1)

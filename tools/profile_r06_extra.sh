@@ -10,4 +10,4 @@ prof() {
   cp $(find $O/prof_$name -name "*kernel_stats.csv" | head -1) $O/${name}_kernel_stats.csv && rm -rf $O/prof_$name
 }
 prof lazy_step $R/tools/lazy_only_prof.py
-prof rmat $R/bench.py --workload rmat:10000000:200000000 --steps 5 --warmup 2 --no-cpu-baseline
+prof rmat $R/bench.py --full --workload rmat:10000000:200000000 --steps 5 --warmup 2 --no-cpu-baseline
