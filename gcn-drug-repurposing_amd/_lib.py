@@ -9,7 +9,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgssgcn.so")
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 _lib = None
 
@@ -32,6 +32,12 @@ class PprDesc(C.Structure):
                 + [(k, C.c_void_p) for k in ("ovr_col", "ovr_row", "ovr_ratio", "zero_ptr", "zero_ovr")]
                 + [("n_sel", C.c_int64)]
                 + [(k, C.c_void_p) for k in ("sel_col", "sel_row", "sel_val", "keep_ptr", "keep_row", "keep_val", "ovr_ptr")])
+
+
+class SgnsDesc(C.Structure):
+    _fields_ = ([(k, C.c_int32) for k in ("n", "d", "walk_length", "window", "negative", "epochs")] + [("n_walks", C.c_int64)]
+                + [(k, C.c_void_p) for k in ("walks", "lengths", "cum_table", "sample_int")]
+                + [("cum_last", C.c_uint32), ("alpha", C.c_float), ("min_alpha", C.c_float), ("seed", C.c_uint64), ("concurrency", C.c_int32)])
 
 
 class HaloDesc(C.Structure):
@@ -143,6 +149,12 @@ SIGNATURES = {
     "gss_ppr_check_guards": (C.c_int, [_P]),
     "gss_ppr_run": (C.c_int, [_P, _D, _D, _I32, _P, _P, _P]),
     "gss_ppr_spmm": (C.c_int, [_P, _P, _P, _P]),
+    "gss_walk_prefix": (C.c_int, [_I32, _P, _P, _P, _P]),
+    "gss_node2vec_walks": (C.c_int, [_I32, _P, _P, _P, _P, _I64, _P, _I32, _D, _D, C.c_uint64, _P, _P, _P]),
+    "gss_sgns_counts": (C.c_int, [_I64, _I32, _P, _P, _P, _P]),
+    "gss_sgns_init": (C.c_int, [_I32, _I32, C.c_uint64, _P, _P, _P]),
+    "gss_sgns_default_concurrency": (C.c_int, []),
+    "gss_sgns_epoch": (C.c_int, [C.POINTER(SgnsDesc), _I32, _P, _P, _P]),
 }
 
 

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define GSS_ABI_VERSION 6   /* 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
+#define GSS_ABI_VERSION 7   /* 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
 
 #define GSS_OK 0
 #define GSS_EINVAL (-22)   /* bad argument (shape, null pointer, unsupported d) */
@@ -300,6 +300,44 @@ int gss_ppr_check_guards(gss_ppr *p);
 int gss_ppr_run(gss_ppr *p, double alpha, double tol, int32_t max_iter, double *x, int32_t *iters_out, void *stream);
 /* one product y = M'^T x on the handle's schedule (fp64; the kernel the iteration is built on) */
 int gss_ppr_spmm(gss_ppr *p, const double *x, double *y, void *stream);
+
+/* ---- node2vec input embeddings: multiscale/openne/node2vec.py:7-47 (walker.py:58-207 + gensim Word2Vec sg=1 negative sampling) ------------
+ * The trainer's input .embs.txt (predict_drug.py:33-46) made on the device: second-order biased walks over the raw weighted directed
+ * graph (walk.hip), then skip-gram with negative sampling over them (sgns.hip).  Every random number comes from a counter-based generator
+ * keyed by (seed, what, counters) -- csrc/counter_rng.h --, so walks and a serial SGNS epoch are pure functions of their inputs.
+ *
+ * gss_walk_prefix: cum[e] = inclusive fp64 prefix sum of val over e's row, in row order.  Validates every weight: returns GSS_EINVAL
+ * naming the first CSR entry whose weight is not positive and finite.  Waits for the stream (it reads the verdict).
+ * gss_node2vec_walks: walk w starts at starts[w] and takes at most walk_length nodes (the start included); step 1 is first-order in the
+ * edge weights, later steps from cur with predecessor prev pick x with weight w(cur, x) * (1/p if x == prev, else 1 if x -> prev is an
+ * edge, else 1/q).  A walk ends early at a node without out-edges.  Out: walks [n_walks][walk_length] (unused tail = -1), lengths
+ * [n_walks].  Columns must be sorted within each row, cum from gss_walk_prefix; p, q > 0 and walk_length >= 1 are checked by name. */
+int gss_walk_prefix(int32_t n, const int32_t *rowptr, const double *val, double *cum, void *stream);
+int gss_node2vec_walks(int32_t n, const int32_t *rowptr, const int32_t *col, const double *val, const double *cum, int64_t n_walks,
+                       const int32_t *starts, int32_t walk_length, double p, double q, uint64_t seed, int32_t *walks, int32_t *lengths,
+                       void *stream);
+/* gss_sgns_counts: counts[node] += occurrences of node in the walks (counts: int64 [n], zeroed by the caller).
+ * gss_sgns_init: syn0[i][k] = (u - 0.5) / d with u uniform fp32 keyed by (seed, i, k); syn1neg = 0.
+ * gss_sgns_epoch: one epoch of gensim 3.x skip-gram negative sampling (sgns.hip has the update rule).  The sigmoid is evaluated
+ * exactly (1 / (1 + expf(-f)), fp32), a target with |f| >= 6 is skipped as gensim skips it.  cum_table is gensim's negative-sampling
+ * table (uint32 [n], cumulative count^ns_exponent scaled to 2^31 - 1, cum_last = its last entry), sample_int gensim's downsampling
+ * threshold per node (a token is kept iff a uint32 draw <= sample_int).  concurrency = center positions in flight (one wave each);
+ * 1 runs the epoch in serial order, gss_sgns_default_concurrency() fills the device.  d must be 64, 128, 256 or 512. */
+typedef struct gss_sgns_desc {
+  int32_t n, d, walk_length, window, negative, epochs;
+  int64_t n_walks;
+  const int32_t *walks, *lengths;   /* from gss_node2vec_walks; one sentence per walk */
+  const uint32_t *cum_table;
+  const int64_t *sample_int;
+  uint32_t cum_last;
+  float alpha, min_alpha;           /* linear decay over (epoch + sentence / n_walks) / epochs */
+  uint64_t seed;
+  int32_t concurrency;
+} gss_sgns_desc;
+int gss_sgns_counts(int64_t n_walks, int32_t walk_length, const int32_t *walks, const int32_t *lengths, int64_t *counts, void *stream);
+int gss_sgns_init(int32_t n, int32_t d, uint64_t seed, float *syn0, float *syn1neg, void *stream);
+int gss_sgns_default_concurrency(void);
+int gss_sgns_epoch(const gss_sgns_desc *desc, int32_t epoch, float *syn0, float *syn1neg, void *stream);
 
 /* ---- a13  np.savetxt('graph_embs.txt', hidden_emb), train.py:193 (host-side; h_emb is a HOST pointer) ---------------------
  * Every value of the float32 matrix as Python prints it with '%.18e' after widening to double (exact decimal expansion, round
