@@ -47,8 +47,6 @@ struct GemmArgs {
                                  // rows_out[rows_out_pos[r]] where that is >= 0 (the batch-position map: E_B of a FULL step)
   float *rows_out;      // EPI_FWD_NORM over a row list (nullable): the unit-norm row of tile row t ALSO goes to rows_out[t] -- the lazy step's
                         // tile rows are the batch positions, so this IS E_B = emb[idx] (model.py:216-217) without a gather launch
-  unsigned long long *stamps;  // diagnostic (gss_debug_set_stamp_buffer, NULL in production): per wave {start, loop begin, loop end, end} in
-                               // 100 MHz wall-clock ticks + {linear workgroup id, HW_ID}; tools/gemm_stamps.py reads it
 };
 
 // Epilogue of the forward projection for one 16-node x 16 NT tile row: lane (r, q) holds OUT[nd][j0 + 16 u + 4 q + 0..3]
@@ -309,9 +307,7 @@ __device__ __forceinline__ XcdIds xcd_ids(int L, int n_spread, int n_share, bool
 
 // WAVES = 1 (forward over a short row list, gss_plan_step_lazy's 2048 batch rows): one wave and 16 MT nodes per workgroup, so that the
 // few rows spread over 4 x as many CUs; a row's MFMA chain is the same, its result has the same bits
-// STAMP: the diagnostic instantiation of tools/gemm_stamps.py (per-wave wall-clock stamps); production launches use STAMP = false,
-// whose code carries none of it
-template <int NT, int MT, int EPI, int WAVES = 4, bool STAMP = false, bool LINES = false, int MINW = 1>
+template <int NT, int MT, int EPI, int WAVES = 4, bool LINES = false, int MINW = 1>
 __global__ __launch_bounds__(64 * WAVES, MINW) void gemm_nt_lds_kernel(GemmArgs g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int BN = 16 * NT;
@@ -328,12 +324,6 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void gemm_nt_lds_kernel(GemmArgs 
   const int r = lane & 15, q = lane >> 4;
   // grid = (node tiles, column tiles): the column tiles of a node tile read the same input rows
   const int linear = (int)(blockIdx.x + gridDim.x * blockIdx.y);
-  unsigned long long *stamp = (STAMP && g.stamps) ? g.stamps + ((size_t)linear * WAVES + (threadIdx.x >> 6)) * 6 : nullptr;
-  if (STAMP && stamp && (threadIdx.x & 63) == 0) {
-    stamp[0] = wall_clock64();
-    stamp[4] = (unsigned long long)linear;
-    stamp[5] = (unsigned long long)__builtin_amdgcn_s_getreg((4) | (0 << 6) | ((16 - 1) << 11));
-  }
   const XcdIds id = xcd_ids(linear, (int)gridDim.x, (int)gridDim.y, true);
   const int node_base = id.spread * BM;
   const int j0 = id.share * BN;
@@ -386,7 +376,6 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void gemm_nt_lds_kernel(GemmArgs 
   if (HOIST) fwd_prefetch<NT, EPI, LINES>(g, node_base + 16 * (MT * w) + r, j0, q, pre);
 
   for (int c = 0; c < PF && c < nchunk; ++c) stage(c);
-  if (STAMP && stamp && lane == 0) stamp[1] = wall_clock64();
   for (int ci = 0; ci < nchunk; ++ci) {
     // chunk ci has landed once at most min(PF-1, nchunk-1-ci) younger chunks of this wave are outstanding
     const int younger = min(PF - 1, nchunk - 1 - ci);
@@ -419,7 +408,6 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void gemm_nt_lds_kernel(GemmArgs 
     __builtin_amdgcn_sched_barrier(0);  // keep the MFMA cluster inside its iteration
   }
 
-  if (STAMP && stamp && lane == 0) stamp[2] = wall_clock64();
   // epilogue: lane (r, q) holds OUT[node_base + 16 (MT w + t) + r][j0 + 16 u + 4 q + 0..3]
 #pragma unroll
   for (int t = 0; t < MT; ++t) {
@@ -457,10 +445,6 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void gemm_nt_lds_kernel(GemmArgs 
     } else {
       fwd_epilogue<NT, EPI, LINES>(g, acc[t], nd, j0, q);
     }
-  }
-  if (STAMP && stamp) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the stores of this wave have left
-    if (lane == 0) stamp[3] = wall_clock64();
   }
 }
 
@@ -575,12 +559,9 @@ __global__ __launch_bounds__(256) void gemm_rows_split_kernel(GemmArgs g) {
 // youngest" at the end of a tile's MFMAs is "everything except the DMA pieces of the tile after next", whatever stores are in flight.
 constexpr int kWsWorkgroups = 512;        // its persistent workgroups: two per CU (256 / 768 measured slower, profiles/r05_proj_ws_bench.txt)
 constexpr int kWsStagger = 4;             // its second generation of workgroups (linear id >= 256) starts this many x 512 cycles late (0 / 2 / 6 / 8 measured slower)
-struct WsStamp {
-  unsigned long long t[24];   // [0] start, [1] weights + first tile ready, [2 + 2 i] MFMAs of tile i done, [3 + 2 i] its stores issued (i < 9),
-};                            // [20] linear id, [21] HW_ID, [22] tiles, [23] XCC_ID
 
-template <int EPI, bool STAMP>
-__global__ __launch_bounds__(256, 1) void proj_ws_kernel(GemmArgs g, WsStamp *stamps) {
+template <int EPI>
+__global__ __launch_bounds__(256, 1) void proj_ws_kernel(GemmArgs g) {
   constexpr int stagger = kWsStagger;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NCH = 16;             // 16-wide chunks of K = 2 d = 256
@@ -596,14 +577,6 @@ __global__ __launch_bounds__(256, 1) void proj_ws_kernel(GemmArgs g, WsStamp *st
   const int ntiles = (g.n + 15) >> 4;
   const int G = (int)gridDim.x, b = (int)blockIdx.x;
   const int my_tiles = b < ntiles ? (ntiles - b + G - 1) / G : 0;
-  WsStamp *stamp = (STAMP && stamps) ? stamps + ((size_t)b * 4 + w) : nullptr;
-  if (STAMP && stamp && lane == 0) {
-    stamp->t[0] = wall_clock64();
-    stamp->t[20] = (unsigned long long)b;
-    stamp->t[21] = (unsigned long long)__builtin_amdgcn_s_getreg((4) | (0 << 6) | ((32 - 1) << 11));
-    stamp->t[22] = (unsigned long long)my_tiles;
-    stamp->t[23] = (unsigned long long)__builtin_amdgcn_s_getreg((20) | (0 << 6) | ((4 - 1) << 11));
-  }
   if (my_tiles == 0) return;
 
   // a tile's DMA: wave w stages fragment blocks w, w + 4 (AX: k < 128) and w + 8, w + 12 (AM)
@@ -635,7 +608,6 @@ __global__ __launch_bounds__(256, 1) void proj_ws_kernel(GemmArgs g, WsStamp *st
     f32x4 sink;
     asm volatile("global_load_dwordx4 %0, %1, off\n\ts_waitcnt vmcnt(0)" : "=v"(sink) : "v"(wp) : "memory");
   }
-  if (STAMP && stamp && lane == 0) stamp->t[19] = wall_clock64();
   // the wave's slice of [W1 | W2]: block u (features 32 w + 16 u + r), chunk c (k = 16 c + 4 q .. + 3; c >= 8 is W2)
   float4 wr[2][NCH];
   // (fetching them in whole 128-B lines, the halves of a 16-lane row traded by DPP -- round 5's gemm_ws_mode bit 1 -- measured no faster and
@@ -655,7 +627,6 @@ __global__ __launch_bounds__(256, 1) void proj_ws_kernel(GemmArgs g, WsStamp *st
   // covers the previous tile's stores on every trip
   __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0), expcnt / lgkmcnt untouched
   __builtin_amdgcn_s_barrier();
-  if (STAMP && stamp && lane == 0) stamp->t[1] = wall_clock64();
 
   for (int i = 0; i < my_tiles; ++i) {
     const int T = b + i * G;
@@ -705,7 +676,6 @@ __global__ __launch_bounds__(256, 1) void proj_ws_kernel(GemmArgs g, WsStamp *st
       wait_vmcnt<4>();
     else
       wait_vmcnt<0>();
-    if (STAMP && stamp && lane == 0 && i < 9) stamp->t[2 + 2 * i] = wall_clock64();
 
     // epilogue (fwd_epilogue_lines for the one block pair of this wave)
     const float4 lo = make_float4(acc[0][0], acc[0][1], acc[0][2], acc[0][3]);
@@ -763,7 +733,6 @@ __global__ __launch_bounds__(256, 1) void proj_ws_kernel(GemmArgs g, WsStamp *st
       if (!odd && live0) g.inv_den[nd0] = 1.f / den0;
       if (odd && live1) g.inv_den[nd1] = 1.f / den1;
     }
-    if (STAMP && stamp && lane == 0 && i < 9) stamp->t[3 + 2 * i] = wall_clock64();
   }
 }
 
@@ -782,15 +751,11 @@ __global__ __launch_bounds__(256, 1) void proj_ws_kernel(GemmArgs g, WsStamp *st
 
 // debug knob "wgrad_wgs": workgroups of a full-size weight-gradient launch (one per CU)   [knob wgrad_wgs, common.h Knobs]
 
-unsigned long long *g_gemm_stamps = nullptr;   // gss_debug_set_stamp_buffer: diagnostic only, process-wide, not a knob
-
 constexpr int kWsMinRows = 256 * 128 + 1;   // gemm_ws = -1: the weight-stationary projection from this many rows on -- more 128-node tiles than CUs
 
 template <int EPI>
-static int launch_gemm(const GemmArgs &g_in, int d, hipStream_t st) {
-  if (g_in.n <= 0) return GSS_OK;
-  GemmArgs g = g_in;
-  g.stamps = g_gemm_stamps;
+static int launch_gemm(const GemmArgs &g, int d, hipStream_t st) {
+  if (g.n <= 0) return GSS_OK;
   {
     int nt = (d % 128 == 0) ? 8 : (d % 64 == 0) ? 4 : (d % 32 == 0) ? 2 : 1;
     if (EPI == EPI_FWD_NORM && d == 256) nt = 16;   // the fused row norm needs a row's features in one tile
@@ -799,7 +764,7 @@ static int launch_gemm(const GemmArgs &g_in, int d, hipStream_t st) {
     if (EPI == EPI_SPLIT)
       while (nt > 2 && (int64_t)ceil_div(g.n, 64) * (g.J / (16 * nt)) < 256) nt >>= 1;
     // 64-node tiles give 2-3 co-resident workgroups per CU (epilogue traffic overlaps MFMA); at d >= 256 the
-    // W-staging redundancy of small tiles costs more than that buys (measured, tools/gemm_bench.py), and so it does once
+    // W-staging redundancy of small tiles costs more than that buys (profiles/r03_projection_pipeline_experiments.txt), and so it does once
     // the grid is many waves of workgroups deep (d = 128: N = 1M 791 -> 753 us, N = 4M 3061 -> 2913 us with 128-node tiles)
     const int mt = K().gemm_variant == 3 ? 2 : ((d >= 256 || g.n >= 262144) ? 2 : 1);
     if (EPI != EPI_SPLIT && g.rows && (int64_t)ceil_div(g.n, 64) * (g.J / (16 * nt)) < 256) {
@@ -839,11 +804,7 @@ static int launch_gemm(const GemmArgs &g_in, int d, hipStream_t st) {
         const int ntiles = ceil_div(g.n, 16);
         const int wgs = std::min(ntiles, kWsWorkgroups);
         const size_t ldsw = (size_t)(3 * 16 * 256 + 2 * 512) * sizeof(float);
-        WsStamp *sp = reinterpret_cast<WsStamp *>(g.stamps);   // diagnostic (gss_debug_set_stamp_buffer; tools/proj_ws_stamps.py): 24 x 8 bytes per wave
-        if (sp)
-          hipLaunchKernelGGL((proj_ws_kernel<EPI, true>), dim3(wgs), dim3(256), ldsw, st, g, sp);
-        else
-          hipLaunchKernelGGL((proj_ws_kernel<EPI, false>), dim3(wgs), dim3(256), ldsw, st, g, sp);
+        hipLaunchKernelGGL((proj_ws_kernel<EPI>), dim3(wgs), dim3(256), ldsw, st, g);
         GSS_LAUNCH_CHECK("proj_ws_kernel");
         return GSS_OK;
       }
@@ -852,20 +813,15 @@ static int launch_gemm(const GemmArgs &g_in, int d, hipStream_t st) {
     //  projection below -- is 1.0 us per step SLOWER than the 128 x 128 tiles of four waves: profiles/r06_ab_live_prefetch_and_norm8.txt.)
     dim3 grid(ceil_div(g.n, 64 * mt), g.J / (16 * nt));
     const size_t lds = 4 * (size_t)(64 * mt * 16 + 16 * nt * 16) * sizeof(float);
-    if (g.stamps && EPI == EPI_FWD && nt == 8 && mt == 1) {   // diagnostic twin (tools/gemm_stamps.py): the d = 128 projection only
-      hipLaunchKernelGGL((gemm_nt_lds_kernel<8, 1, EPI_FWD, 4, true>), grid, dim3(256), lds, st, g);
-      GSS_LAUNCH_CHECK("gemm_nt_lds_kernel (stamped)");
-      return GSS_OK;
-    }
     if ((K().gemm_variant == 5 || (K().gemm_variant == 2 && d == 128)) && nt == 8 && !g.rows && EPI != EPI_SPLIT) {
       // 128-node tiles as EIGHT waves of 16 nodes (round 4): the weights are staged once per 128 nodes as with MT = 2, but a wave keeps
       // the 16-node tile's 104-110 registers (no hoisted operands, the whole-line epilogue), so two such workgroups share a CU: 16
-      // waves per CU instead of 8.  Same MFMA order per output, same bits.  d = 128 (tools/gemm_w8_ab.py): 28.0 vs 30.2 us (64-node
+      // waves per CU instead of 8.  Same MFMA order per output, same bits.  d = 128 (profiles/r04_gemm_eight_waves_ab.txt): 28.0 vs 30.2 us (64-node
       // tiles) at N = 29,960, 188 vs 197 us (128-node, 4 waves) at 250k, equal from 1M on; in the step -1.75 us (full), -1.1 us (the
       // trainer's).  gemm_variant 5 forces it for other widths, 3 forces the 4-wave 128-node tiles.
       dim3 grid8(ceil_div(g.n, 128), g.J / (16 * nt));
       const size_t lds8 = 4 * (size_t)(128 * 16 + 16 * nt * 16) * sizeof(float);
-      hipLaunchKernelGGL((gemm_nt_lds_kernel<8, 1, EPI, 8, false, true, 4>), grid8, dim3(512), lds8, st, g);
+      hipLaunchKernelGGL((gemm_nt_lds_kernel<8, 1, EPI, 8, true, 4>), grid8, dim3(512), lds8, st, g);
       GSS_LAUNCH_CHECK("gemm_nt_lds_kernel (8 waves)");
       return GSS_OK;
     }
@@ -879,11 +835,11 @@ static int launch_gemm(const GemmArgs &g_in, int d, hipStream_t st) {
         dim3 gridn(ceil_div(g.n, 128), 1);
         const size_t ldsn = 4 * (size_t)(128 * 16 + 256 * 16) * sizeof(float);
         if (K().gemm_variant != 3) {
-          hipLaunchKernelGGL((gemm_nt_lds_kernel<16, 1, EPI_FWD_NORM, 8, false, true, 2>), gridn, dim3(512), lds_request(gemm_nt_lds_kernel<16, 1, EPI_FWD_NORM, 8, false, true, 2>, ldsn), st, g);
+          hipLaunchKernelGGL((gemm_nt_lds_kernel<16, 1, EPI_FWD_NORM, 8, true, 2>), gridn, dim3(512), lds_request(gemm_nt_lds_kernel<16, 1, EPI_FWD_NORM, 8, true, 2>, ldsn), st, g);
           GSS_LAUNCH_CHECK("gemm_nt_lds_kernel (256 features, fused row norm, 8 waves)");
           return GSS_OK;
         }
-        hipLaunchKernelGGL((gemm_nt_lds_kernel<16, 2, EPI_FWD_NORM, 4, false, true>), gridn, dim3(256), lds_request(gemm_nt_lds_kernel<16, 2, EPI_FWD_NORM, 4, false, true>, ldsn), st, g);
+        hipLaunchKernelGGL((gemm_nt_lds_kernel<16, 2, EPI_FWD_NORM, 4, true>), gridn, dim3(256), lds_request(gemm_nt_lds_kernel<16, 2, EPI_FWD_NORM, 4, true>, ldsn), st, g);
         GSS_LAUNCH_CHECK("gemm_nt_lds_kernel (256 features, fused row norm)");
         return GSS_OK;
       }
@@ -895,9 +851,9 @@ static int launch_gemm(const GemmArgs &g_in, int d, hipStream_t st) {
 #define GSS_GEMM_LINES(NTV)                                                                             \
   case NTV:                                                                                             \
     if (mt == 2)                                                                                        \
-      hipLaunchKernelGGL((gemm_nt_lds_kernel<NTV, 2, E, 4, false, true>), grid, dim3(256), lds, st, g); \
+      hipLaunchKernelGGL((gemm_nt_lds_kernel<NTV, 2, E, 4, true>), grid, dim3(256), lds, st, g);        \
     else                                                                                                \
-      hipLaunchKernelGGL((gemm_nt_lds_kernel<NTV, 1, E, 4, false, true>), grid, dim3(256), lds, st, g); \
+      hipLaunchKernelGGL((gemm_nt_lds_kernel<NTV, 1, E, 4, true>), grid, dim3(256), lds, st, g);        \
     break;
       switch (nt) {
         GSS_GEMM_LINES(8)

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define GSS_ABI_VERSION 7   /* 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
+#define GSS_ABI_VERSION 8   /* 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
 
 #define GSS_OK 0
 #define GSS_EINVAL (-22)   /* bad argument (shape, null pointer, unsupported d) */
@@ -44,10 +44,6 @@ int gss_abi_version(void);
  * measured; bench.py drops a counter file whose recorded spmm.hip hash is not this library's, __graft_entry__.build() rebuilds a library
  * whose hashes are not the tree's (a stale .so with fresh timestamps cannot pass for a current one). */
 const char *gss_source_hash(const char *file);
-/* Diagnostic builds of a measurement only (tools/gemm_stamps.py): while a device buffer is set, every wave of a projection launch
- * (gss_dense_fwd) stores its wall-clock stamps {start, loop begin, loop end, end} + {workgroup id, HW_ID} there (6 x 8 bytes per wave).
- * NULL (the default) switches it off; no production path sets it. */
-int gss_debug_set_stamp_buffer(void *device_buffer);
 /* measurement aid (tools/ab_live.py): changes one KERNEL-SELECTION knob ("gemm_variant", "gemm_ws", "spmm_slices", "spmm_pin", "spmm_list_blocks") in a live
  * plan's snapshot, so that one plan -- the same buffers at the same addresses --
  * can be timed under alternating settings; knobs that size a workspace or steer the plan's bookkeeping are refused (GSS_EINVAL).
@@ -180,7 +176,9 @@ int gss_comm_create_local(gss_comm **out /* [world] */, int32_t world);
  * of them running says nothing about one rank's kernels.  mode 1 = record: keep a device copy of what every collective DELIVERS to this
  * rank, in call order; mode 2 = replay: serve those copies again (same call sequence and sizes, checked) by a device-to-device copy --
  * no peers, no barrier, no host wait -- so that one rank's step can run alone on the GPU and be timed; mode 0 (default) = normal, frees
- * the log.  gss_comm_local_log: the delivered bytes of every recorded collective (n_out = how many there are; at most cap are written). */
+ * the log.  gss_comm_local_log: the delivered bytes of every recorded collective (n_out = how many there are; at most cap are written).
+ * Besides the collectives of the steps, gss_plan_create_sharded at world > 1 runs one all-gather (the job-wide knob check), which a log
+ * recorded across a plan's creation also holds. */
 int gss_comm_local_mode(gss_comm *c, int32_t mode);
 int gss_comm_local_log(gss_comm *c, int64_t *bytes_out, int32_t cap, int32_t *n_out);
 /* A third backend for boxes where RCCL cannot run the job: one PROCESS per rank as with RCCL, but every collective is staged through
@@ -538,8 +536,8 @@ enum {
 };
 int gss_plan_profile(gss_plan *p, int enable);
 int gss_plan_profile_read(gss_plan *p, double *ms_out, int64_t *count_out, void *stream);
-/* tuning/debug knobs (A/B runs inside one process; 18 of them since round 6 -- the access-shape variants whose sweeps said "default holds" in
- * two or more rounds were removed from the kernels): "spmm_list_blocks" = workgroups from which a ROW-FILTERED balanced SpMM (the lazy step's
+/* tuning/debug knobs (A/B runs inside one process; 19 of them -- round 6 removed the access-shape variants whose sweeps said "default holds" in
+ * two or more rounds from the kernels): "spmm_list_blocks" = workgroups from which a ROW-FILTERED balanced SpMM (the lazy step's
  * top-layer products, the batch-sparse backward hop) lists the workgroups that hold a passing row and walks the list with persistent
  * workgroups instead of dispatching every workgroup (default 2048; 0 = never; same bits); "spmm_variant" = 1 (whole-row gather, wave per row) or
  * 2 (nnz-balanced segments, default); "spmm_slices" = 0 (automatic, default) or 1..8 feature slices in the balanced SpMM, "spmm_pin" = with a
@@ -558,7 +556,7 @@ int gss_plan_profile_read(gss_plan *p, double *ms_out, int64_t *count_out, void 
  * loss finish and the batch rows' input gradient in one launch instead of two (same bits; on a shard it spares a collective); "prep_side" = 1 (default) / 0: on one GPU a step's batch preparation rides in its
  * first forward SpMM launch and E_B comes out of the top layer's projection (no batch_prepare / gather launch; same bits);
  * JOB-WIDE knobs -- "lazy_halo", "lazy_halo_u", "halo_recompute", "loss_slab" -- must have the same value on every rank:
- * gss_plan_create_sharded compares them across the ranks (one all-reduce of min / max) and fails by name when they differ;
+ * gss_plan_create_sharded all-gathers every rank's values and compares them on the host, and fails by name when they differ;
  * "loss_slab" = -1 (default: batches of >= 8192
  * rows) / 0 / 1: sharded plans sweep the B x B loss as row slabs (rank r the i tiles r, r + P, ...; one more all-reduce of B d + 1
  * floats) instead of replicating it on every rank (every rank of a job must use the same value; results agree to rounding).  Every setting computes the same results (some in a different summation order); the defaults are

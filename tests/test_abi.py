@@ -98,11 +98,21 @@ def test_library_carries_the_hashes_of_the_sources_in_the_tree(lib):
 
 
 def test_removed_knobs_are_refused_by_name(lib):
-    """round 6 pruned the access-shape knobs: 17 remain, the removed names are errors, not silent no-ops"""
+    """round 6 pruned the access-shape knobs: the removed names are errors, not silent no-ops, and 19 remain --
+    one `struct Knobs` field per name gss_debug_set_option accepts"""
     for name in ("gemm_ws_mode", "gemm_ws_stagger", "gemm_ws_wgs", "wgrad_variant", "spmm_fly", "gemm_small_nt", "gemm_nt_cap",
                  "gemm_lines", "gemm_hoist", "gemm_rows_split", "wgrad_deep", "spmm_pair", "xcd_remap"):
         assert lib.gss_debug_set_option(name.encode(), 1) != 0, name
         assert name in lib.gss_last_error().decode()
     text = open(os.path.join(ROOT, "gcn-drug-repurposing_amd", "csrc", "common.h")).read()
     body = text[text.index("struct Knobs {"):text.index("};", text.index("struct Knobs {"))]
-    assert len(re.findall(r"^  int \w+ = ", body, flags=re.M)) <= 20
+    fields = re.findall(r"^  int \w+ = ", body, flags=re.M)
+    api = open(os.path.join(ROOT, "gcn-drug-repurposing_amd", "csrc", "api.hip")).read()
+    names = re.findall(r'strcmp\(name, "(\w+)"\) == 0', api)
+    assert len(set(names)) == len(names) == len(fields) == 19, (len(names), len(fields))
+
+
+def test_stamp_instrumentation_is_not_exported(lib):
+    """ABI 8 dropped the projection kernels' diagnostic wall-clock stamps and their entry point"""
+    with pytest.raises(AttributeError):
+        lib.gss_debug_set_stamp_buffer

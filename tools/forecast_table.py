@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""profiles/r06_scaling_forecast_*.json (tools/forecast_r06.sh -> tools/scaling_forecast.py) -> the markdown table of DESIGN.md section 8.
+"""profiles/r06_scaling_forecast_*.json (tools/scaling_forecast.py) -> the markdown table of DESIGN.md section 8.
 usage: forecast_table.py "<label>::<file>" ..."""
 import json
 import sys

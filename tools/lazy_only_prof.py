@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """config 2, LAZY steps only (gss_plan_step_lazy with layer 1's SpMM results kept: the step train.py runs) -- for a rocprofv3
---kernel-trace --stats run whose per-kernel averages are not mixed with the full step's (tools/profile_r04.sh)"""
+--kernel-trace --stats run whose per-kernel averages are not mixed with the full step's (profiles/r04_lazy_step_kernel_stats.csv, r05_lazy_step_kernel_stats.csv)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
