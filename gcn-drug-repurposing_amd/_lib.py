@@ -9,7 +9,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgssgcn.so")
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 _lib = None
 
@@ -38,6 +38,10 @@ class SgnsDesc(C.Structure):
     _fields_ = ([(k, C.c_int32) for k in ("n", "d", "walk_length", "window", "negative", "epochs")] + [("n_walks", C.c_int64)]
                 + [(k, C.c_void_p) for k in ("walks", "lengths", "cum_table", "sample_int")]
                 + [("cum_last", C.c_uint32), ("alpha", C.c_float), ("min_alpha", C.c_float), ("seed", C.c_uint64), ("concurrency", C.c_int32)])
+
+
+class ProxSets(C.Structure):
+    _fields_ = [("n_sets", C.c_int32), ("max_size", C.c_int32)] + [(k, C.c_void_p) for k in ("nodes", "sizes", "inner", "centres", "n_centres")]
 
 
 class HaloDesc(C.Structure):
@@ -154,6 +158,13 @@ SIGNATURES = {
     "gss_sgns_init": (C.c_int, [_I32, _I32, C.c_uint64, _P, _P, _P]),
     "gss_sgns_default_concurrency": (C.c_int, []),
     "gss_sgns_epoch": (C.c_int, [C.POINTER(SgnsDesc), _I32, _P, _P, _P]),
+    "gss_prox_create": (C.c_int, [C.POINTER(_P), _I32, _P, _P, _I64, _P]),
+    "gss_prox_destroy": (None, [_P]),
+    "gss_prox_distances": (_P, [_P]),
+    "gss_prox_diameter": (_I32, [_P]),
+    "gss_prox_random_sets": (C.c_int, [_P, _I32, _I32, _P, _P, _I32, _P, _P, _P, _I32, C.c_uint64, _P, _P, _P]),
+    "gss_prox_set_stats": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
+    "gss_prox_score": (C.c_int, [_P, C.POINTER(ProxSets), C.POINTER(ProxSets), _I32, _I64, _P, _P, _I32, _P, _P]),
 }
 
 

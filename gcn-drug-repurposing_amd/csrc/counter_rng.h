@@ -1,4 +1,4 @@
-// counter_rng.h -- the counter-based generator of the node2vec kernels (walk.hip, sgns.hip).
+// counter_rng.h -- the counter-based generator of the node2vec kernels (walk.hip, sgns.hip) and of proximity.hip's random sets.
 //
 // Every random number is a pure function of (seed, stream tag, three 64-bit counters): no state is carried between draws, so
 // walks and SGNS are bitwise reproducible run to run, independent of the launch shape, and replayable by a numpy statement of
@@ -17,6 +17,8 @@ enum RngTag : uint64_t {
   kRngKeep = 4,    // (epoch, token, 0)
   kRngNeg = 5,     // (epoch, center token, context token * 64 + k)
   kRngInit = 6,    // (node, component, 0)
+  kRngProxFrom = 7,  // proximity random sets of the from-side (drug targets): (set, sample, member * 32 + attempt)
+  kRngProxTo = 8,    // proximity random sets of the to-side (disease genes): (set, sample, member * 32 + attempt)
 };
 
 __host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define GSS_ABI_VERSION 8   /* 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
+#define GSS_ABI_VERSION 9   /* 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
 
 #define GSS_OK 0
 #define GSS_EINVAL (-22)   /* bad argument (shape, null pointer, unsupported d) */
@@ -336,6 +336,45 @@ int gss_sgns_counts(int64_t n_walks, int32_t walk_length, const int32_t *walks, 
 int gss_sgns_init(int32_t n, int32_t d, uint64_t seed, float *syn0, float *syn1neg, void *stream);
 int gss_sgns_default_concurrency(void);
 int gss_sgns_epoch(const gss_sgns_desc *desc, int32_t epoch, float *syn0, float *syn1neg, void *stream);
+
+/* ---- network proximity of drug targets to disease genes: Guney et al. 2016 (method/test_proximity.py, toolbox wrappers.calculate_proximity)
+ * gss_prox_create: all-pairs hop distances of an undirected graph (symmetric CSR, no self loops, rowptr/col device) into a uint8 [n][n]
+ * matrix owned by the handle (255 = unreachable).  Refuses n * n > max_bytes and a graph with a node 255 or more hops from another
+ * (GSS_EINVAL, by name).  Synchronises the stream.  gss_prox_distances: the device matrix; gss_prox_diameter: the largest finite hop count.
+ * Sets are LCC node indices.  A set table holds n_sets x n_samples compacted sets of at most max_size nodes, ascending: nodes
+ * [n_sets][n_samples][max_size], sizes [n_sets][n_samples].  Sample 0 is the set itself, sample r >= 1 the random set k = r - 1.
+ * gss_prox_random_sets: from the sets in CSR form (set_ptr [n_sets + 1], set_nodes ascending unique) and the degree bins (node_bin [n],
+ * bin_ptr, bin_nodes), writes the table with n_samples = n_random + 1.  Random set k walks the members v_i in order: draw a node of v_i's bin,
+ * redraw (at most 20 times) while it is already in the set, add it if it is not; draw a of member i of set s is
+ * bin_nodes[lo + (u32 * bin size >> 32)], u32 keyed by (seed, 7 + side, s, k, i * 32 + a) in counter_rng.h.  side: 0 from, 1 to.
+ * Synchronises the stream (validates the member indices).
+ * gss_prox_set_stats: per (set, sample): inner = mean over members of the hop count to the closest other member (0 for fewer than 2);
+ * with centres / n_centres: every member whose summed distance to the set is minimal, ascending (centres laid out like nodes).
+ * gss_prox_score: for every pair (pair_from[q], pair_to[q]), or all n_from x n_to pairs q = i * n_to + j when the lists are NULL, and every
+ * sample r, the five measures of (from sample r, to sample r): closest = mean_t min_s D, shortest = mean D, kernel = -mean_t
+ * ln(sum_s e^-(D+1) / |S|), center = mean D(t, c) over t and the tied centres, separation = (sum_t min_s D + sum_s min_t D) / (|T| + |S|)
+ * - (inner_from + inner_to) / 2.  out [n_pairs][5 measures][5] = d (sample 0), mean and population sd over samples 1.., z = (d - m) / sd
+ * (0 when sd = 0), pval = Phi(z), all fp64 in a fixed order (bitwise reproducible); NaN where a set is empty.  measures: bit mask
+ * (1 closest, 2 shortest, 4 kernel, 8 center, 16 separation); closest and shortest always come out, unmasked others are 0.  The
+ * to-side max_size must be <= 4096. */
+typedef struct gss_prox gss_prox;
+typedef struct gss_prox_sets {
+  int32_t n_sets, max_size;
+  const int32_t *nodes, *sizes;       /* the set table (device) */
+  const double *inner;                /* [n_sets][n_samples] from gss_prox_set_stats */
+  const int32_t *centres, *n_centres; /* to-side, for center; may be NULL otherwise */
+} gss_prox_sets;
+int gss_prox_create(gss_prox **out, int32_t n, const int32_t *rowptr, const int32_t *col, int64_t max_bytes, void *stream);
+void gss_prox_destroy(gss_prox *p);
+const uint8_t *gss_prox_distances(const gss_prox *p);
+int32_t gss_prox_diameter(const gss_prox *p);
+int gss_prox_random_sets(gss_prox *p, int32_t side, int32_t n_sets, const int32_t *set_ptr, const int32_t *set_nodes, int32_t max_size,
+                         const int32_t *node_bin, const int32_t *bin_ptr, const int32_t *bin_nodes, int32_t n_random, uint64_t seed,
+                         int32_t *out_nodes, int32_t *out_size, void *stream);
+int gss_prox_set_stats(gss_prox *p, int32_t n_sets, int32_t n_samples, int32_t max_size, const int32_t *nodes, const int32_t *sizes,
+                       double *inner, int32_t *centres, int32_t *n_centres, void *stream);
+int gss_prox_score(gss_prox *p, const gss_prox_sets *from, const gss_prox_sets *to, int32_t n_samples, int64_t n_pairs,
+                   const int32_t *pair_from, const int32_t *pair_to, int32_t measures, double *out, void *stream);
 
 /* ---- a13  np.savetxt('graph_embs.txt', hidden_emb), train.py:193 (host-side; h_emb is a HOST pointer) ---------------------
  * Every value of the float32 matrix as Python prints it with '%.18e' after widening to double (exact decimal expansion, round
