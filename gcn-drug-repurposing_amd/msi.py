@@ -29,6 +29,29 @@ COVID_WEIGHTS = {  # predict_drug.py:173-180
 }
 
 
+# the strings pandas.read_csv reads as NaN by default (keep_default_na): MSI's tables go through read_csv(dtype=str), so such a name
+# cell is missing there (node_to_node.py:85-88) and the reference prints the node id instead
+NA_STRINGS = frozenset(["", "#N/A", "#N/A N/A", "#NA", "-1.#IND", "-1.#QNAN", "-NaN", "-nan", "1.#IND", "1.#QNAN", "<NA>", "N/A", "NA",
+                        "NULL", "NaN", "None", "n/a", "nan", "null"])
+
+
+def read_name_table(path):
+    """node_1 / node_2 with node_1_name / node_2_name of one MSI edge table -> [(node_1, name_1, node_2, name_2)], None for a missing
+    name (a cell pandas reads as NaN, or a table without the column)"""
+    with open(path, newline="") as f:
+        rows = csv.reader(f, delimiter="\t")
+        header = next(rows)
+        i1, i2 = header.index("node_1"), header.index("node_2")
+        n1 = header.index("node_1_name") if "node_1_name" in header else None
+        n2 = header.index("node_2_name") if "node_2_name" in header else None
+
+        def name(r, i):
+            if i is None or i >= len(r) or r[i] in NA_STRINGS:
+                return None
+            return r[i]
+        return [(r[i1], name(r, n1), r[i2], name(r, n2)) for r in rows if len(r) > max(i1, i2)]
+
+
 def read_node_table(path):
     """node_1 / node_2 columns of one MSI edge table (multiscale/msi/node_to_node.py:85-95)"""
     with open(path, newline="") as f:
@@ -45,6 +68,7 @@ class MsiGraph:
         self.up = {}         # pathway -> set of parents (node_1 -> node_2 rows of the GO table)
         self.down = {}
         self.drug_or_indication2proteins = {}   # MSI.load_drug_or_indication2proteins (msi.py:192-205)
+        self.node2name = {}  # MSI.load_node2name (msi.py:98-103); None where the name cell is missing
 
     # -- MSI.load_graph ------------------------------------------------------------------------------------
     def _add_edge(self, u, v):
@@ -72,7 +96,16 @@ class MsiGraph:
                 if name == "functional_pathway_to_functional_pathway":
                     self.up.setdefault(u, set()).add(v)
                     self.down.setdefault(v, set()).add(u)
+            self._load_names(files[name])
         return self
+
+    def _load_names(self, path):
+        """node_to_node.py:103-133 + msi.py:70-79: per table all node_1 names in row order, then all node_2 names; the first value
+        seen for a node wins, across tables in load order"""
+        rows = read_name_table(path)
+        for k in (0, 2):
+            for r in rows:
+                self.node2name.setdefault(r[k], r[k + 1])
 
     # -- MSI.weight_graph ------------------------------------------------------------------------------------
     def _class_of(self, node, succ):

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define GSS_ABI_VERSION 9   /* 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
+#define GSS_ABI_VERSION 10  /* 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
 
 #define GSS_OK 0
 #define GSS_EINVAL (-22)   /* bad argument (shape, null pointer, unsupported d) */
@@ -375,6 +375,27 @@ int gss_prox_set_stats(gss_prox *p, int32_t n_sets, int32_t n_samples, int32_t m
                        double *inner, int32_t *centres, int32_t *n_centres, void *stream);
 int gss_prox_score(gss_prox *p, const gss_prox_sets *from, const gss_prox_sets *to, int32_t n_samples, int64_t n_pairs,
                    const int32_t *pair_from, const int32_t *pair_to, int32_t measures, double *out, void *stream);
+
+/* ---- shortest-path trees toward up to 64 targets per pass (predict_drug.py:268-273, run_covid.py:310-319: one networkx
+ * shortest_path per table row; here one search toward each target answers every row) ------------------------------------------
+ * Directed graph as a CSR: rowptr [n + 1], col [nnz], the columns of every row ascending (MsiGraph.to_csr, embio's edgelist reader).
+ * gss_paths_create: on_device = 0 uploads host rowptr / col into the handle, 1 borrows device pointers (they must outlive it).
+ * Validates the CSR on the device (GSS_EINVAL by name: a bad row pointer, a column out of range, a row not ascending) and
+ * allocates 24 n bytes of state.  max_bytes bounds one pass (below); synchronises the stream.
+ * gss_paths_run: targets t[0..q) (HOST int32, 1 <= q <= 64, any node index, repeats allowed) -> per target i, device
+ *   dist [q][n] uint8: hop count of the shortest directed path v -> t_i, 255 = unreachable;
+ *   next [q][n] int32: the first hop of that path, -1 at t_i and wherever v cannot reach t_i.
+ * Tie rule (the contract): next is the successor with the smallest node index that is one hop closer, so following next spells a
+ * shortest path v -> t_i in the direction of nx.shortest_path(G, source=v, target=t_i).  Bitwise deterministic.  Level-synchronous
+ * and bottom-up (one launch per level, the host reads a "changed" word after each: the call synchronises the stream per level).
+ * levels (may be NULL): the number of levels that found something = the largest finite dist.  Refuses (GSS_EINVAL, by name) q out
+ * of range, a target out of range, a pass above the budget (5 q n bytes of output + 24 n of state > max_bytes) and a graph where
+ * some node lies 255 or more hops from a target. */
+typedef struct gss_paths gss_paths;
+int gss_paths_create(gss_paths **out, int32_t n, int64_t nnz, const int32_t *rowptr, const int32_t *col, int32_t on_device,
+                     int64_t max_bytes, void *stream);
+int gss_paths_run(gss_paths *p, int32_t q, const int32_t *targets, uint8_t *dist, int32_t *next, int32_t *levels, void *stream);
+void gss_paths_destroy(gss_paths *p);
 
 /* ---- a13  np.savetxt('graph_embs.txt', hidden_emb), train.py:193 (host-side; h_emb is a HOST pointer) ---------------------
  * Every value of the float32 matrix as Python prints it with '%.18e' after widening to double (exact decimal expansion, round
