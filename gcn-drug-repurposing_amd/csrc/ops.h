@@ -1,27 +1,50 @@
 // ops.h -- internal launchers shared between the per-op C entry points and the plan.
 #pragma once
+#include <memory>
 #include <vector>
 
 #include "common.h"
 
+struct gss_giant_rows;
+
 struct gss_csr {
-  int32_t n_rows, n_cols;
-  int64_t nnz;
-  const int32_t *rowptr, *col;
-  const float *val;
-  int32_t n_long;
-  int32_t *d_long_rows;
-  int32_t max_row;
-  int32_t hot_own, hot_halo0, hot_halo1;  // gss_csr_set_hot: operand rows [0, hot_own) and [hot_halo0, hot_halo1) are the hubs' (-1: no split)
+  int32_t n_rows = 0, n_cols = 0;
+  int64_t nnz = 0;
+  const int32_t *rowptr = nullptr, *col = nullptr;   // borrowed
+  const float *val = nullptr;
+  int32_t n_long = 0;
+  int32_t *d_long_rows = nullptr;
+  int32_t max_row = 0;
+  int32_t hot_own = -1, hot_halo0 = 0, hot_halo1 = 0;  // gss_csr_set_hot: operand rows [0, hot_own) and [hot_halo0, hot_halo1) are the hubs' (-1: no split)
+  int32_t seg_edges = 32;         // entries per segment of the balanced SpMM: knob spmm_seg_edges at gss_csr_create (a view: its parent's)
   std::vector<int32_t> h_rowptr;  // host copy, used to build segment descriptors lazily
-  int32_t *d_segs[5];             // balanced SpMM: int4 descriptors per lane group, by log2(groups per wave)
-  int32_t n_seg_blocks[5];
-  int32_t *d_live[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // row-filtered launches over many workgroups: [0] = count, [1 ..] = the workgroups (segment blocks) that hold a row the filter lets through (spmm.hip live_blocks_kernel)
   // a VIEW (spmm.hip GiantRows): the schedule covers the listed rows / entry ranges of the borrowed arrays instead of every row of rowptr
   bool by_items = false;
   std::vector<int32_t> item_row, item_first, item_len;
-  struct gss_giant_rows *giant = nullptr;   // rows too long for one workgroup, cut into chunks (built on first use; spmm.hip)
-  int32_t giant_threshold = -1;             // the knob value `giant` was built (or found empty) for; -1 = not looked at yet
+  // What the handle builds after creation, on first use (spmm.hip).  Mutable: the launchers take const handles, and a handle is driven
+  // from one host thread.  ~gss_csr frees it.
+  struct Cache {
+    int32_t *segs[5] = {};        // balanced SpMM: int4 descriptors per lane group, by log2(groups per wave)
+    int32_t seg_blocks[5] = {};
+    std::unique_ptr<gss_giant_rows> giant;   // rows too long for one workgroup, cut into chunks (NULL: none)
+    int32_t giant_threshold = -1;            // the knob value `giant` was built (or found empty) for; -1 = not looked at yet
+    // device scratch by (stream, slot): a plan's pipelined / overlapped hops run products of one matrix on two streams.  Allocated by
+    // the first launch of a (stream, slot) and grown, never shrunk -- nothing is allocated per product
+    struct Scratch {
+      hipStream_t st;
+      int slot;
+      void *buf;
+      size_t bytes;
+    };
+    std::vector<Scratch> scratch;
+    int scratch_for(hipStream_t st, int slot, size_t bytes, void **out);
+  };
+  mutable Cache cache;
+
+  gss_csr() = default;
+  gss_csr(const gss_csr &) = delete;
+  gss_csr &operator=(const gss_csr &) = delete;
+  ~gss_csr();
 };
 
 // communicator interface of the sharded plan (comm.hip): RCCL, or threads of one process

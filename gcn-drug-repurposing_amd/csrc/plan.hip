@@ -333,6 +333,7 @@ static int check_job_knobs(gss_comm *comm, const Knobs &k) {
 
 int plan_create_impl(gss_plan **out, const gss_plan_desc *desc, const gss_shard_desc *shard, gss_comm *comm, const gss_csr *a,
                      const gss_csr *at, const gss_plan_io *io) {
+  const Knobs snap = g_knobs;   // read once: the value the ranks compare is the value the plan keeps
   GSS_REQUIRE(out && desc && a && io, "plan_create: null argument");
   GSS_REQUIRE(io->w1 && io->b1 && io->w2 && io->b2 && io->loss && io->gw1 && io->gb1 && io->gw2 && io->gb2,
               "plan_create: null pointer in gss_plan_io");
@@ -385,9 +386,9 @@ int plan_create_impl(gss_plan **out, const gss_plan_desc *desc, const gss_shard_
     }
   }
   if (P > 1)
-    if (int rc = check_job_knobs(comm, g_knobs)) return rc;
+    if (int rc = check_job_knobs(comm, snap)) return rc;
   gss_plan *p = new gss_plan();
-  p->knobs = g_knobs;
+  p->knobs = snap;
   KnobScope knob_scope(&p->knobs);
   p->desc = *desc;
   p->comm = P > 1 ? comm : nullptr;

@@ -691,30 +691,34 @@ static int launch_spmm_t(const gss_csr *a, int d4, const float *x, const SpmmEpi
 }
 
 
+// slots of gss_csr::Cache::scratch
+constexpr int kScratchLive = 0;        // + log2(groups per wave): the live-workgroup list of that width class (live_blocks_kernel)
+constexpr int kScratchChunkSums = 5;   // the giant rows' chunk partial sums (launch_giant)
+
 // Segment descriptors for the balanced kernel, built on first use for a given groups-per-wave count.
 int csr_segments(const gss_csr *a, int gpw_log2, const int4 **out, int *n_blocks) {
-  gss_csr *m = const_cast<gss_csr *>(a);  // lazily filled cache; a gss_csr is used from one host thread
-  if (m->d_segs[gpw_log2]) {
-    *out = (const int4 *)m->d_segs[gpw_log2];
-    *n_blocks = m->n_seg_blocks[gpw_log2];
+  gss_csr::Cache &c = a->cache;
+  if (c.segs[gpw_log2]) {
+    *out = (const int4 *)c.segs[gpw_log2];
+    *n_blocks = c.seg_blocks[gpw_log2];
     return GSS_OK;
   }
   std::vector<int32_t> segs;
   int nblk = 0;
-  if (m->by_items) {
-    std::vector<SegItem> items(m->item_row.size());
-    for (size_t i = 0; i < items.size(); ++i) items[i] = SegItem{m->item_row[i], m->item_first[i], m->item_len[i]};
-    nblk = build_segments_items(items.data(), items.size(), kBalWaves, gpw_log2, K().seg_edges, segs);
+  if (a->by_items) {
+    std::vector<SegItem> items(a->item_row.size());
+    for (size_t i = 0; i < items.size(); ++i) items[i] = SegItem{a->item_row[i], a->item_first[i], a->item_len[i]};
+    nblk = build_segments_items(items.data(), items.size(), kBalWaves, gpw_log2, a->seg_edges, segs);
   } else {
-    nblk = build_segments(m->h_rowptr.data(), a->n_rows, kBalWaves, gpw_log2, K().seg_edges, segs);
+    nblk = build_segments(a->h_rowptr.data(), a->n_rows, kBalWaves, gpw_log2, a->seg_edges, segs);
   }
   const size_t bytes = segs.size() * sizeof(int32_t);
   if (bytes) {
-    GSS_HIP(hipMalloc((void **)&m->d_segs[gpw_log2], bytes));
-    GSS_HIP(hipMemcpy(m->d_segs[gpw_log2], segs.data(), bytes, hipMemcpyHostToDevice));
+    GSS_HIP(hipMalloc((void **)&c.segs[gpw_log2], bytes));
+    GSS_HIP(hipMemcpy(c.segs[gpw_log2], segs.data(), bytes, hipMemcpyHostToDevice));
   }
-  m->n_seg_blocks[gpw_log2] = nblk;
-  *out = (const int4 *)m->d_segs[gpw_log2];
+  c.seg_blocks[gpw_log2] = nblk;
+  *out = (const int4 *)c.segs[gpw_log2];
   *n_blocks = nblk;
   return GSS_OK;
 }
@@ -750,21 +754,21 @@ static int launch_balanced_t(const gss_csr *a, int d4_slice, int nslices, bool p
     const int list_min = K().spmm_list_blocks;
     const bool sparse_enough = list_min == 1 || t_live_hint <= 0 || t_live_hint * 4 < (int64_t)a->n_rows;   // (LiveHint: mostly-live launches keep the hardware's dispatch; knob value 1 = always: tests)
     if ((f.pos || f.bits) && !prep && list_min > 0 && nblk >= list_min && sparse_enough) {
-      gss_csr *m = const_cast<gss_csr *>(a);   // lazily allocated scratch of the handle (one stream at a time, like the handle's other caches)
-      const int k = 6 - LPR_LOG2;
-      if (!m->d_live[k]) GSS_HIP(hipMalloc((void **)&m->d_live[k], sizeof(int32_t) * ((size_t)nblk + 1)));
-      GSS_HIP(hipMemsetAsync(m->d_live[k], 0, sizeof(int32_t), st));
-      hipLaunchKernelGGL(live_blocks_kernel, dim3(ceil_div(nblk, 4)), dim3(256), 0, st, segs, nblk, kBalWaves * (64 >> LPR_LOG2), f, m->d_live[k]);
+      void *buf = nullptr;   // [0] = count, [1 ..] = the workgroups (segment blocks) that hold a row the filter lets through
+      if (int rc = a->cache.scratch_for(st, kScratchLive + 6 - LPR_LOG2, sizeof(int32_t) * ((size_t)nblk + 1), &buf)) return rc;
+      int32_t *live = static_cast<int32_t *>(buf);
+      GSS_HIP(hipMemsetAsync(live, 0, sizeof(int32_t), st));
+      hipLaunchKernelGGL(live_blocks_kernel, dim3(ceil_div(nblk, 4)), dim3(256), 0, st, segs, nblk, kBalWaves * (64 >> LPR_LOG2), f, live);
       GSS_LAUNCH_CHECK("live_blocks_kernel");
       int gx = std::min(nblk, kListWorkgroups);
       if (pin) gx = std::max(nslices, gx / nslices * nslices);   // a multiple of the slice count: a workgroup keeps its slice
       const dim3 grid = pin ? dim3(gx) : dim3(gx, nslices);
       if (narrow)
         hipLaunchKernelGGL((spmm_balanced_list_kernel<MODE, LPR_LOG2, VPL, true>), grid, dim3(kBalThreads), lds, st, v, segs, d4_slice, x, ep,
-                           d4_slice * nslices * 4, pin ? nslices : 0, make_int3(-1, 0, 0), (const int32_t *)m->d_live[k]);
+                           d4_slice * nslices * 4, pin ? nslices : 0, make_int3(-1, 0, 0), (const int32_t *)live);
       else
         hipLaunchKernelGGL((spmm_balanced_list_kernel<MODE, LPR_LOG2, VPL, false>), grid, dim3(kBalThreads), lds, st, v, segs, d4_slice, x, ep,
-                           d4_slice * nslices * 4, pin ? nslices : 0, hot, (const int32_t *)m->d_live[k]);
+                           d4_slice * nslices * 4, pin ? nslices : 0, hot, (const int32_t *)live);
       GSS_LAUNCH_CHECK("spmm_balanced_list_kernel");
       return GSS_OK;
     }
@@ -833,120 +837,95 @@ static int launch_balanced(const gss_csr *a, int d4, const float *x, const SpmmE
 // first pass) keep the single schedule: they test entries, they do not gather for most of them.
 struct gss_giant_rows {
   int32_t n_giant = 0, n_chunks = 0;
-  gss_csr chunks{}, shortv{}, finish{};
+  gss_csr chunks, shortv, finish;
   int32_t *d_chunk_row = nullptr, *d_fin_col = nullptr;
   float *d_fin_val = nullptr;
-  // the chunks' partial sums [n_chunks][d]: one buffer per stream the handle is used on (a plan's pipelined / overlapped hops run products
-  // of one matrix on two streams), grown to the widest d seen -- nothing is allocated per product
-  struct Scratch {
-    hipStream_t st;
-    float *buf;
-    size_t floats;
-  };
-  std::vector<Scratch> scratch;
-  int scratch_for(hipStream_t st, size_t floats, float **out) {
-    for (Scratch &s : scratch)
-      if (s.st == st) {
-        if (s.floats < floats) {
-          GSS_HIP(hipStreamSynchronize(st));   // (a product of a narrower d may still read it)
-          GSS_HIP(hipFree(s.buf));
-          s.buf = nullptr;
-          s.floats = 0;
-          GSS_HIP(hipMalloc((void **)&s.buf, sizeof(float) * floats));
-          s.floats = floats;
-        }
-        *out = s.buf;
-        return GSS_OK;
-      }
-    float *b = nullptr;
-    GSS_HIP(hipMalloc((void **)&b, sizeof(float) * floats));
-    scratch.push_back(Scratch{st, b, floats});
-    *out = b;
-    return GSS_OK;
-  }
-  size_t scratch_bytes() const {
-    size_t t = 0;
-    for (const Scratch &s : scratch) t += sizeof(float) * s.floats;
-    return t;
-  }
   ~gss_giant_rows() {
-    for (Scratch &s : scratch)
-      if (s.buf) (void)hipFree(s.buf);
-    for (gss_csr *v : {&chunks, &shortv, &finish})
-      for (int k = 0; k < 5; ++k) {
-        if (v->d_segs[k]) (void)hipFree(v->d_segs[k]);
-        if (v->d_live[k]) (void)hipFree(v->d_live[k]);
-      }
     if (d_chunk_row) (void)hipFree(d_chunk_row);
     if (d_fin_col) (void)hipFree(d_fin_col);
     if (d_fin_val) (void)hipFree(d_fin_val);
   }
 };
 
+gss_csr::~gss_csr() {
+  if (d_long_rows) (void)hipFree(d_long_rows);
+  for (int32_t *s : cache.segs)
+    if (s) (void)hipFree(s);
+  for (const Cache::Scratch &s : cache.scratch)
+    if (s.buf) (void)hipFree(s.buf);
+}
+
+int gss_csr::Cache::scratch_for(hipStream_t st, int slot, size_t bytes, void **out) {
+  for (Scratch &s : scratch)
+    if (s.st == st && s.slot == slot) {
+      if (s.bytes < bytes) {
+        GSS_HIP(hipStreamSynchronize(st));   // (a product of a narrower d may still read it)
+        GSS_HIP(hipFree(s.buf));
+        s.buf = nullptr;
+        s.bytes = 0;
+        GSS_HIP(hipMalloc(&s.buf, bytes));
+        s.bytes = bytes;
+      }
+      *out = s.buf;
+      return GSS_OK;
+    }
+  void *b = nullptr;
+  GSS_HIP(hipMalloc(&b, bytes));
+  scratch.push_back(Scratch{st, slot, b, bytes});
+  *out = b;
+  return GSS_OK;
+}
+
 namespace gss {
 
-static void giant_view_init(gss_csr &v, const gss_csr *a, int32_t n_rows, int32_t n_cols) {
+// a view of `a`'s arrays that schedules `items` (rows / entry ranges) instead of every row of rowptr
+static void giant_view_init(gss_csr &v, const gss_csr *a, int32_t n_rows, int32_t n_cols, const std::vector<SegItem> &items) {
   v.n_rows = n_rows;
   v.n_cols = n_cols;
-  v.nnz = 0;
   v.rowptr = a->rowptr;   // (the balanced kernel reads descriptors, not rowptr)
   v.col = a->col;
   v.val = a->val;
-  v.n_long = 0;
-  v.d_long_rows = nullptr;
-  v.max_row = 0;
   v.hot_own = a->hot_own;
   v.hot_halo0 = a->hot_halo0;
   v.hot_halo1 = a->hot_halo1;
-  for (int k = 0; k < 5; ++k) {
-    v.d_segs[k] = nullptr;
-    v.n_seg_blocks[k] = 0;
-  }
+  v.seg_edges = a->seg_edges;
   v.by_items = true;
+  v.item_row.reserve(items.size());
+  v.item_first.reserve(items.size());
+  v.item_len.reserve(items.size());
+  for (const SegItem &it : items) {
+    v.item_row.push_back(it.row);
+    v.item_first.push_back(it.first);
+    v.item_len.push_back(it.len);
+  }
 }
 
 // the chunked views of `a`, or NULL when it has no giant row (looked at once per handle, with the knob as it stands then)
 static int csr_giant_rows(const gss_csr *a, gss_giant_rows **out) {
-  gss_csr *m = const_cast<gss_csr *>(a);   // lazily filled cache; a gss_csr is used from one host thread
+  gss_csr::Cache &c = a->cache;
   *out = nullptr;
-  if (m->by_items) return GSS_OK;          // a view itself
+  if (a->by_items) return GSS_OK;          // a view itself
   const int thr = K().spmm_giant;
-  if (m->giant_threshold == thr) {
-    *out = m->giant;
+  if (c.giant_threshold == thr) {
+    *out = c.giant.get();
     return GSS_OK;
   }
-  delete m->giant;
-  m->giant = nullptr;
-  m->giant_threshold = thr;
-  if (thr <= 0 || m->h_rowptr.empty()) return GSS_OK;
-  const int32_t *rp = m->h_rowptr.data();
+  c.giant.reset();
+  c.giant_threshold = thr;
+  if (thr <= 0 || a->h_rowptr.empty()) return GSS_OK;
+  const int32_t *rp = a->h_rowptr.data();
   int64_t n_giant = 0;
   for (int32_t r = 0; r < a->n_rows; ++r) n_giant += (rp[r + 1] - rp[r]) > thr;
   if (n_giant == 0) return GSS_OK;
   GiantItems items;
   (void)giant_items(rp, a->n_rows, thr, items);     // segments.h: host-only, checked under ASan / UBSan by tests/native/segments_check.cpp
-  gss_giant_rows *g = new gss_giant_rows();
-  giant_view_init(g->chunks, a, 0, a->n_cols);
-  giant_view_init(g->shortv, a, a->n_rows, a->n_cols);
-  giant_view_init(g->finish, a, a->n_rows, 0);
-  auto fill = [](gss_csr &v, const std::vector<SegItem> &src) {
-    v.item_row.reserve(src.size());
-    v.item_first.reserve(src.size());
-    v.item_len.reserve(src.size());
-    for (const SegItem &it : src) {
-      v.item_row.push_back(it.row);
-      v.item_first.push_back(it.first);
-      v.item_len.push_back(it.len);
-    }
-  };
-  fill(g->shortv, items.shortv);
-  fill(g->chunks, items.chunks);
-  fill(g->finish, items.finish);
+  std::unique_ptr<gss_giant_rows> g(new gss_giant_rows());
   const std::vector<int32_t> &chunk_row = items.chunk_row;
   g->n_giant = (int32_t)n_giant;
   g->n_chunks = (int32_t)chunk_row.size();
-  g->chunks.n_rows = g->n_chunks;
-  g->finish.n_cols = g->n_chunks;
+  giant_view_init(g->chunks, a, g->n_chunks, a->n_cols, items.chunks);
+  giant_view_init(g->shortv, a, a->n_rows, a->n_cols, items.shortv);
+  giant_view_init(g->finish, a, a->n_rows, g->n_chunks, items.finish);
   g->finish.hot_own = -1;                  // the scratch is small: no hot / cold split
   std::vector<int32_t> fin_col((size_t)g->n_chunks);
   std::vector<float> fin_val((size_t)g->n_chunks, 1.0f);
@@ -957,23 +936,21 @@ static int csr_giant_rows(const gss_csr *a, gss_giant_rows **out) {
   if (e == hipSuccess) e = hipMemcpy(g->d_chunk_row, chunk_row.data(), sizeof(int32_t) * (size_t)g->n_chunks, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(g->d_fin_col, fin_col.data(), sizeof(int32_t) * (size_t)g->n_chunks, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(g->d_fin_val, fin_val.data(), sizeof(float) * (size_t)g->n_chunks, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    delete g;
-    return fail(GSS_EHIP, "spmm: giant-row tables -> %s", hipGetErrorString(e));
-  }
+  if (e != hipSuccess) return fail(GSS_EHIP, "spmm: giant-row tables -> %s", hipGetErrorString(e));
   g->finish.col = g->d_fin_col;
   g->finish.val = g->d_fin_val;
-  m->giant = g;
-  *out = g;
+  c.giant = std::move(g);
+  *out = c.giant.get();
   return GSS_OK;
 }
 
 template <int MODE>
 static int launch_giant(const gss_csr *a, gss_giant_rows *g, int d4, const float *x, const SpmmEpi &ep, hipStream_t st) {
-  (void)a;
-  float *scratch = nullptr;
-  int rc = g->scratch_for(st, 4 * (size_t)d4 * (size_t)g->n_chunks, &scratch);
+  // the chunks' partial sums [n_chunks][d], in the parent handle's scratch: the passes' live-workgroup lists are in the views' own
+  void *buf = nullptr;
+  int rc = a->cache.scratch_for(st, kScratchChunkSums, sizeof(float) * 4 * (size_t)d4 * (size_t)g->n_chunks, &buf);
   if (rc != GSS_OK) return rc;
+  float *scratch = static_cast<float *>(buf);
   {
     // 1. the chunks' partial sums; only chunks of rows the caller's product computes at all
     SpmmEpi pe{};
@@ -1241,57 +1218,30 @@ int gss_csr_create(gss_csr **out, int32_t n_rows, int32_t n_cols, int64_t nnz, c
               n_rows, n_cols, (long long)nnz);
   GSS_REQUIRE(h_rowptr[0] == 0 && (int64_t)h_rowptr[n_rows] == nnz, "csr_create: rowptr[0]=%d rowptr[n]=%d do not match nnz=%lld",
               h_rowptr[0], h_rowptr[n_rows], (long long)nnz);
-  gss_csr *a = new gss_csr();
+  std::unique_ptr<gss_csr> a(new gss_csr());
   a->n_rows = n_rows;
   a->n_cols = n_cols;
   a->nnz = nnz;
   a->rowptr = d_rowptr;
   a->col = d_col;
   a->val = d_val;
-  a->n_long = 0;
-  a->hot_own = -1;
-  a->hot_halo0 = a->hot_halo1 = 0;
-  a->d_long_rows = nullptr;
-  a->max_row = 0;
-  for (int k = 0; k < 5; ++k) {
-    a->d_segs[k] = nullptr;
-    a->n_seg_blocks[k] = 0;
+  a->seg_edges = K().seg_edges;
+  std::vector<int32_t> h_long;
+  for (int32_t r = 0; r < n_rows; ++r) {
+    const int32_t len = h_rowptr[r + 1] - h_rowptr[r];
+    if (len < 0) return fail(GSS_EINVAL, "csr_create: rowptr not monotone at row %d", r);
+    if (len > a->max_row) a->max_row = len;
+    if (len > kLongRow) h_long.push_back(r);
   }
-  int32_t *h_long = nullptr;
-  int n_long = 0;
-  for (int pass = 0; pass < 2; ++pass) {
-    n_long = 0;
-    for (int32_t r = 0; r < n_rows; ++r) {
-      const int32_t len = h_rowptr[r + 1] - h_rowptr[r];
-      if (len < 0) {
-        delete[] h_long;
-        delete a;
-        return fail(GSS_EINVAL, "csr_create: rowptr not monotone at row %d", r);
-      }
-      if (len > a->max_row) a->max_row = len;
-      if (len > kLongRow) {
-        if (pass == 1) h_long[n_long] = r;
-        ++n_long;
-      }
-    }
-    if (pass == 0) {
-      if (n_long == 0) break;
-      h_long = new int32_t[n_long];
-    }
-  }
-  if (n_long > 0) {
-    hipError_t e = hipMalloc((void **)&a->d_long_rows, sizeof(int32_t) * (size_t)n_long);
-    if (e == hipSuccess) e = hipMemcpy(a->d_long_rows, h_long, sizeof(int32_t) * (size_t)n_long, hipMemcpyHostToDevice);
-    delete[] h_long;
-    if (e != hipSuccess) {
-      if (a->d_long_rows) (void)hipFree(a->d_long_rows);
-      delete a;
-      return fail(GSS_ENOMEM, "csr_create: long-row list: %s", hipGetErrorString(e));
-    }
-    a->n_long = n_long;
+  if (!h_long.empty()) {
+    const size_t bytes = sizeof(int32_t) * h_long.size();
+    hipError_t e = hipMalloc((void **)&a->d_long_rows, bytes);
+    if (e == hipSuccess) e = hipMemcpy(a->d_long_rows, h_long.data(), bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(GSS_ENOMEM, "csr_create: long-row list: %s", hipGetErrorString(e));
+    a->n_long = (int32_t)h_long.size();
   }
   a->h_rowptr.assign(h_rowptr, h_rowptr + (size_t)n_rows + 1);
-  *out = a;
+  *out = a.release();
   return GSS_OK;
 }
 
@@ -1302,8 +1252,8 @@ int gss_csr_set_hot(gss_csr *a, int32_t own_hot, int32_t halo_begin, int32_t hal
   a->hot_own = own_hot;
   a->hot_halo0 = halo_begin;
   a->hot_halo1 = halo_end;
-  if (a->giant)   // the views that gather from the same operand follow
-    for (gss_csr *v : {&a->giant->chunks, &a->giant->shortv}) {
+  if (a->cache.giant)   // the views that gather from the same operand follow
+    for (gss_csr *v : {&a->cache.giant->chunks, &a->cache.giant->shortv}) {
       v->hot_own = own_hot;
       v->hot_halo0 = halo_begin;
       v->hot_halo1 = halo_end;
@@ -1321,16 +1271,7 @@ int gss_csr_giant_rows(const gss_csr *a, int32_t *n_rows_out, int32_t *n_chunks_
   return GSS_OK;
 }
 
-void gss_csr_destroy(gss_csr *a) {
-  if (!a) return;
-  delete a->giant;
-  if (a->d_long_rows) (void)hipFree(a->d_long_rows);
-  for (int k = 0; k < 5; ++k) {
-    if (a->d_segs[k]) (void)hipFree(a->d_segs[k]);
-    if (a->d_live[k]) (void)hipFree(a->d_live[k]);
-  }
-  delete a;
-}
+void gss_csr_destroy(gss_csr *a) { delete a; }
 
 
 int gss_spmm(const gss_csr *a, int32_t d, const float *x, float *y, const float *h, float *m, void *stream) {

@@ -560,7 +560,7 @@ int gss_plan_sync_stats(gss_plan *p, int64_t *out2);
  * is ignored for 3 .. 8 */
 const float *gss_plan_activation(const gss_plan *p, int layer, int which);
 /* bytes of the plan's slab.  Not counted: what a gss_csr handle caches for itself -- its segment descriptors, the chunk scratch of giant rows (one
- * buffer per stream the handle is used on, grown to the widest d seen), the live-workgroup list of row-filtered products. */
+ * buffer per stream the handle is used on, grown to the widest d seen), the live-workgroup lists of row-filtered products (one per stream too). */
 size_t gss_plan_device_bytes(const gss_plan *p);
 /* every buffer the plan carves from its slab is followed by a 256-byte guard no kernel may touch; this synchronises the device and
  * verifies them all (GSS_EINVAL names the first one that was overwritten).  For tests. */

@@ -97,6 +97,47 @@ def test_library_carries_the_hashes_of_the_sources_in_the_tree(lib):
     assert pkg._lib.library_is_current()
 
 
+def _fake_library(path, hashes):
+    path.write_bytes(b"\0".join(h.encode() for h in hashes))
+
+
+def test_library_is_current_reads_the_file_each_time(tmp_path, monkeypatch):
+    """library_is_current looks for the digests in the file on disk and loads nothing: a check after the library at the same path was
+    replaced sees the new file (a process that had dlopened the old one would keep getting the old image)"""
+    import gcn_drug_repurposing_amd as pkg
+    lib_path = tmp_path / "libgssgcn.so"
+    monkeypatch.setattr(pkg._lib, "LIB_PATH", str(lib_path))
+    hashes = list(pkg._lib.source_hashes().values())
+    assert not pkg._lib.library_is_current()
+    _fake_library(lib_path, hashes[1:])
+    assert not pkg._lib.library_is_current()
+    _fake_library(lib_path, hashes)
+    assert pkg._lib.library_is_current()
+
+
+def test_build_recovers_from_a_stale_library(tmp_path, monkeypatch):
+    """build() over a library that lacks a digest of this tree: the incremental make leaves it stale, the forced `make -B` replaces it,
+    and build() then succeeds (make is stubbed: no hipcc needed)"""
+    import types
+    import gcn_drug_repurposing_amd as pkg
+    lib_path = tmp_path / "libgssgcn.so"
+    monkeypatch.setattr(pkg._lib, "LIB_PATH", str(lib_path))
+    monkeypatch.delenv("GSS_REBUILD", raising=False)
+    hashes = list(pkg._lib.source_hashes().values())
+    _fake_library(lib_path, hashes[:-1])
+    calls = []
+
+    def make(cmd, **kw):
+        calls.append(cmd)
+        if "-B" in cmd:
+            _fake_library(lib_path, hashes)
+        return subprocess.CompletedProcess(cmd, 0, "", "")
+
+    monkeypatch.setattr(pkg._lib, "subprocess", types.SimpleNamespace(run=make))
+    assert pkg._lib.build() == str(lib_path)
+    assert ["-B" in c for c in calls] == [False, True]
+
+
 def test_removed_knobs_are_refused_by_name(lib):
     """round 6 pruned the access-shape knobs: the removed names are errors, not silent no-ops, and 19 remain --
     one `struct Knobs` field per name gss_debug_set_option accepts"""
