@@ -1,0 +1,254 @@
+"""evaluate_auc.py (evaluate_auc.py:114-171): the median and mean ROC-AUC, over every indication, of ranking all drugs for it by a method's
+scores -- diffusion profiles, raw node2vec inner products or row-normalised GCN inner products -- against the drugs listed for it in
+networks.drug_to_indication.
+
+The reference's embedding branches end in a NameError (dp_saved is only set for diffusion); the evident intent, embedding inner products
+as scores (consumer.py), is what this does.  It crashes on an indication without a row in the label table, on a listed drug that is not in
+the graph and on a single-class label vector; here such indications are skipped and counted on stderr, listed drugs that are not drug
+nodes are left out (consumer.indication_aucs' rules).  Scores stay host fp64 (np.matmul per indication, predict.py's arithmetic; a
+gather from the profiles for diffusion); the ranking statistic of every indication runs in one device launch (csrc/auc.hip).  DESIGN.md
+section 9.4 has the contract decisions and the measurements.
+"""
+from __future__ import annotations
+
+import argparse
+import contextlib
+import csv
+import json
+import os
+import sys
+import time
+import warnings
+
+import numpy as np
+
+from .consumer import read_drug_indication_tsv
+from .msi import COMPONENTS, DRUG, INDICATION, MsiGraph
+from .predict import PredictError, _get, diffusion_profiles, display, embedding_scores, load_config
+
+METHODS = ("diffusion", "node2vec", "gcn")
+PER_INDICATION_HEADER = ["indication", "name", "positives", "negatives", "auc"]
+MAX_COLS = 16384          # drugs per row: csrc/auc.hip sorts a row's keys in one workgroup's LDS
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description="Drug Repurposing: median / mean ROC-AUC over indications (evaluate_auc.py)")
+    p.add_argument("-c", "--config", default="config.json", type=str, help="config file path (default: config.json)")
+    p.add_argument("-s", "--save-dir", default=None, type=str, help="accepted and ignored")
+    p.add_argument("-r", "--resume", default=None, type=str, help="accepted and ignored")
+    p.add_argument("-d", "--device", default=None, type=str, help="accepted and ignored")
+    p.add_argument("--seed", default=0, type=int, help="seed of the node2vec walks / skip-gram when the eval embedding file is generated")
+    p.add_argument("--per-indication", default=None, type=str,
+                   help="also write a TSV with one row per evaluated indication: id, name, positives, negatives, AUC")
+    return p.parse_args(argv)
+
+
+class Settings:
+    """the config keys evaluate_auc.main reads, resolved and checked before anything touches the GPU.  The attribute names are those
+    predict.node2vec_file / embedding_scores / diffusion_profiles read."""
+
+    def __init__(self, cfg):
+        self.method = _get(cfg, "method")
+        if self.method not in METHODS:
+            raise PredictError(f"config: method {self.method!r} is unknown; choose one of {', '.join(METHODS)}")
+        if self.method == "gcn" and _get(cfg, "gcn", "embs") != "node2vec":
+            raise PredictError(f"config: gcn.embs = {_get(cfg, 'gcn', 'embs')!r} is not supported; only 'node2vec' (the reference's one branch)")
+        self.graph_out = _get(cfg, "eval", "graph")
+        self.ppi = _get(cfg, "networks", "protein_to_protein")
+        self.data_dir = os.path.dirname(self.ppi)
+        self.labels = _get(cfg, "networks", "drug_to_indication")
+        if not os.path.exists(self.labels):
+            raise PredictError(f"networks.drug_to_indication {self.labels!r} does not exist")
+        self.diffusion_dir = _get(cfg, "diffusion", "eval_diffusion_embs_dir") if self.method == "diffusion" else None
+        self.n2v_file = self.walk_length = self.number_walk = self.gcn_file = None
+        if self.method != "diffusion":
+            prefix = _get(cfg, "node2vec", "eval_emb_file_prefix")
+            self.walk_length = int(_get(cfg, "node2vec", "walk_length"))
+            self.number_walk = int(_get(cfg, "node2vec", "number_walk"))
+            self.n2v_file = f"{prefix}_num_{self.number_walk}_len_{self.walk_length}.embs.txt"   # evaluate_auc.py:29-32
+        if self.method == "gcn":
+            self.gcn_file = _get(cfg, "gcn", "emb_file")
+            if not os.path.exists(self.gcn_file):
+                raise PredictError(f"gcn.emb_file {self.gcn_file!r} does not exist; make it with `python train.py --emb-file {self.n2v_file} "
+                                   f"--adj-file {self.graph_out}` (it writes graph_embs.txt) and move that file to {self.gcn_file!r}")
+        for name, path in self.tables().items():
+            if not os.path.exists(path):
+                raise PredictError(f"MSI table {name}: {path!r} does not exist")
+
+    def tables(self):
+        """MSI() with its default tables, data/<table>.tsv, the directory taken from networks.protein_to_protein (the plain
+        indication_to_protein.tsv, not the covid table)"""
+        return {name: os.path.join(self.data_dir, name + ".tsv") for name, _, _ in COMPONENTS}
+
+
+def format_line(aucs):
+    """evaluate_auc.py:170's f-string on fp64 values"""
+    a = np.asarray(aucs, dtype=np.float64)
+    return f"median auc: {np.median(a)}, mean auc: {a.mean()}"
+
+
+def device_aucs(scores, pos_ptr, pos_col, timings=None):
+    """one device launch: host scores fp64 [R, C] and the positives as a CSR -> host (auc [R], n_pos [R], n_neg [R]); NaN AUC where a
+    row has one class.  No CPU fallback.  timings: upload_s / kernel_s (host clock around synchronised work)."""
+    import torch
+
+    from . import _lib
+    s = np.ascontiguousarray(scores, dtype=np.float64)
+    ptr = np.ascontiguousarray(pos_ptr, dtype=np.int32)
+    col = np.ascontiguousarray(pos_col, dtype=np.int32)
+    if s.ndim != 2 or s.shape[1] < 1 or ptr.shape != (s.shape[0] + 1,) or ptr[0] != 0 or np.any(np.diff(ptr) < 0) or ptr[-1] != len(col):
+        raise PredictError(f"device_aucs: scores {s.shape} and the positives' row pointer ({len(ptr)} entries over {len(col)}) disagree")
+    if s.shape[1] > MAX_COLS:
+        raise PredictError(f"{s.shape[1]} drugs per indication is above the limit of {MAX_COLS} (one workgroup sorts a row in LDS)")
+    R = s.shape[0]
+    if R == 0:
+        return np.zeros(0), np.zeros(0, np.int32), np.zeros(0, np.int32)
+    t = {} if timings is None else timings
+    lib = _lib.load()
+    dev = torch.device("cuda")
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    d_s = torch.from_numpy(s).to(dev)
+    d_ptr = torch.from_numpy(ptr).to(dev)
+    d_col = torch.from_numpy(col if len(col) else np.zeros(1, np.int32)).to(dev)
+    auc = torch.empty(R, dtype=torch.float64, device=dev)
+    n_pos = torch.empty(R, dtype=torch.int32, device=dev)
+    n_neg = torch.empty(R, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    _lib.check(lib.gss_auc_rows(R, s.shape[1], _lib.ptr(d_s), s.shape[1], _lib.ptr(d_ptr), _lib.ptr(d_col), _lib.ptr(auc),
+                                _lib.ptr(n_pos), _lib.ptr(n_neg), _lib.current_stream()), "gss_auc_rows")   # synchronises the stream
+    t["upload_s"], t["kernel_s"] = t1 - t0, time.perf_counter() - t1
+    return auc.cpu().numpy(), n_pos.cpu().numpy(), n_neg.cpu().numpy()
+
+
+# ---- scores and labels ---------------------------------------------------------------------------------------------------------------
+
+def score_rows(s, g, seed):
+    """-> (indications, drugs, scores fp64 [len(indications), len(drugs)]), both lists in the reference's node order"""
+    if s.method == "diffusion":
+        nodelist, profiles = diffusion_profiles(s, g)
+        drugs = [n for n in nodelist if g.type.get(n) == DRUG]
+        inds = [n for n in nodelist if g.type.get(n) == INDICATION]
+        pos = {n: i for i, n in enumerate(nodelist)}
+        didx = np.asarray([pos[d] for d in drugs], dtype=np.int64)
+        rows = []
+        for i in inds:                      # evaluate_auc.py:156-161: the indication's visit probability at each drug node
+            if i not in profiles:
+                raise PredictError(f"indication {i!r} has no diffusion profile in {s.diffusion_dir!r}")
+            p = np.asarray(profiles[i], dtype=np.float64)
+            if len(p) != len(nodelist):
+                raise PredictError(f"the profile of {i!r} has {len(p)} entries, node2idx.pkl {len(nodelist)}")
+            rows.append(p[didx])
+    else:
+        names, x = embedding_scores(s, g, seed)
+        drugs = [n for n in g.names if g.type[n] == DRUG]
+        inds = [n for n in g.names if g.type[n] == INDICATION]
+        idx = {n: i for i, n in enumerate(names)}
+        missing = [n for n in drugs + inds if n not in idx]
+        if missing:
+            raise PredictError(f"{s.n2v_file}: node {missing[0]!r} has no row ({len(missing)} drug / indication nodes are missing)")
+        xd = x[[idx[d] for d in drugs]]
+        rows = [np.matmul(xd, np.array(x[idx[i]])) for i in inds]   # predict_drug.py:55-58's arithmetic, one indication at a time
+    scores = np.asarray(rows, dtype=np.float64).reshape(len(inds), len(drugs))
+    return inds, drugs, scores
+
+
+def label_rows(inds, drugs, positives):
+    """-> (pos_ptr, pos_col, listed {indication: bool}, unknown pairs): the columns of the drugs listed for each indication; listed drugs
+    that are not drug nodes of the graph are left out and counted"""
+    col_of = {d: k for k, d in enumerate(drugs)}
+    ptr, cols, listed, unknown = [0], [], {}, 0
+    for i in inds:
+        listed[i] = i in positives
+        known = sorted(col_of[d] for d in positives.get(i, ()) if d in col_of)
+        unknown += len(positives.get(i, ())) - len(known)
+        cols += known
+        ptr.append(len(cols))
+    return np.asarray(ptr, np.int32), np.asarray(cols, np.int32), listed, unknown
+
+
+class Result:
+    def __init__(self, inds, auc, n_pos, n_neg, skipped, unknown):
+        self.indications, self.auc, self.n_pos, self.n_neg = inds, auc, n_pos, n_neg
+        self.skipped, self.unknown_pairs = skipped, unknown
+        self.kept = [k for k in range(len(inds)) if n_pos[k] > 0 and n_neg[k] > 0]
+        self.line = format_line(auc[self.kept])
+
+
+def skip_report(res, labels):
+    sk = res.skipped
+    total = sum(len(v) for v in sk.values())
+    lines = []
+    if total:
+        lines.append(f"evaluate_auc: skipped {total} of {len(res.indications)} indications: {len(sk['no_row'])} without a row in {labels}, "
+                     f"{len(sk['no_known_drug'])} whose listed drugs are not drug nodes of the graph, {len(sk['all_positive'])} with every "
+                     "drug listed (one class: ROC-AUC is undefined)")
+    if res.unknown_pairs:
+        lines.append(f"evaluate_auc: {res.unknown_pairs} listed (drug, indication) pairs name a drug that is not a drug node of the graph; "
+                     "they are left out")
+    return lines
+
+
+def write_per_indication(path, g, res):
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f, delimiter="\t", lineterminator="\n")
+        w.writerow(PER_INDICATION_HEADER)
+        for k in res.kept:
+            i = res.indications[k]
+            w.writerow([i, display(g, i), int(res.n_pos[k]), int(res.n_neg[k]), repr(float(res.auc[k]))])
+
+
+def run(s, seed=0, per_indication=None, auc_source=device_aucs, timings=None, err=None):
+    """evaluate_auc.main on Settings s -> Result (per-indication AUCs, counts, skipped indications by reason, the stdout line).
+    auc_source(scores, pos_ptr, pos_col) -> (auc, n_pos, n_neg), NaN where a row has one class."""
+    err = sys.stderr if err is None else err
+    t = {} if timings is None else timings
+    t0 = time.perf_counter()
+    g = MsiGraph().load(s.tables())
+    if not os.path.exists(s.graph_out):      # before the diffusion branch weights g in place (evaluate_auc.py:123-129)
+        g.write_unweighted_edgelist(s.graph_out)
+    else:
+        warnings.warn(f"graph struc file {s.graph_out} already exists. change this line if want to overwrite.")
+    t1 = time.perf_counter()
+    t["graph_s"] = t1 - t0
+    with contextlib.redirect_stdout(err):    # progress text of the profile / embedding stage; stdout carries the result line alone
+        inds, drugs, scores = score_rows(s, g, seed)
+    if not drugs:
+        raise PredictError("the graph has no drug node; there is nothing to rank")
+    positives = read_drug_indication_tsv(s.labels)
+    pos_ptr, pos_col, listed, unknown = label_rows(inds, drugs, positives)
+    t2 = time.perf_counter()
+    t["scores_s"] = t2 - t1
+    auc, n_pos, n_neg = auc_source(scores, pos_ptr, pos_col)
+    t["auc_s"] = time.perf_counter() - t2
+    skipped = {"no_row": [], "no_known_drug": [], "all_positive": []}
+    for k, i in enumerate(inds):
+        if n_pos[k] == 0:
+            skipped["no_known_drug" if listed[i] else "no_row"].append(i)
+        elif n_neg[k] == 0:
+            skipped["all_positive"].append(i)
+    res = Result(inds, np.asarray(auc, np.float64), np.asarray(n_pos), np.asarray(n_neg), skipped, unknown)
+    for line in skip_report(res, s.labels):
+        print(line, file=err)
+    if not res.kept:
+        raise PredictError(f"no indication has both a listed drug and an unlisted one in {s.labels!r}; there is no AUC to report")
+    if per_indication:
+        write_per_indication(per_indication, g, res)
+    t["total_s"] = time.perf_counter() - t0
+    return res
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    try:
+        s = Settings(load_config(args.config))
+    except (PredictError, OSError, json.JSONDecodeError) as e:
+        print(f"evaluate_auc: {e}", file=sys.stderr)
+        sys.exit(2)
+    try:
+        res = run(s, args.seed, args.per_indication)
+    except (PredictError, OSError) as e:
+        print(f"evaluate_auc: {e}", file=sys.stderr)
+        sys.exit(2)
+    print(res.line)

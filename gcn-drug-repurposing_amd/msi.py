@@ -161,6 +161,14 @@ class MsiGraph:
                 for v, w in succs.items():
                     f.write(f"{u} {v} {1.0 if w is None else w}\n")
 
+    def write_unweighted_edgelist(self, path):
+        """nx.write_weighted_edgelist text as networkx writes it for edges without a weight attribute (evaluate_auc.py:123-125 on the
+        unweighted MSI): 'u v' per directed edge, 'u v w' where a weight is set, in node / adjacency order"""
+        with open(path, "w") as f:
+            for u, succs in self.adj.items():
+                for v, w in succs.items():
+                    f.write(f"{u} {v}\n" if w is None else f"{u} {v} {w}\n")
+
     def to_csr(self):
         """-> (adj CSR fp64 [N, N] with A[u, v] = w(u -> v), names, types)"""
         names = self.names

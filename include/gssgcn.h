@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define GSS_ABI_VERSION 10  /* 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
+#define GSS_ABI_VERSION 11  /* 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
 
 #define GSS_OK 0
 #define GSS_EINVAL (-22)   /* bad argument (shape, null pointer, unsupported d) */
@@ -396,6 +396,18 @@ int gss_paths_create(gss_paths **out, int32_t n, int64_t nnz, const int32_t *row
                      int64_t max_bytes, void *stream);
 int gss_paths_run(gss_paths *p, int32_t q, const int32_t *targets, uint8_t *dist, int32_t *next, int32_t *levels, void *stream);
 void gss_paths_destroy(gss_paths *p);
+
+/* ---- ROC-AUC per query row (evaluate_auc.py:156-170: roc_auc_score of every drug's score against the drugs listed for an indication)
+ * gss_auc_rows: device fp64 scores [R][ld] (row r: the C candidates' scores for query r), the positives of row r in device CSR form,
+ * pos_col[pos_ptr[r] .. pos_ptr[r + 1]) (column indices, any order) -> device auc [R] fp64, n_pos [R], n_neg [R] int32.
+ * auc = sklearn.metrics.roc_auc_score with average ranks for ties: sum over tie groups of pos_g (neg_below + neg_g / 2) / (P N), the
+ * counts kept in integers (so it depends only on the multiset of (score, label) pairs, not on their order), one rounding at the end;
+ * -0.0 and +0.0 are one tie group.  A row with P = 0 or N = 0 gets auc = NaN and its counts.  One workgroup per row sorts the row's
+ * keys in LDS, so 1 <= C <= 16384.  Bitwise deterministic (no atomics on results).  Synchronises the stream: refuses (GSS_EINVAL, by
+ * row and column in gss_last_error) C above the limit, ld < C, a NaN or infinite score, a pos_col outside [0, C) or repeated within
+ * its row, and a pos_ptr that is not a row pointer (0 first, non-decreasing, at most C per row); the outputs are then unspecified. */
+int gss_auc_rows(int32_t R, int32_t C, const double *scores, int64_t ld, const int32_t *pos_ptr, const int32_t *pos_col, double *auc,
+                 int32_t *n_pos, int32_t *n_neg, void *stream);
 
 /* ---- a13  np.savetxt('graph_embs.txt', hidden_emb), train.py:193 (host-side; h_emb is a HOST pointer) ---------------------
  * Every value of the float32 matrix as Python prints it with '%.18e' after widening to double (exact decimal expansion, round
