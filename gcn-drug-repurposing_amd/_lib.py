@@ -9,7 +9,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgssgcn.so")
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 _lib = None
 
@@ -168,6 +168,9 @@ SIGNATURES = {
     "gss_paths_create": (C.c_int, [C.POINTER(_P), _I32, _I64, _P, _P, _I32, _I64, _P]),
     "gss_paths_run": (C.c_int, [_P, _I32, _P, _P, _P, C.POINTER(_I32), _P]),
     "gss_paths_destroy": (None, [_P]),
+    "gss_paths_count": (C.c_int, [_P, _I32, _P, _P, _I32, _P, _P, _P, _P, _P]),
+    "gss_paths_between": (C.c_int, [_I32, _I32, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gss_paths_between_fill": (C.c_int, [_I32, _I32, _P, _P, _P, _I32, _P, _P, _P, _I32, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P]),
     "gss_auc_rows": (C.c_int, [_I32, _I32, _P, _I64, _P, _P, _P, _P, _P, _P]),
 }
 

@@ -225,4 +225,14 @@ size_t loss_workspace_bytes_max(int32_t b_max, int32_t d, int parts = 1);   // e
                                                                               // parts > 1: also for the row-slab sweep over that many ranks
 int loss_fwd_bwd(int32_t n, int32_t d, const float *e, const int32_t *idx, int32_t b, float beta, float alpha,
                  float *loss_out, float *de_b, void *ws, void *stream);
+// paths.hip: the parts of a gss_paths handle that a count pass (trace.hip) reads -- the device CSR, the budget, the device copy of the
+// pass's targets and a 64-bit status word with its pinned host copy
+struct PathsView {
+  int32_t n;
+  int64_t nnz, max_bytes;
+  const int32_t *rowptr, *col;
+  int32_t *targets;
+  unsigned long long *status, *h_status;
+};
+int paths_view(const gss_paths *p, PathsView *out);
 }  // namespace gss

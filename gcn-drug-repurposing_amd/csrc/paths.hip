@@ -13,6 +13,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "ops.h"
 
 struct gss_paths {
   int32_t n;
@@ -21,8 +22,9 @@ struct gss_paths {
   const int32_t *rowptr, *col;   // device CSR (owned when uploaded)
   int32_t *own_rowptr, *own_col;
   uint64_t *seen, *front[2];     // [n] each: 24 n bytes of state
-  int32_t *flag;                 // device word: 1 changed, 2 a node 255+ hops away, 4 a bad column
-  int32_t *h_flag;               // pinned host copy
+  int32_t *flag;                 // device word: 1 changed, 2 a node 255+ hops away, 4 a bad column; the 64-bit word behind it (flag + 2) is
+                                 // the status of a count pass (trace.hip)
+  int32_t *h_flag;               // pinned host copy (4 words as well)
   int32_t *targets;              // [kMaxTargets] device
 };
 
@@ -178,6 +180,20 @@ int read_flag(gss_paths *p, hipStream_t st, int32_t *out) {
 }
 
 }  // namespace
+
+// what a count pass (trace.hip) needs of a handle
+int paths_view(const gss_paths *p, PathsView *out) {
+  out->n = p->n;
+  out->nnz = p->nnz;
+  out->max_bytes = p->max_bytes;
+  out->rowptr = p->rowptr;
+  out->col = p->col;
+  out->targets = p->targets;
+  out->status = reinterpret_cast<unsigned long long *>(p->flag + 2);
+  out->h_status = reinterpret_cast<unsigned long long *>(p->h_flag + 2);
+  return GSS_OK;
+}
+
 }  // namespace gss
 
 using namespace gss;
@@ -201,9 +217,9 @@ int gss_paths_create(gss_paths **out, int32_t n, int64_t nnz, const int32_t *row
   p->nnz = nnz;
   p->max_bytes = max_bytes;
   bool ok = hipMalloc((void **)&p->seen, (size_t)n * 8) == hipSuccess && hipMalloc((void **)&p->front[0], (size_t)n * 8) == hipSuccess &&
-            hipMalloc((void **)&p->front[1], (size_t)n * 8) == hipSuccess && hipMalloc((void **)&p->flag, sizeof(int32_t)) == hipSuccess &&
+            hipMalloc((void **)&p->front[1], (size_t)n * 8) == hipSuccess && hipMalloc((void **)&p->flag, 4 * sizeof(int32_t)) == hipSuccess &&
             hipMalloc((void **)&p->targets, kMaxTargets * sizeof(int32_t)) == hipSuccess &&
-            hipHostMalloc((void **)&p->h_flag, sizeof(int32_t)) == hipSuccess;
+            hipHostMalloc((void **)&p->h_flag, 4 * sizeof(int32_t)) == hipSuccess;
   if (ok && !on_device) {
     ok = hipMalloc((void **)&p->own_rowptr, (size_t)(n + 1) * 4) == hipSuccess &&
          hipMalloc((void **)&p->own_col, (size_t)std::max<int64_t>(nnz, 1) * 4) == hipSuccess;

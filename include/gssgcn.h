@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define GSS_ABI_VERSION 11  /* 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
+#define GSS_ABI_VERSION 12  /* 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
 
 #define GSS_OK 0
 #define GSS_EINVAL (-22)   /* bad argument (shape, null pointer, unsupported d) */
@@ -396,6 +396,46 @@ int gss_paths_create(gss_paths **out, int32_t n, int64_t nnz, const int32_t *row
                      int64_t max_bytes, void *stream);
 int gss_paths_run(gss_paths *p, int32_t q, const int32_t *targets, uint8_t *dist, int32_t *next, int32_t *levels, void *stream);
 void gss_paths_destroy(gss_paths *p);
+
+/* ---- what lies between a source and a target besides one shortest path (interpret.py; csrc/trace.hip) -----------------------------------
+ * gss_paths_count: for the pass of gss_paths_run on the same handle with the same targets (HOST int32, 1 <= q <= 64), its device
+ * dist [q][n] and its levels, -> device
+ *   sigma [q][n] fp64: the number of distinct shortest paths v -> t_i: 1 at t_i, the sum of sigma over the successors u of v with
+ *     dist[u] = dist[v] - 1, 0 where t_i is unreachable.  Exact integers: a pass in which a count would exceed 2^53 is refused, naming
+ *     the target and the node, so the order of the sum cannot matter;
+ *   and with device weights w [q][n] fp64 (NULL: best and best_next are NULL too), finite,
+ *   best_next [q][n] int32: among the successors one hop closer the one with the largest best, the smallest index on equal values; -1
+ *     at t_i and where t_i is unreachable;
+ *   best [q][n] fp64: w[v] + best[best_next[v]], 0 at t_i and where unreachable: the largest sum of node weights (t_i excluded) over
+ *     the shortest paths v -> t_i, summed from the target outward, one addition per node.
+ * One launch per level 1 .. levels, enqueued back to back with no read-back between them; one status word is read after the last (the
+ * call synchronises the stream once).  Bitwise deterministic.  Refuses (GSS_EINVAL, by name): a null argument, q outside 1..64, levels
+ * outside 0..254 or smaller than a finite distance in dist (node and target named), a dist that is not 0 exactly at the targets, a
+ * weight that is not finite (target and node named), a row that holds a column twice (row named), a count above 2^53 (target and node
+ * named), and a pass above the handle's budget: (1 + 4 + 8) q n bytes (dist, next, sigma), with weights (1 + 4 + 8 + 8 + 4 + 8) q n,
+ * beside the 24 n of state.  "From a source" is the same call on a handle made of the transposed CSR.
+ * gss_paths_between: one pass of sources (HOST indices s[0..ns), ns <= 64; device dist_s / sigma_s [ns][n] = gss_paths_run /
+ * gss_paths_count toward the sources on the TRANSPOSED graph, i.e. hops and path counts s -> v) and one pass of targets (HOST
+ * t[0..nt), nt <= 64; device dist_t / sigma_t [nt][n]) -> device, per pair (i, j) at [i * nt + j],
+ *   pair_len int32: D = dist_t[j][s_i], -1 when s_i cannot reach t_j;  pair_paths fp64: sigma_t[j][s_i] (0 when unreachable);
+ *   pair_nodes int32: the number of nodes v with dist_s[i][v] + dist_t[j][v] = D (both finite; the two end points are counted);
+ *   and (med_sum, med_count both or neither) ADDS to med_sum [nt][n] fp64, for every v not in {s_i, t_j} on a shortest path of a
+ *   reachable pair, share = (sigma_s[i][v] * sigma_t[j][v]) / sigma_t[j][s_i] (one multiply, one divide), over i in list order, and to
+ *   med_count [nt][n] int32 the number of sources that contributed.  The caller zeroes both before the first pass of sources; a later
+ *   pass continues them, so the sum has the order of the source list however it is cut into passes.  Does not synchronise.
+ * gss_paths_between_fill: for n_pairs chosen pairs (device pairs [n_pairs][2] int32: source and target position in the pass) and device
+ * offset [n_pairs + 1] int64 (the exclusive scan of their pair_nodes) writes, at offset[p] .. offset[p + 1], the nodes on the shortest
+ * paths of pair p in ascending node index: node int32, hops_from / hops_to uint8, paths_from fp64 (sigma_s), through fp64 (sigma_s * sigma_t), share fp64
+ * (through / sigma_t[j][s_i]).  Nothing is written at or beyond `capacity` entries or for a pair outside the pass.  Does not synchronise. */
+int gss_paths_count(gss_paths *p, int32_t q, const int32_t *targets, const uint8_t *dist, int32_t levels, const double *w, double *sigma,
+                    double *best, int32_t *best_next, void *stream);
+int gss_paths_between(int32_t n, int32_t ns, const int32_t *sources, const uint8_t *dist_s, const double *sigma_s, int32_t nt,
+                      const int32_t *targets, const uint8_t *dist_t, const double *sigma_t, int32_t *pair_len, double *pair_paths,
+                      int32_t *pair_nodes, double *med_sum, int32_t *med_count, void *stream);
+int gss_paths_between_fill(int32_t n, int32_t ns, const int32_t *sources, const uint8_t *dist_s, const double *sigma_s, int32_t nt,
+                           const int32_t *targets, const uint8_t *dist_t, const double *sigma_t, int32_t n_pairs, const int32_t *pairs,
+                           const int64_t *offset, int64_t capacity, int32_t *node, uint8_t *hops_from, uint8_t *hops_to, double *paths_from,
+                           double *through, double *share, void *stream);
 
 /* ---- ROC-AUC per query row (evaluate_auc.py:156-170: roc_auc_score of every drug's score against the drugs listed for an indication)
  * gss_auc_rows: device fp64 scores [R][ld] (row r: the C candidates' scores for query r), the positives of row r in device CSR form,
