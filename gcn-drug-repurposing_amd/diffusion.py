@@ -8,7 +8,11 @@ iteration is one batched SpMM through libgssgcn.so (gss_ppr_*, csrc/ppr.hip).  N
 
 Host side (this file): what the reference also does on the host with scipy -- the weighted adjacency, its row sums
 (:49-56) and, per start node, which rows of x need special treatment (:30-47) -- as index lists, not as a matrix copy
-per start node."""
+per start node.
+
+compare_profiles: the comparison of two profiles the method rests on (multiscale/README.md, overview (c)), which the reference never makes: a
+pairwise distance between columns of the profile matrix (gss_profile_dist, csrc/profile_dist.hip), on the tensor PprEngine.run returned or on
+profiles loaded from a directory."""
 from __future__ import annotations
 
 import ctypes as C
@@ -159,6 +163,83 @@ class PprEngine:
         if getattr(self, "handle", None) is not None and self.handle.value:
             self.lib.gss_ppr_destroy(self.handle)
             self.handle = C.c_void_p()
+
+
+METRICS = ("cityblock", "euclidean", "canberra", "cosine", "correlation")   # index = GSS_DIST_* of include/gssgcn.h
+
+
+def check_metric(metric):
+    if metric not in METRICS:
+        raise ValueError(f"profile distance {metric!r} is unknown; choose one of {', '.join(METRICS)}")
+    return METRICS.index(metric)
+
+
+def _column_list(what, sel, width, names=None):
+    """-> int32 column indices of a selection: integers (None = every column), or keys of `names` ({key: column})"""
+    if sel is None:
+        return np.arange(width, dtype=np.int32)
+    if names is not None:
+        missing = [k for k in sel if k not in names]
+        if missing:
+            raise ValueError(f"compare_profiles: {what} {missing[0]!r} has no profile")
+        return np.asarray([names[k] for k in sel], dtype=np.int32)
+    idx = np.asarray(sel, dtype=np.int64).reshape(-1)
+    bad = np.flatnonzero((idx < 0) | (idx >= width))
+    if len(bad):
+        raise ValueError(f"compare_profiles: {what} index {int(idx[bad[0]])} is outside [0, {width})")
+    return idx.astype(np.int32)
+
+
+def compare_profiles(profiles, rows, cols, metric, device="cuda"):
+    """distance between diffusion profiles -> device tensor fp64 [len(rows)][len(cols)], scipy.spatial.distance.cdist's value of `metric`
+    (one of METRICS) for every (row profile, column profile) pair.  `profiles` is
+      * the device tensor PprEngine.run returned, x [N][kpad] with profile c in column c: used in place; rows / cols are column indices;
+      * a host array [K][N] (one profile per row): uploaded once, transposed into the kernel's layout; rows / cols index its rows;
+      * the {name: vector} dict DiffusionProfiles.load_diffusion_profiles fills: the named profiles are uploaded once; rows / cols are names.
+    rows / cols may repeat and come in any order; None means every profile (not for a dict).  An unknown metric is refused by name before
+    the GPU is touched.  No CPU fallback."""
+    metric_id = check_metric(metric)
+    import torch
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.GssError("profile distances run on the GPU only (no CPU fallback)")
+    if isinstance(profiles, torch.Tensor):
+        x = profiles
+        if (x.dim() != 2 or x.dtype != torch.float64 or not x.is_cuda or x.shape[1] < 1 or (x.shape[1] > 1 and x.stride(1) != 1)
+                or (x.shape[0] > 1 and x.stride(0) < x.shape[1])):
+            raise ValueError("compare_profiles: a profile tensor must be a device fp64 matrix [N][columns] with unit column stride and "
+                             "a row stride of at least its width")
+        ca, cb = _column_list("row", rows, x.shape[1]), _column_list("column", cols, x.shape[1])
+    elif isinstance(profiles, dict):
+        if rows is None or cols is None:
+            raise ValueError("compare_profiles: rows and cols must name the profiles of a dict")
+        keys = list(dict.fromkeys(list(rows) + list(cols)))
+        pos = {k: i for i, k in enumerate(keys) if k in profiles}
+        ca, cb = _column_list("row", rows, len(keys), pos), _column_list("column", cols, len(keys), pos)
+        host = [np.asarray(profiles[k], dtype=np.float64).reshape(-1) for k in keys]
+        if len({len(v) for v in host}) > 1:
+            raise ValueError("compare_profiles: the profiles differ in length")
+        x = torch.from_numpy(np.stack(host)).to(dev).t().contiguous() if host else None
+    else:
+        host = np.ascontiguousarray(profiles, dtype=np.float64)
+        if host.ndim != 2:
+            raise ValueError(f"compare_profiles: a host profile array must be [K][N], not {host.shape}")
+        ca, cb = _column_list("row", rows, host.shape[0]), _column_list("column", cols, host.shape[0])
+        x = torch.from_numpy(host).to(dev).t().contiguous()
+    out = torch.empty(len(ca), len(cb), dtype=torch.float64, device=dev)
+    if len(ca) == 0 or len(cb) == 0:
+        return out
+    if x.shape[0] < 1:
+        raise ValueError("compare_profiles: the profiles are empty")
+    lists = []
+    for c in (ca, cb):   # "the first n columns" needs no list (and no check of one)
+        lists.append(None if np.array_equal(c, np.arange(len(c))) else torch.from_numpy(c).to(x.device))
+    ld = x.stride(0) if x.shape[0] > 1 else x.shape[1]   # one row: no row stride is ever applied (torch leaves it unspecified)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().gss_profile_dist(x.shape[0], x.data_ptr(), ld, len(ca), _lib.ptr(lists[0]), len(cb), _lib.ptr(lists[1]),
+                                                metric_id, out.data_ptr(), len(cb), _lib.current_stream()),
+                   "gss_profile_dist")
+    return out
 
 
 def diffusion_profiles(m0, starts, proteins_of, alpha, max_iter, tol, device="cuda", max_columns=4096):

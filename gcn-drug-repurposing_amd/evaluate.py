@@ -24,7 +24,7 @@ import numpy as np
 
 from .consumer import read_drug_indication_tsv
 from .msi import COMPONENTS, DRUG, INDICATION, MsiGraph
-from .predict import PredictError, _get, diffusion_profiles, display, embedding_scores, load_config
+from .predict import PredictError, _get, compare_setting, diffusion_profiles, display, embedding_scores, load_config, profile_distances
 
 METHODS = ("diffusion", "node2vec", "gcn")
 PER_INDICATION_HEADER = ["indication", "name", "positives", "negatives", "auc"]
@@ -51,6 +51,7 @@ class Settings:
         self.method = _get(cfg, "method")
         if self.method not in METHODS:
             raise PredictError(f"config: method {self.method!r} is unknown; choose one of {', '.join(METHODS)}")
+        self.compare = compare_setting(cfg, self.method)
         if self.method == "gcn" and _get(cfg, "gcn", "embs") != "node2vec":
             raise PredictError(f"config: gcn.embs = {_get(cfg, 'gcn', 'embs')!r} is not supported; only 'node2vec' (the reference's one branch)")
         self.graph_out = _get(cfg, "eval", "graph")
@@ -89,14 +90,21 @@ def format_line(aucs):
 
 def device_aucs(scores, pos_ptr, pos_col, timings=None):
     """one device launch: host scores fp64 [R, C] and the positives as a CSR -> host (auc [R], n_pos [R], n_neg [R]); NaN AUC where a
-    row has one class.  No CPU fallback.  timings: upload_s / kernel_s (host clock around synchronised work)."""
+    row has one class.  No CPU fallback.  timings: upload_s / kernel_s (host clock around synchronised work).  Scores that are already a
+    device tensor (fp64 [R, C], the negated output of gss_profile_dist) go into the kernel where they are."""
     import torch
 
     from . import _lib
-    s = np.ascontiguousarray(scores, dtype=np.float64)
+    on_device = isinstance(scores, torch.Tensor)
+    if on_device:
+        if scores.dim() != 2 or scores.dtype != torch.float64 or not scores.is_cuda:
+            raise PredictError("device_aucs: device scores must be an fp64 matrix [R, C] on the GPU")
+        s = scores.contiguous()
+    else:
+        s = np.ascontiguousarray(scores, dtype=np.float64)
     ptr = np.ascontiguousarray(pos_ptr, dtype=np.int32)
     col = np.ascontiguousarray(pos_col, dtype=np.int32)
-    if s.ndim != 2 or s.shape[1] < 1 or ptr.shape != (s.shape[0] + 1,) or ptr[0] != 0 or np.any(np.diff(ptr) < 0) or ptr[-1] != len(col):
+    if len(s.shape) != 2 or s.shape[1] < 1 or ptr.shape != (s.shape[0] + 1,) or ptr[0] != 0 or np.any(np.diff(ptr) < 0) or ptr[-1] != len(col):
         raise PredictError(f"device_aucs: scores {s.shape} and the positives' row pointer ({len(ptr)} entries over {len(col)}) disagree")
     if s.shape[1] > MAX_COLS:
         raise PredictError(f"{s.shape[1]} drugs per indication is above the limit of {MAX_COLS} (one workgroup sorts a row in LDS)")
@@ -108,7 +116,7 @@ def device_aucs(scores, pos_ptr, pos_col, timings=None):
     dev = torch.device("cuda")
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    d_s = torch.from_numpy(s).to(dev)
+    d_s = s if on_device else torch.from_numpy(s).to(dev)
     d_ptr = torch.from_numpy(ptr).to(dev)
     d_col = torch.from_numpy(col if len(col) else np.zeros(1, np.int32)).to(dev)
     auc = torch.empty(R, dtype=torch.float64, device=dev)
@@ -125,11 +133,18 @@ def device_aucs(scores, pos_ptr, pos_col, timings=None):
 # ---- scores and labels ---------------------------------------------------------------------------------------------------------------
 
 def score_rows(s, g, seed):
-    """-> (indications, drugs, scores fp64 [len(indications), len(drugs)]), both lists in the reference's node order"""
+    """-> (indications, drugs, scores fp64 [len(indications), len(drugs)]), both lists in the reference's node order.  With
+    diffusion.compare = a metric the scores are minus the distance between the indication's profile and the drug's, a device tensor that
+    never visits the host"""
     if s.method == "diffusion":
         nodelist, profiles = diffusion_profiles(s, g)
         drugs = [n for n in nodelist if g.type.get(n) == DRUG]
         inds = [n for n in nodelist if g.type.get(n) == INDICATION]
+        if s.compare != "visit":
+            for i in inds:
+                if i not in profiles:
+                    raise PredictError(f"indication {i!r} has no diffusion profile in {s.diffusion_dir!r}")
+            return inds, drugs, -profile_distances(profiles, inds, drugs, s.compare)
         pos = {n: i for i, n in enumerate(nodelist)}
         didx = np.asarray([pos[d] for d in drugs], dtype=np.int64)
         rows = []
@@ -169,8 +184,9 @@ def label_rows(inds, drugs, positives):
 
 
 class Result:
-    def __init__(self, inds, auc, n_pos, n_neg, skipped, unknown):
+    def __init__(self, inds, auc, n_pos, n_neg, skipped, unknown, drugs=None, scores=None):
         self.indications, self.auc, self.n_pos, self.n_neg = inds, auc, n_pos, n_neg
+        self.drugs, self.scores = drugs, scores    # what was ranked: scores [indications][drugs] (a device tensor under diffusion.compare = a metric)
         self.skipped, self.unknown_pairs = skipped, unknown
         self.kept = [k for k in range(len(inds)) if n_pos[k] > 0 and n_neg[k] > 0]
         self.line = format_line(auc[self.kept])
@@ -228,7 +244,7 @@ def run(s, seed=0, per_indication=None, auc_source=device_aucs, timings=None, er
             skipped["no_known_drug" if listed[i] else "no_row"].append(i)
         elif n_neg[k] == 0:
             skipped["all_positive"].append(i)
-    res = Result(inds, np.asarray(auc, np.float64), np.asarray(n_pos), np.asarray(n_neg), skipped, unknown)
+    res = Result(inds, np.asarray(auc, np.float64), np.asarray(n_pos), np.asarray(n_neg), skipped, unknown, drugs, scores)
     for line in skip_report(res, s.labels):
         print(line, file=err)
     if not res.kept:

@@ -6,7 +6,8 @@ and what share of the paths passes through each, the one path that the model's o
 mediators of the query.  Counts, best paths and the between pass run on the GPU (trace.py / csrc/trace.hip); no CPU fallback.
 
 The weight of node v for query t is the model's proximity of v to t: x[v] . x[t] in fp64 for node2vec / gcn (rows normalised for gcn,
-as predict.embedding_scores does), the query's diffusion profile at v for diffusion.
+as predict.embedding_scores does), the query's diffusion profile at v for diffusion -- also when the config's diffusion.compare ranks the
+drugs by a distance between profiles, which changes which drugs are traced and their proximity column, nothing else.
 """
 from __future__ import annotations
 
@@ -112,7 +113,7 @@ def run(s, top=None, drugs=None, all_drugs=False, out="trace.tsv", nodes=None, e
     t["graph_s"] = t1 - t0
     if s.method == "diffusion":
         nodelist, profiles = predict.diffusion_profiles(s, g)
-        ranked = {q: predict.rank_diffusion(nodelist, profiles, g, q) for q in s.queries}
+        ranked = predict.rank_profiles(s, nodelist, profiles, g)   # diffusion.compare changes the ranking only: the node weights
         weights = {q: profile_weights(nodelist, profiles, names, q) for q in s.queries}
     else:
         emb_names, x = predict.embedding_scores(s, g, seed)

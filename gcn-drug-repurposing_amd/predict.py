@@ -44,7 +44,9 @@ def parse_args(argv=None):
     p.add_argument("--query", action="append", default=None,
                    help="node to rank for (repeatable; default NodeCovid); with several, outputs are named <stem>.<query>.tsv")
     p.add_argument("--protein-table", default=None, type=str,
-                   help="also write run_covid.py's table: every named protein, its proximity to the query, its path and its length")
+                   help="also write run_covid.py's table: every named protein, its proximity to the query, its path and its length "
+                        "(unaffected by the config's diffusion.compare: proteins have no profile of their own, so their proximity stays the "
+                        "query's visit probability)")
     p.add_argument("--seed", default=0, type=int, help="seed of the node2vec walks / skip-gram when the embedding file is generated")
     return p.parse_args(argv)
 
@@ -60,6 +62,21 @@ def _get(cfg, *keys, default=KeyError):
     return d
 
 
+def compare_setting(cfg, method):
+    """diffusion.compare: 'visit' (the default: the query's visit probability at the drug's node, the reference's score) or one of
+    diffusion.METRICS (the score is minus that distance between the query's profile and the drug's own)"""
+    from .diffusion import METRICS
+    compare = _get(cfg, "diffusion", "compare", default="visit")
+    if compare == "visit":
+        return compare
+    if compare not in METRICS:
+        raise PredictError(f"config: diffusion.compare = {compare!r} is unknown; choose 'visit' or one of {', '.join(METRICS)}")
+    if method != "diffusion":
+        raise PredictError(f"config: diffusion.compare = {compare!r} compares diffusion profiles and needs method = 'diffusion', "
+                           f"not {method!r}")
+    return compare
+
+
 class Settings:
     """the config keys predict_drug.main reads, resolved and checked before anything touches the GPU"""
 
@@ -67,6 +84,7 @@ class Settings:
         self.method = _get(cfg, "method")
         if self.method not in METHODS:
             raise PredictError(f"config: method {self.method!r} is unknown; choose one of {', '.join(METHODS)}")
+        self.compare = compare_setting(cfg, self.method)
         if self.method == "gcn" and _get(cfg, "gcn", "embs") != "node2vec":
             raise PredictError(f"config: gcn.embs = {_get(cfg, 'gcn', 'embs')!r} is not supported; only 'node2vec' (the reference's one branch)")
         self.topk = int(_get(cfg, "topk"))
@@ -237,6 +255,49 @@ def rank_diffusion(nodelist, profiles, g, query):
     return [drugs[i] for i in order], prox[order]
 
 
+def profile_distances(profiles, rows, cols, metric):
+    """the distance of every (row node, column node) pair of diffusion profiles, on the device (diffusion.compare_profiles) -> device
+    tensor fp64 [len(rows)][len(cols)].  A node whose distances are NaN (a zero profile, or a constant one under 'correlation') is refused
+    by its id: it cannot be ranked"""
+    import torch
+
+    from .diffusion import compare_profiles
+    for what, nodes in (("query", rows), ("drug", cols)):
+        for n in nodes:
+            if n not in profiles:
+                raise PredictError(f"{what} {n!r} has no diffusion profile in the profile directory; diffusion.compare needs one")
+    try:
+        d = compare_profiles(profiles, rows, cols, metric)
+    except ValueError as e:
+        raise PredictError(str(e)) from None
+    bad = torch.isnan(d)
+    if bool(bad.any()):
+        bad = bad.cpu().numpy()
+        whole = np.flatnonzero(bad.all(axis=1))
+        node = rows[whole[0]] if len(whole) else cols[np.flatnonzero(bad.any(axis=0))[0]]
+        raise PredictError(f"the {metric} distance of node {node!r} is NaN (its diffusion profile is zero or constant); it cannot be ranked")
+    return d
+
+
+def rank_compare(nodelist, profiles, g, queries, metric):
+    """diffusion.compare = a metric: the score of drug d for query q is -dist(profile_q, profile_d); drugs in nodelist order, nearest first,
+    ties by that order -> {query: (drugs ranked, scores ranked)}"""
+    drugs = [n for n in nodelist if g.type.get(n) == DRUG]
+    dist = profile_distances(profiles, list(queries), drugs, metric).cpu().numpy()
+    out = {}
+    for q, row in zip(queries, dist):
+        order = np.argsort(row, kind="stable")
+        out[q] = ([drugs[i] for i in order], -row[order])
+    return out
+
+
+def rank_profiles(s, nodelist, profiles, g):
+    """-> {query: (drugs ranked, scores ranked)} by the config's diffusion.compare"""
+    if s.compare == "visit":
+        return {q: rank_diffusion(nodelist, profiles, g, q) for q in s.queries}
+    return rank_compare(nodelist, profiles, g, s.queries, s.compare)
+
+
 # ---- the tables ----------------------------------------------------------------------------------------------------------------------
 
 def fmt_float(v):
@@ -326,7 +387,7 @@ def run(s, protein_table=None, seed=0, path_source=device_paths, timings=None):
     t["graph_s"] = t1 - t0
     if s.method == "diffusion":
         nodelist, profiles = diffusion_profiles(s, g)
-        ranked = {q: rank_diffusion(nodelist, profiles, g, q) for q in s.queries}
+        ranked = rank_profiles(s, nodelist, profiles, g)
         prot_names = nodelist
         prot_scores = {q: np.asarray(profiles[q])[named_proteins(g, nodelist)] for q in s.queries} if protein_table else None
     else:

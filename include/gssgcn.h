@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define GSS_ABI_VERSION 12  /* 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
+#define GSS_ABI_VERSION 13  /* 13: pairwise distances between diffusion profiles -- gss_profile_dist; 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
 
 #define GSS_OK 0
 #define GSS_EINVAL (-22)   /* bad argument (shape, null pointer, unsupported d) */
@@ -448,6 +448,33 @@ int gss_paths_between_fill(int32_t n, int32_t ns, const int32_t *sources, const 
  * its row, and a pos_ptr that is not a row pointer (0 first, non-decreasing, at most C per row); the outputs are then unspecified. */
 int gss_auc_rows(int32_t R, int32_t C, const double *scores, int64_t ld, const int32_t *pos_ptr, const int32_t *pos_col, double *auc,
                  int32_t *n_pos, int32_t *n_neg, void *stream);
+
+/* ---- pairwise distances between diffusion profiles (multiscale/README.md, overview (c): "by comparing the diffusion profiles of a drug and
+ * a disease ...")
+ * gss_profile_dist: device fp64 x [n][ld], profile c = column c (the layout gss_ppr_run writes, so profiles go from the power iteration into
+ * the comparison without leaving the device); device int32 column lists cols_a [na], cols_b [nb], honoured as given (any order, repeats
+ * allowed; null = columns 0 .. na - 1 / 0 .. nb - 1; an ascending contiguous list costs what null costs)
+ * -> device fp64 out [na][ld_out], out[i][j] = dist(x[:, cols_a[i]], x[:, cols_b[j]]) as scipy.spatial.distance.cdist defines it:
+ *   GSS_DIST_CITYBLOCK   sum |a - b|
+ *   GSS_DIST_EUCLIDEAN   sqrt(sum (a - b)^2), from the differences
+ *   GSS_DIST_CANBERRA    sum |a - b| / (|a| + |b|); a term with a = b = 0 contributes 0
+ *   GSS_DIST_COSINE      1 - a.b / (|a| |b|), the quotient clipped to [-1, 1]; a zero vector gives NaN for its whole row / column
+ *   GSS_DIST_CORRELATION the cosine distance of the two vectors after each has its mean subtracted (two passes: the mean first, then the
+ *                        centred values enter the product and the norm); a constant vector gives NaN
+ * The NaN of a degenerate vector is a value, not an error.  Every output sums the n rows in an order that depends on n alone, without
+ * atomics: bitwise deterministic, out(a, b) and out(b, a) are bit-equal, a pair has the same bits alone and inside a larger call, and
+ * cityblock / euclidean / canberra of a column with itself is exactly 0.0.  Tails in n, na and nb are handled here; na = 0 or nb = 0 is a
+ * no-op.  Refuses (GSS_EINVAL, by name in gss_last_error): a null x or out, n < 1, a negative or too large na / nb, an unknown metric,
+ * ld < 1, ld below na / nb where that list is null, ld_out < nb, and a list entry outside [0, ld) (by list, position and value; nothing
+ * has read x through the list by then).  The scratch (two status words, a mean and a norm per listed column) is allocated and freed
+ * inside the call.  Synchronises the stream, except for cityblock / euclidean / canberra with both lists null, which only enqueue. */
+#define GSS_DIST_CITYBLOCK 0
+#define GSS_DIST_EUCLIDEAN 1
+#define GSS_DIST_CANBERRA 2
+#define GSS_DIST_COSINE 3
+#define GSS_DIST_CORRELATION 4
+int gss_profile_dist(int32_t n, const double *x, int64_t ld, int32_t na, const int32_t *cols_a, int32_t nb, const int32_t *cols_b,
+                     int32_t metric, double *out, int64_t ld_out, void *stream);
 
 /* ---- a13  np.savetxt('graph_embs.txt', hidden_emb), train.py:193 (host-side; h_emb is a HOST pointer) ---------------------
  * Every value of the float32 matrix as Python prints it with '%.18e' after widening to double (exact decimal expansion, round
