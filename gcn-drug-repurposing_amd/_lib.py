@@ -9,7 +9,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgssgcn.so")
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 _lib = None
 
@@ -173,6 +173,7 @@ SIGNATURES = {
     "gss_paths_between_fill": (C.c_int, [_I32, _I32, _P, _P, _P, _I32, _P, _P, _P, _I32, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P]),
     "gss_auc_rows": (C.c_int, [_I32, _I32, _P, _I64, _P, _P, _P, _P, _P, _P]),
     "gss_profile_dist": (C.c_int, [_I32, _P, _I64, _I32, _P, _I32, _P, _I32, _P, _I64, _P]),
+    "gss_embedding_scores": (C.c_int, [_I32, _I32, _P, _I64, _I32, _P, _I32, _P, _I32, _P, _I64, _P]),
 }
 
 

@@ -5,7 +5,7 @@ networks.drug_to_indication.
 The reference's embedding branches end in a NameError (dp_saved is only set for diffusion); the evident intent, embedding inner products
 as scores (consumer.py), is what this does.  It crashes on an indication without a row in the label table, on a listed drug that is not in
 the graph and on a single-class label vector; here such indications are skipped and counted on stderr, listed drugs that are not drug
-nodes are left out (consumer.indication_aucs' rules).  Scores stay host fp64 (np.matmul per indication, predict.py's arithmetic; a
+nodes are left out (consumer.indication_aucs' rules).  Scores of the CLI stay host fp64 (np.matmul per indication, predict.py's arithmetic; a
 gather from the profiles for diffusion); the ranking statistic of every indication runs in one device launch (csrc/auc.hip).  DESIGN.md
 section 9.4 has the contract decisions and the measurements.
 """
@@ -253,6 +253,113 @@ def run(s, seed=0, per_indication=None, auc_source=device_aucs, timings=None, er
         write_per_indication(per_indication, g, res)
     t["total_s"] = time.perf_counter() - t0
     return res
+
+
+# ---- scoring embeddings where they lie: the trainer's model-selection signal ------------------------------------------------------------
+
+class DeviceEvaluator:
+    """The gcn / node2vec branch of run() for embeddings that are a device tensor: built once from the MSI tables (the directory of
+    networks.protein_to_protein, as Settings.tables), networks.drug_to_indication and the node names of an embedding file (row k of the
+    tensor is names[k]); score(emb) then runs gss_embedding_scores and gss_auc_rows on the device and brings back the AUCs and the counts
+    alone.  The lists are run()'s: drugs and indications in g.names order, the positives of label_rows.  DESIGN.md section 9.7.
+
+    Everything that can be wrong with the inputs is found on the host, before upload() touches the GPU."""
+
+    def __init__(self, ppi, labels, names, normalize=True, source="the embedding file", device=None, upload=True):
+        self.labels, self.normalize, self.n = labels, bool(normalize), len(names)
+        if not os.path.exists(labels):
+            raise PredictError(f"networks.drug_to_indication {labels!r} does not exist")
+        tables = {name: os.path.join(os.path.dirname(ppi), name + ".tsv") for name, _, _ in COMPONENTS}
+        for name, path in tables.items():
+            if not os.path.exists(path):
+                raise PredictError(f"MSI table {name}: {path!r} does not exist")
+        g = MsiGraph().load(tables)
+        self.drugs = [n for n in g.names if g.type[n] == DRUG]
+        self.indications = [n for n in g.names if g.type[n] == INDICATION]
+        idx = {n: i for i, n in enumerate(names)}
+        missing = [n for n in self.drugs + self.indications if n not in idx]
+        if missing:
+            raise PredictError(f"{source}: node {missing[0]!r} has no row ({len(missing)} drug / indication nodes are missing)")
+        if not self.drugs:
+            raise PredictError("the graph has no drug node; there is nothing to rank")
+        if len(self.drugs) > MAX_COLS:
+            raise PredictError(f"{len(self.drugs)} drugs per indication is above the limit of {MAX_COLS} (one workgroup sorts a row in LDS)")
+        self.rows = np.asarray([idx[i] for i in self.indications], np.int32)
+        self.cols = np.asarray([idx[d] for d in self.drugs], np.int32)
+        self.pos_ptr, self.pos_col, self.listed, self.unknown_pairs = label_rows(self.indications, self.drugs, read_drug_indication_tsv(labels))
+        n_pos = np.diff(self.pos_ptr)
+        if not np.any((n_pos > 0) & (n_pos < len(self.drugs))):
+            raise PredictError(f"no indication has both a listed drug and an unlisted one in {labels!r}; there is no AUC to report")
+        self.device = None
+        self.reported = False     # the trainer prints the skip report of the eval graph once
+        if upload:
+            self.upload(device)
+
+    def upload(self, device=None):
+        """the index lists, the positives and the output buffers onto the device (the current one by default)"""
+        import torch
+        dev = torch.device("cuda") if device is None else torch.device(device)
+        R, C = len(self.rows), len(self.cols)
+        self.d_rows, self.d_cols = torch.from_numpy(self.rows).to(dev), torch.from_numpy(self.cols).to(dev)
+        self.d_ptr = torch.from_numpy(self.pos_ptr).to(dev)
+        self.d_col = torch.from_numpy(self.pos_col if len(self.pos_col) else np.zeros(1, np.int32)).to(dev)
+        self.d_scores = torch.empty(R, C, dtype=torch.float64, device=dev)
+        self.d_auc = torch.empty(R, dtype=torch.float64, device=dev)
+        self.d_pos = torch.empty(R, dtype=torch.int32, device=dev)
+        self.d_neg = torch.empty(R, dtype=torch.int32, device=dev)
+        self.device = self.d_rows.device      # with its index, as a tensor's device has it
+
+    def check_tensor(self, emb, d=None):
+        """-> d; refuses by name what score() cannot take.  Host only."""
+        import torch
+        if not isinstance(emb, torch.Tensor):
+            raise PredictError(f"DeviceEvaluator.score: emb is a {type(emb).__name__}, not a torch tensor")
+        if emb.dtype != torch.float32:
+            raise PredictError(f"DeviceEvaluator.score: emb has dtype {emb.dtype}, not torch.float32")
+        if emb.dim() != 2 or emb.shape[0] != self.n:
+            raise PredictError(f"DeviceEvaluator.score: emb has shape {tuple(emb.shape)}, but the name list has {self.n} rows")
+        if not emb.is_cuda:
+            raise PredictError(f"DeviceEvaluator.score: emb is on device {emb.device}, not on the GPU")
+        d = emb.shape[1] if d is None else int(d)
+        if d < 1 or d > emb.shape[1]:
+            raise PredictError(f"DeviceEvaluator.score: d = {d} is outside 1..{emb.shape[1]}, the width of emb")
+        if emb.stride(1) != 1 or emb.stride(0) < emb.shape[1]:
+            raise PredictError(f"DeviceEvaluator.score: emb has strides {tuple(emb.stride())}; its rows must be contiguous")
+        return d
+
+    def score(self, emb, d=None, timings=None):
+        """emb: device fp32 [N, >= d], row k = names[k] (d: the leading columns that count; the zero padding behind them changes no bit)
+        -> Result.  Result.scores is the evaluator's own device buffer [indications][drugs], which the next score() overwrites: clone it to
+        keep it.  timings: scores_s / auc_s / host_s (host clock around synchronised calls)."""
+        import torch
+
+        from . import _lib
+        d = self.check_tensor(emb, d)
+        if self.device is None:
+            self.upload(emb.device)
+        if emb.device != self.device:
+            raise PredictError(f"DeviceEvaluator.score: emb is on device {emb.device}, the evaluator's lists on {self.device}")
+        t = {} if timings is None else timings
+        lib = _lib.load()
+        R, C = len(self.rows), len(self.cols)
+        t0 = time.perf_counter()
+        with torch.cuda.device(self.device):     # the stream the launches go to is this device's, whichever is current outside
+            _lib.check(lib.gss_embedding_scores(self.n, d, _lib.ptr(emb), emb.stride(0), R, _lib.ptr(self.d_rows), C, _lib.ptr(self.d_cols),
+                                                int(self.normalize), _lib.ptr(self.d_scores), C, _lib.current_stream()), "gss_embedding_scores")
+            t1 = time.perf_counter()
+            _lib.check(lib.gss_auc_rows(R, C, _lib.ptr(self.d_scores), C, _lib.ptr(self.d_ptr), _lib.ptr(self.d_col), _lib.ptr(self.d_auc),
+                                        _lib.ptr(self.d_pos), _lib.ptr(self.d_neg), _lib.current_stream()), "gss_auc_rows")   # both synchronise
+        t2 = time.perf_counter()
+        auc, n_pos, n_neg = self.d_auc.cpu().numpy(), self.d_pos.cpu().numpy(), self.d_neg.cpu().numpy()
+        skipped = {"no_row": [], "no_known_drug": [], "all_positive": []}
+        for k, i in enumerate(self.indications):
+            if n_pos[k] == 0:
+                skipped["no_known_drug" if self.listed[i] else "no_row"].append(i)
+            elif n_neg[k] == 0:
+                skipped["all_positive"].append(i)
+        res = Result(self.indications, auc, n_pos, n_neg, skipped, self.unknown_pairs, self.drugs, self.d_scores)
+        t["scores_s"], t["auc_s"], t["host_s"] = t1 - t0, t2 - t1, time.perf_counter() - t2
+        return res
 
 
 def main(argv=None):

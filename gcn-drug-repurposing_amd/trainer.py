@@ -6,12 +6,15 @@
 reads F ('.embs.txt'), trains the GSS graph-convolution embedding and writes ./graph_embs.txt.
 Flags the reference parses but never uses (--dataset, --data-path, --report-hard, --regularizer-scale, --kq)
 are accepted and ignored.  New optional flags: --adj-file (weighted edgelist / .sif adjacency instead of the
-kNN graph), --out, --cache-layer1, --batch-file (replay recorded batches), --log-loss, --checkpoint / --resume.
+kNN graph), --out, --cache-layer1, --batch-file (replay recorded batches), --log-loss, --checkpoint / --resume, and --eval-config with
+--eval-every / --eval-log / --keep-best / --patience: the per-indication ROC-AUC of evaluate_auc.py's gcn method on the embeddings of an
+epoch, taken on the device where they lie (evaluate.DeviceEvaluator), as the run's model-selection signal.
 """
 from __future__ import annotations
 
 import argparse
 import os
+import sys
 import time
 
 import numpy as np
@@ -70,7 +73,56 @@ def build_parser():
     p.add_argument('--ngpus', type=int, default=None,
                    help='node-range shards over N GPUs of this node; launch with `python -m torch.distributed.run '
                         '--nproc-per-node N train.py ...` (defaults to WORLD_SIZE)')
+    p.add_argument('--eval-config', default=None,
+                   help="an evaluate_auc.py config: score the embeddings of every eval epoch by per-indication ROC-AUC on the GPU "
+                        "(its networks.protein_to_protein and networks.drug_to_indication; the node names are --emb-file's)")
+    p.add_argument('--eval-every', type=int, default=1, help='epochs E, 2E, ... and the last one are eval epochs (default 1)')
+    p.add_argument('--eval-log', default=None, help='TSV with one row per eval epoch: epoch, median_auc, mean_auc, indications, seconds')
+    p.add_argument('--keep-best', default=None,
+                   help="write the embeddings of every eval epoch whose median AUC is strictly above all earlier ones to this file "
+                        "(graph_embs.txt format; a tie keeps the earlier file)")
+    p.add_argument('--patience', type=int, default=None,
+                   help='stop after this many (>= 1) consecutive eval epochs without a strict improvement of the median AUC')
     return p
+
+
+EVAL_FLAGS = ("eval_config", "eval_every", "eval_log", "keep_best", "patience")
+EVAL_LOG_HEADER = ["epoch", "median_auc", "mean_auc", "indications", "seconds"]
+
+
+def parse_args(argv=None):
+    p = build_parser()
+    args = p.parse_args(argv)
+    if args.eval_every < 1:
+        p.error(f"--eval-every {args.eval_every} must be >= 1")
+    if args.patience is not None and args.patience < 1:
+        p.error(f"--patience {args.patience} must be >= 1")
+    if args.eval_config is None:
+        for flag, given in (("--keep-best", args.keep_best is not None), ("--eval-log", args.eval_log is not None),
+                            ("--patience", args.patience is not None)):
+            if given:
+                p.error(f"{flag} needs --eval-config (there is nothing to evaluate without it)")
+    return args
+
+
+def build_evaluator(args):
+    """--eval-config -> (evaluate.DeviceEvaluator with its lists still on the host, the (names, X) read from --emb-file).  Host only: what is
+    wrong with the config, the tables or the coverage of --emb-file ends the run here, before a GPU is looked for or a graph built."""
+    from .evaluate import DeviceEvaluator
+    from .predict import PredictError, _get, load_config
+    try:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("GSS_FORCE_SHARDED") == "1":
+            raise PredictError("--eval-config is not supported on sharded runs (WORLD_SIZE > 1 or GSS_FORCE_SHARDED=1): the evaluation "
+                               "reads the embeddings of one device")
+        if args.emb_file is None:
+            raise PredictError("--eval-config needs --emb-file (its node names say which row is which drug and indication)")
+        cfg = load_config(args.eval_config)
+        ppi, labels = _get(cfg, "networks", "protein_to_protein"), _get(cfg, "networks", "drug_to_indication")
+        names, X = embio.read_embs(args.emb_file)
+        return DeviceEvaluator(ppi, labels, names, normalize=True, source=args.emb_file, upload=False), (names, X)
+    except (PredictError, OSError, ValueError) as e:
+        print(f"train: --eval-config {args.eval_config}: {e}", file=sys.stderr)
+        sys.exit(2)
 
 
 class _IndexDataset(Dataset):
@@ -94,8 +146,10 @@ def epoch_batches(loader):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     for key in vars(args):
+        if key in EVAL_FLAGS and args.eval_config is None:   # a run without --eval-config prints what it always printed
+            continue
         print(key + ":" + str(vars(args)[key]))
     if args.beta is not None and args.beta_percentile is not None:
         raise Exception('beta and beta_percentile can not be used at the same time!')
@@ -105,6 +159,7 @@ def main(argv=None):
         raise Exception("only --loss gss is supported (tri_loss is dead code in the reference, modules/model.py:223-240)")
     if args.graph_mode != 'descriptor':
         raise Exception("--graph-mode ransac/approx_ransac need the image-retrieval RANSAC graphs the reference never ships")
+    evaluator, emb_read = build_evaluator(args) if args.eval_config else (None, None)
     if not torch.cuda.is_available():
         raise RuntimeError("no GPU visible: this trainer has no CPU path (the reference's CPU path is the oracle, not the product)")
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -141,7 +196,9 @@ def main(argv=None):
         torch.manual_seed(args.seed)
         np.random.seed(args.seed)
 
-    names, X = embio.read_embs(args.emb_file)                 # train.py:79-81
+    names, X = emb_read if emb_read is not None else embio.read_embs(args.emb_file)   # train.py:79-81
+    if evaluator is not None:
+        evaluator.upload(dev)
     n, d = X.shape
     if d != args.hidden_units:
         raise Exception(f"--hidden-units {args.hidden_units} must equal the embedding width {d} (modules/model.py:142)")
@@ -248,6 +305,7 @@ def main(argv=None):
     beta_score = args.beta
     itr = 0
     step_no = 0
+    best_median, best_epoch, stale = -np.inf, 0, 0     # --eval-config: the best median AUC so far, its epoch, eval epochs since
     # what a resumed run must share with the run that wrote the checkpoint to be its continuation
     hyper = {"lr": args.lr, "alpha": args.alpha, "layer_decay": args.layer_decay, "batch_size": float(bsz),
              "seed": float(args.seed or 0), "init_weights": args.init_weights}
@@ -265,6 +323,8 @@ def main(argv=None):
                             f"from the post-step state)")
         engine.load_state_dict(z)
         itr, step_no, beta_score = int(z["epoch"]), int(z["step"]), float(z["beta"])
+        if evaluator is not None and "eval_best_median" in z.files:
+            best_median, best_epoch, stale = float(z["eval_best_median"]), int(z["eval_best_epoch"]), int(z["eval_stale"])
         torch.set_rng_state(torch.from_numpy(z["torch_rng"].copy()))     # the sampler continues its permutation stream
         engine.forward()                                     # the embeddings a finished run writes come from a forward
         print(f"resumed from {args.resume}: {itr} epochs done, beta {beta_score}")
@@ -285,6 +345,8 @@ def main(argv=None):
             else:
                 dist.broadcast(idx32, src=0)     # every rank trains on rank 0's batches even when no --seed is given
         off = 0
+        # an eval epoch ends with a full step, like the run's last epoch: the plan's tensor then holds what --epochs itr + 1 would write
+        is_eval = evaluator is not None and ((itr + 1) % args.eval_every == 0 or itr == args.epochs - 1)
         for batch_id, b in enumerate(sizes):
             if itr == 0 and batch_id == 0:
                 engine.forward()                              # train.py:158-161
@@ -293,7 +355,7 @@ def main(argv=None):
                     print(f"selected beta:{beta_score}")
                 engine.loss_backward(idx32, beta_score, count=b, offset=off)   # train.py:175,183
                 engine.adam()                                 # train.py:184
-            elif itr == args.epochs - 1 and batch_id == len(sizes) - 1:
+            elif (itr == args.epochs - 1 or is_eval) and batch_id == len(sizes) - 1:
                 engine.step(idx32, beta_score, count=b, offset=off)          # the run's last forward: all rows (they are written out)
             else:
                 # every other step reads B rows of its top layer (the loss, train.py:175): gss_plan_step_lazy computes those -- the
@@ -303,16 +365,50 @@ def main(argv=None):
             step_no += 1
         watch()
         itr += 1
+        eval_line, eval_s, stop = None, 0.0, False
+        if is_eval:
+            torch.cuda.synchronize()
+            t_eval = time.time()
+            emb_now = full_embeddings()
+            res = evaluator.score(emb_now, d)
+            score_s = time.time() - t_eval
+            median, mean = float(np.median(res.auc[res.kept])), float(res.auc[res.kept].mean())
+            eval_line = f"eval {itr} {res.line}"
+            if not evaluator.reported:
+                from .evaluate import skip_report
+                for line in skip_report(res, evaluator.labels):
+                    print(line.replace("evaluate_auc:", "train: eval:", 1), file=sys.stderr)
+                evaluator.reported = True
+            if median > best_median:
+                best_median, best_epoch, stale = median, itr, 0
+                if args.keep_best:
+                    embio.write_graph_embs(args.keep_best, emb_now.cpu().numpy()[:, :d])
+            else:
+                stale += 1
+            if args.eval_log:
+                fresh = not os.path.exists(args.eval_log) or os.path.getsize(args.eval_log) == 0
+                with open(args.eval_log, "a") as f:
+                    if fresh:
+                        f.write("\t".join(EVAL_LOG_HEADER) + "\n")
+                    f.write("\t".join([str(itr), repr(median), repr(mean), str(len(res.kept)), repr(score_s)]) + "\n")
+            stop = args.patience is not None and stale >= args.patience and itr < args.epochs
+            eval_s = time.time() - t_eval              # kept out of the epoch time of the `iter` line
         if args.checkpoint and rank == 0:          # weights and optimizer state are replicated: rank 0's copy is the job's
             sd = engine.state_dict()
             tmp = args.checkpoint + ".tmp.npz"
             np.savez(tmp, epoch=itr, beta=float(beta_score), n=n, d=d_pad, num_layers=args.num_layers,
-                     torch_rng=torch.get_rng_state().numpy(), **{"hp_" + k: v for k, v in hyper.items()}, **sd)
+                     torch_rng=torch.get_rng_state().numpy(), **{"hp_" + k: v for k, v in hyper.items()}, **sd,
+                     **({} if evaluator is None else {"eval_best_median": best_median, "eval_best_epoch": best_epoch, "eval_stale": stale}))
             os.replace(tmp, args.checkpoint)
         if args.log_loss:
-            print(f"iter {itr} loss {float(engine.loss.item()):.8f} time {time.time() - start_time:.4f}s")
+            print(f"iter {itr} loss {float(engine.loss.item()):.8f} time {time.time() - start_time - eval_s:.4f}s")
         else:
             print(f"iter {itr}")
+        if eval_line is not None:
+            print(eval_line)
+        if stop:
+            print(f"early stop at iter {itr}")
+            break
     torch.cuda.synchronize()
     # embeddings of the last forward, i.e. before the last optimizer step (train.py:158,193)
     final = full_embeddings().cpu().numpy()[:, :d]

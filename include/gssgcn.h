@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define GSS_ABI_VERSION 13  /* 13: pairwise distances between diffusion profiles -- gss_profile_dist; 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
+#define GSS_ABI_VERSION 14  /* 14: indication x drug scores from the embedding tensor -- gss_embedding_scores; 13: pairwise distances between diffusion profiles -- gss_profile_dist; 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
 
 #define GSS_OK 0
 #define GSS_EINVAL (-22)   /* bad argument (shape, null pointer, unsupported d) */
@@ -475,6 +475,26 @@ int gss_auc_rows(int32_t R, int32_t C, const double *scores, int64_t ld, const i
 #define GSS_DIST_CORRELATION 4
 int gss_profile_dist(int32_t n, const double *x, int64_t ld, int32_t na, const int32_t *cols_a, int32_t nb, const int32_t *cols_b,
                      int32_t metric, double *out, int64_t ld_out, void *stream);
+
+/* ---- inner-product scores between listed embedding rows (predict_drug.py:52-66: sklearn.preprocessing.normalize, then np.matmul)
+ * gss_embedding_scores: device fp32 emb [n][ld], ld >= d (a plan's embedding tensor with its zero padding); device int32 index lists rows
+ * [nr] and cols [nc], honoured as given (any order, repeats allowed) -> device fp64 out [nr][ld_out], out[i][j] = the inner product of
+ * row rows[i] and row cols[j] of emb over the first d values.
+ *   normalize = 1: every value is widened to fp64 and divided by its row's fp64 L2 norm (a zero norm divides by 1), and the product is
+ *   taken after that -- the order of sklearn's normalize followed by np.matmul;  normalize = 0: the widened raw values (node2vec).
+ * The order of every sum depends on d alone:
+ *   norm   the 64 partial sums p[l] = sum of x[k]^2 over k = l, l + 64, l + 128 ... (ascending, from +0.0), combined by the butterfly
+ *          p[l] = p[l] + p[l ^ m] for m = 32, 16, 8, 4, 2, 1; norm = sqrt(p[0]), correctly rounded;
+ *   value  (double)x / norm, one correctly rounded division;
+ *   dot    acc = +0.0; acc = acc + a[k] * b[k] for k = 0 .. d - 1, the product and the sum each rounded to fp64 (no fused multiply-add).
+ * So an entry is bit-equal run to run, under any other choice of rows and cols, and with rows and cols swapped (out(a, b) == out(b, a));
+ * nothing is accumulated with atomics.  Tails in d, nr and nc are handled here.  Refuses (GSS_EINVAL, by name in gss_last_error): a null
+ * emb, rows, cols or out, n < 1, d < 1, ld < d, nr < 1 or nc < 1 (or above 2^21), ld_out < nc, normalize outside {0, 1}, and -- checked on
+ * the device, one status word read at the end -- a list entry outside [0, n) (by list, position and value; no row is read through it) and a
+ * NaN or infinite value in a listed row (by row of emb); out is then unspecified.  The scratch (the status word and the listed rows as
+ * fp64) is allocated and freed inside the call.  Synchronises the stream. */
+int gss_embedding_scores(int32_t n, int32_t d, const float *emb, int64_t ld, int32_t nr, const int32_t *rows, int32_t nc, const int32_t *cols,
+                         int32_t normalize, double *out, int64_t ld_out, void *stream);
 
 /* ---- a13  np.savetxt('graph_embs.txt', hidden_emb), train.py:193 (host-side; h_emb is a HOST pointer) ---------------------
  * Every value of the float32 matrix as Python prints it with '%.18e' after widening to double (exact decimal expansion, round
