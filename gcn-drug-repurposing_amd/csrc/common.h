@@ -21,7 +21,6 @@ struct Knobs {
   int spmm_slices = 0;       // 0 = automatic feature slicing (launch_balanced)
   int spmm_pin = 0;          // with a manual spmm_slices: slices pinned to XCDs (1) or time-separated (0)
   int spmm_hot = -1;         // overrides every CSR's hot set with rows [0, value) (-1 = the CSR's own, 0 = none)
-  int seg_edges = 32;        // entries per SpMM segment (CSR handles created afterwards)
   int spmm_list_blocks = 2048;  // a row-filtered balanced SpMM over at least this many workgroups lists the workgroups that hold a passing row and walks the
                              // list with persistent workgroups (spmm.hip live_blocks_kernel) -- when the caller expects few rows to pass (LiveHint);
                              // 0 = never, 1 = always.  Same bits either way
@@ -45,6 +44,9 @@ struct Knobs {
                              // replicated on every rank (-1 = from B = 8192 on, 0 = never, 1 = always; every rank of a job must use the same value)
   int halo_recompute = -1;   // sharded plans: layer 2's boundary input rows recomputed from layer 1's constant AX / AM instead of exchanged
                              // (-1 = automatic = on, 0 = never, 1 = always; every rank of a job must use the same value)
+  int proj_split = -1;       // one-GPU plans: a layer's forward projection as two launches, the AX half on the plan's side stream beside the layer's
+                             // second SpMM (plan.hip plan_forward_impl): -1 = where dense_fwd_split_auto says it pays (nowhere: it measured
+                             // 31 us per step SLOWER at config 2), 0 = never, 1 = wherever dense_fwd_split_available.  Same bits either way
 };
 template <typename F>
 inline size_t lds_request(F kernel, size_t need) {

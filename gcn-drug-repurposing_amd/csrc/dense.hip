@@ -47,6 +47,9 @@ struct GemmArgs {
                                  // rows_out[rows_out_pos[r]] where that is >= 0 (the batch-position map: E_B of a FULL step)
   float *rows_out;      // EPI_FWD_NORM over a row list (nullable): the unit-norm row of tile row t ALSO goes to rows_out[t] -- the lazy step's
                         // tile rows are the batch positions, so this IS E_B = emb[idx] (model.py:216-217) without a gather launch
+  // K-range forms (PART != 0 of gemm_nt_lds_kernel): the K chunks [c0, c1) of 16 and where the raw accumulators live in between
+  int c0, c1;
+  float *acc;           // [n][ld_out0] fp32 in node-row order: PART 1 writes it, PART 2 starts from it (may be out0: see the kernel)
 };
 
 // Epilogue of the forward projection for one 16-node x 16 NT tile row: lane (r, q) holds OUT[nd][j0 + 16 u + 4 q + 0..3]
@@ -307,8 +310,17 @@ __device__ __forceinline__ XcdIds xcd_ids(int L, int n_spread, int n_share, bool
 
 // WAVES = 1 (forward over a short row list, gss_plan_step_lazy's 2048 batch rows): one wave and 16 MT nodes per workgroup, so that the
 // few rows spread over 4 x as many CUs; a row's MFMA chain is the same, its result has the same bits
-template <int NT, int MT, int EPI, int WAVES = 4, bool LINES = false, int MINW = 1>
+//
+// PART (the forward projection in two launches, so that the half that needs only AX can run beside the layer's second SpMM):
+//   0  the whole reduction and the epilogue (every other use);
+//   1  chunks [g.c0, g.c1) from zero, then the RAW accumulators to g.acc in node-row order, whole 128-B lines -- no bias, no ELU, nothing else;
+//   2  accumulators loaded from g.acc (requested ahead of the K loop), chunks [g.c0, g.c1), then the unchanged epilogue.
+// Contract: PART 1 over [0, c) followed by PART 2 over [c, K / 16) is BIT-IDENTICAL to PART 0.  Every output runs the same MFMA sequence
+// from the same starting value -- an fp32 accumulator survives the round trip through memory unchanged (tests/test_gpu_proj_split.py).
+// g.acc may be the launch's own out0: a lane of PART 2 reads exactly the elements its own epilogue overwrites later, nothing else of g.acc.
+template <int NT, int MT, int EPI, int WAVES = 4, bool LINES = false, int MINW = 1, int PART = 0>
 __global__ __launch_bounds__(64 * WAVES, MINW) void gemm_nt_lds_kernel(GemmArgs g) {
+  static_assert(PART == 0 || (LINES && NT % 2 == 0 && EPI != EPI_SPLIT), "the K-range forms exist for the whole-line forward tiles");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int BN = 16 * NT;
   constexpr int BM = 16 * WAVES * MT;      // nodes per workgroup (MT 16-node tiles per wave)
@@ -352,8 +364,9 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void gemm_nt_lds_kernel(GemmArgs 
 #pragma unroll
     for (int i = 0; i < WG; ++i) wsrc[kh][i] = wp ? wp + (size_t)(jrow0 + 16 * wblk[i] + r) * g.ld_w + 4 * q : nullptr;
   }
-  const int nchunk = g.K / 16;
   const int csplit = g.ksplit / 16;
+  const int cbeg = PART == 0 ? 0 : g.c0;           // chunks [cbeg, nchunk) run here
+  const int nchunk = PART == 0 ? g.K / 16 : g.c1;
   auto stage = [&](int ci) {
     const int kh = ci >= csplit ? 1 : 0;
     const int off = (ci - (kh ? csplit : 0)) * 16;
@@ -365,18 +378,50 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void gemm_nt_lds_kernel(GemmArgs 
   };
 
   f32x4 acc[MT][NT];
+  // PART 2: the first half's accumulators, in the whole-line layout PART 1 stored them in (the lane's column block of both rows of its
+  // even / odd pair).  Requested here, ahead of the first chunk; swapped back into the MFMA layout once the first chunks are on their way
+  float4 part0[PART == 2 ? MT : 1][PART == 2 ? NT / 2 : 1], part1[PART == 2 ? MT : 1][PART == 2 ? NT / 2 : 1];
+  if constexpr (PART == 2) {
+    const int odd = lane & 1;
 #pragma unroll
-  for (int t = 0; t < MT; ++t)
+    for (int t = 0; t < MT; ++t) {
+      const int row0 = node_base + 16 * (MT * w + t) + r - odd;
+      const float *a0 = g.acc + (size_t)min(row0, g.n - 1) * g.ld_out0, *a1 = g.acc + (size_t)min(row0 + 1, g.n - 1) * g.ld_out0;
 #pragma unroll
-    for (int u = 0; u < NT; ++u) acc[t][u] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      for (int m = 0; m < NT / 2; ++m) {
+        const int j = j0 + 32 * m + 16 * odd + 4 * q;
+        part0[t][m] = ld4(a0 + j);
+        part1[t][m] = ld4(a1 + j);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int t = 0; t < MT; ++t)
+#pragma unroll
+      for (int u = 0; u < NT; ++u) acc[t][u] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
 
   // the epilogue's own operands, requested before the first chunk (one 16-node tile per wave; with two the registers are better spent)
-  constexpr bool HOIST = EPI != EPI_SPLIT && MT == 1 && WAVES <= 4 && NT <= 8;   // (a 256-feature tile row: 32 more float4 would not fit)
+  constexpr bool HOIST = PART != 1 && EPI != EPI_SPLIT && MT == 1 && WAVES <= 4 && NT <= 8;   // (a 256-feature tile row: 32 more float4 would not fit)
   FwdPre<NT> pre;
   if (HOIST) fwd_prefetch<NT, EPI, LINES>(g, node_base + 16 * (MT * w) + r, j0, q, pre);
 
-  for (int c = 0; c < PF && c < nchunk; ++c) stage(c);
-  for (int ci = 0; ci < nchunk; ++ci) {
+  for (int c = cbeg; c < cbeg + PF && c < nchunk; ++c) stage(c);
+  if constexpr (PART == 2) {
+    // (these loads are older than every LDS-DMA load, so the counted waits below stay sound; the compiler's own wait for them is a full
+    //  drain, once, of chunks the loop needs next anyway)
+    const bool odd = (lane & 1) != 0;
+#pragma unroll
+    for (int t = 0; t < MT; ++t)
+#pragma unroll
+      for (int m = 0; m < NT / 2; ++m) {
+        const float4 got = swap_neighbour(odd ? part0[t][m] : part1[t][m]);   // even lane: its own upper block; odd lane: its own lower block
+        const float4 lo = odd ? got : part0[t][m], hi = odd ? part1[t][m] : got;
+        acc[t][2 * m] = (f32x4){lo.x, lo.y, lo.z, lo.w};
+        acc[t][2 * m + 1] = (f32x4){hi.x, hi.y, hi.z, hi.w};
+      }
+  }
+  for (int ci = cbeg; ci < nchunk; ++ci) {
     // chunk ci has landed once at most min(PF-1, nchunk-1-ci) younger chunks of this wave are outstanding
     const int younger = min(PF - 1, nchunk - 1 - ci);
     if (younger >= 2)
@@ -412,7 +457,20 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void gemm_nt_lds_kernel(GemmArgs 
 #pragma unroll
   for (int t = 0; t < MT; ++t) {
     const int nd = node_base + 16 * (MT * w + t) + r;
-    if (EPI == EPI_SPLIT && LINES && NT % 2 == 0) {
+    if constexpr (PART == 1) {
+      // the raw accumulators in whole 128-B lines (the layout of fwd_epilogue_lines; PART 2 reads it back lane for lane)
+      const bool odd = (lane & 1) != 0;
+      const int row0 = nd - (odd ? 1 : 0), row1 = row0 + 1;
+#pragma unroll
+      for (int m = 0; m < NT / 2; ++m) {
+        const float4 lo = make_float4(acc[t][2 * m][0], acc[t][2 * m][1], acc[t][2 * m][2], acc[t][2 * m][3]);
+        const float4 hi = make_float4(acc[t][2 * m + 1][0], acc[t][2 * m + 1][1], acc[t][2 * m + 1][2], acc[t][2 * m + 1][3]);
+        const float4 got = swap_neighbour(odd ? lo : hi);
+        const int j = j0 + 32 * m + (odd ? 16 : 0) + 4 * q;
+        if (row0 < g.n) st4(g.acc + (size_t)row0 * g.ld_out0 + j, odd ? got : lo);
+        if (row1 < g.n) st4(g.acc + (size_t)row1 * g.ld_out0 + j, odd ? hi : got);
+      }
+    } else if (EPI == EPI_SPLIT && LINES && NT % 2 == 0) {
       // whole 128-B lines, as fwd_epilogue_lines: the lanes of an even / odd node pair swap one block of every block pair
       const bool odd = (lane & 1) != 0;
       const int row0 = nd - (odd ? 1 : 0), row1 = row0 + 1;
@@ -753,9 +811,26 @@ __global__ __launch_bounds__(256, 1) void proj_ws_kernel(GemmArgs g) {
 
 constexpr int kWsMinRows = 256 * 128 + 1;   // gemm_ws = -1: the weight-stationary projection from this many rows on -- more 128-node tiles than CUs
 
-template <int EPI>
+// The forward projection in two launches (PART 1, then PART 2 of gemm_nt_lds_kernel): which launches have such a form.  The whole-line
+// staged tiles that gemm_variant 2 picks at d = 64, 128 and 256 without a row list; not where the weight-stationary kernel takes over
+// (kWsMinRows), not the row-list kernels, not a width the tiles have no template for.  launch_gemm<EPI, PART> below refuses the rest.
+bool dense_fwd_split_available(int32_t n, int32_t d) {
+  if (n <= 0 || K().gemm_variant != 2 || !(d == 64 || d == 128 || d == 256)) return false;
+  const bool ws = K().gemm_ws == 1 || (K().gemm_ws < 0 && n >= kWsMinRows);
+  return !(ws && d == 128);
+}
+// knob proj_split = -1: where the split is taken without being asked for -- NOWHERE.  Measured at N = 29,960, d = 128, L = 2 on one live
+// plan: 0.2970 ms per step in one launch, 0.3282 ms with both layers split (profiles/proj_split_bench_ab.txt).
+bool dense_fwd_split_auto(int32_t, int32_t) { return false; }
+
+template <int EPI, int PART = 0>
 static int launch_gemm(const GemmArgs &g, int d, hipStream_t st) {
   if (g.n <= 0) return GSS_OK;
+  if (PART != 0) {
+    GSS_REQUIRE(EPI != EPI_SPLIT && !g.rows && g.acc && g.in0 && (PART == 1 || g.in1) && g.J == d && g.jsplit == d && dense_fwd_split_available(g.n, d),
+                "dense_fwd: no two-launch form of this projection");
+    GSS_REQUIRE(0 <= g.c0 && g.c0 < g.c1 && g.c1 <= g.K / 16, "dense_fwd: empty K-chunk range");
+  }
   {
     int nt = (d % 128 == 0) ? 8 : (d % 64 == 0) ? 4 : (d % 32 == 0) ? 2 : 1;
     if (EPI == EPI_FWD_NORM && d == 256) nt = 16;   // the fused row norm needs a row's features in one tile
@@ -767,7 +842,7 @@ static int launch_gemm(const GemmArgs &g, int d, hipStream_t st) {
     // W-staging redundancy of small tiles costs more than that buys (profiles/r03_projection_pipeline_experiments.txt), and so it does once
     // the grid is many waves of workgroups deep (d = 128: N = 1M 791 -> 753 us, N = 4M 3061 -> 2913 us with 128-node tiles)
     const int mt = K().gemm_variant == 3 ? 2 : ((d >= 256 || g.n >= 262144) ? 2 : 1);
-    if (EPI != EPI_SPLIT && g.rows && (int64_t)ceil_div(g.n, 64) * (g.J / (16 * nt)) < 256) {
+    if (PART == 0 && EPI != EPI_SPLIT && g.rows && (int64_t)ceil_div(g.n, 64) * (g.J / (16 * nt)) < 256) {
       // forward over a short row list: 16 listed rows per workgroup.  Whole rows of 64 / 128 / 256 features: 4 waves that split the
       // features (gemm_rows_split_kernel, same bits); other widths: one wave per 16 x 16 nt tile
       if (EPI != EPI_SPLIT && g.J == d && g.jsplit == d && (d == 64 || d == 128 || d == 256)) {
@@ -793,7 +868,7 @@ static int launch_gemm(const GemmArgs &g, int d, hipStream_t st) {
       GSS_LAUNCH_CHECK("gemm_nt_lds_kernel (one wave)");
       return GSS_OK;
     }
-    if constexpr (EPI != EPI_SPLIT) {
+    if constexpr (EPI != EPI_SPLIT && PART == 0) {
       // d = 128, all rows: the weight-stationary persistent kernel (round 5; proj_ws_kernel above).  Same bits as the staged tiles.  It
       // spends ~5 us per workgroup pulling its 128 KB of weights before the first MFMA and earns that back tile by tile: slower than the
       // staged tiles while those fit the chip in one round (<= 256 tiles of 128 nodes: 31.3 vs 28.5 us at N = 32,768), faster from the
@@ -821,7 +896,7 @@ static int launch_gemm(const GemmArgs &g, int d, hipStream_t st) {
       // trainer's).  gemm_variant 5 forces it for other widths, 3 forces the 4-wave 128-node tiles.
       dim3 grid8(ceil_div(g.n, 128), g.J / (16 * nt));
       const size_t lds8 = 4 * (size_t)(128 * 16 + 16 * nt * 16) * sizeof(float);
-      hipLaunchKernelGGL((gemm_nt_lds_kernel<8, 1, EPI, 8, true, 4>), grid8, dim3(512), lds8, st, g);
+      hipLaunchKernelGGL((gemm_nt_lds_kernel<8, 1, EPI, 8, true, 4, PART>), grid8, dim3(512), lds8, st, g);
       GSS_LAUNCH_CHECK("gemm_nt_lds_kernel (8 waves)");
       return GSS_OK;
     }
@@ -835,11 +910,11 @@ static int launch_gemm(const GemmArgs &g, int d, hipStream_t st) {
         dim3 gridn(ceil_div(g.n, 128), 1);
         const size_t ldsn = 4 * (size_t)(128 * 16 + 256 * 16) * sizeof(float);
         if (K().gemm_variant != 3) {
-          hipLaunchKernelGGL((gemm_nt_lds_kernel<16, 1, EPI_FWD_NORM, 8, true, 2>), gridn, dim3(512), lds_request(gemm_nt_lds_kernel<16, 1, EPI_FWD_NORM, 8, true, 2>, ldsn), st, g);
+          hipLaunchKernelGGL((gemm_nt_lds_kernel<16, 1, EPI_FWD_NORM, 8, true, 2, PART>), gridn, dim3(512), lds_request(gemm_nt_lds_kernel<16, 1, EPI_FWD_NORM, 8, true, 2, PART>, ldsn), st, g);
           GSS_LAUNCH_CHECK("gemm_nt_lds_kernel (256 features, fused row norm, 8 waves)");
           return GSS_OK;
         }
-        hipLaunchKernelGGL((gemm_nt_lds_kernel<16, 2, EPI_FWD_NORM, 4, true>), gridn, dim3(256), lds_request(gemm_nt_lds_kernel<16, 2, EPI_FWD_NORM, 4, true>, ldsn), st, g);
+        if constexpr (PART == 0) hipLaunchKernelGGL((gemm_nt_lds_kernel<16, 2, EPI_FWD_NORM, 4, true>), gridn, dim3(256), lds_request(gemm_nt_lds_kernel<16, 2, EPI_FWD_NORM, 4, true>, ldsn), st, g);
         GSS_LAUNCH_CHECK("gemm_nt_lds_kernel (256 features, fused row norm)");
         return GSS_OK;
       }
@@ -851,9 +926,9 @@ static int launch_gemm(const GemmArgs &g, int d, hipStream_t st) {
 #define GSS_GEMM_LINES(NTV)                                                                             \
   case NTV:                                                                                             \
     if (mt == 2)                                                                                        \
-      hipLaunchKernelGGL((gemm_nt_lds_kernel<NTV, 2, E, 4, true>), grid, dim3(256), lds, st, g);        \
+      hipLaunchKernelGGL((gemm_nt_lds_kernel<NTV, 2, E, 4, true, 1, PART>), grid, dim3(256), lds, st, g); \
     else                                                                                                \
-      hipLaunchKernelGGL((gemm_nt_lds_kernel<NTV, 1, E, 4, true>), grid, dim3(256), lds, st, g);        \
+      hipLaunchKernelGGL((gemm_nt_lds_kernel<NTV, 1, E, 4, true, 1, PART>), grid, dim3(256), lds, st, g); \
     break;
       switch (nt) {
         GSS_GEMM_LINES(8)
@@ -865,6 +940,8 @@ static int launch_gemm(const GemmArgs &g, int d, hipStream_t st) {
       GSS_LAUNCH_CHECK("gemm_nt_lds_kernel (whole lines)");
       return GSS_OK;
     }
+    if constexpr (PART != 0) return fail(GSS_EINVAL, "dense_fwd: no two-launch form of this projection");
+    else {
 #define GSS_GEMM_CASE(NTV)                                                                              \
   case NTV:                                                                                             \
     if (mt == 2)                                                                                        \
@@ -882,11 +959,34 @@ static int launch_gemm(const GemmArgs &g, int d, hipStream_t st) {
 #undef GSS_GEMM_CASE
     GSS_LAUNCH_CHECK("gemm_nt_lds_kernel");
     return GSS_OK;
+    }
   }
 }
 
+// The AX half of a forward projection on its own: acc[n][j] = sum_k AX[n][k] W1[j][k], raw, into `acc` (the layer's P buffer).
+// dense_fwd / dense_fwd_norm with acc_in_p finish it: they start from those accumulators, add the AM half and run their usual epilogue.
+int dense_fwd_first(int32_t n, int32_t d, const float *ax, const float *w1, float *acc, void *stream) {
+  if (int rc = check_d(d)) return rc;
+  GSS_REQUIRE(n >= 0 && ax && w1 && acc, "dense_fwd_first: null operand");
+  GemmArgs g{};
+  g.n = n;
+  g.K = 2 * d;
+  g.ksplit = d;
+  g.J = d;
+  g.jsplit = d;
+  g.in0 = ax;
+  g.ld_in0 = g.ld_in1 = d;
+  g.w[0][0] = w1;
+  g.ld_w = d;
+  g.ld_out0 = g.ld_out1 = d;
+  g.c0 = 0;
+  g.c1 = d / 16;
+  g.acc = acc;
+  return launch_gemm<EPI_FWD, 1>(g, d, as_stream(stream));
+}
+
 int dense_fwd(int32_t n, int32_t d, const float *ax, const float *am, const float *w1, const float *b1, const float *w2,
-              const float *b2, const float *p_prev, float decay, float *p, float *x_next, void *stream, const int32_t *row_list) {
+              const float *b2, const float *p_prev, float decay, float *p, float *x_next, void *stream, const int32_t *row_list, bool acc_in_p) {
   if (int rc = check_d(d)) return rc;
   GSS_REQUIRE(n >= 0 && ax && am && w1 && b1 && w2 && b2 && p && x_next, "dense_fwd: null operand");
   GemmArgs g{};
@@ -911,6 +1011,12 @@ int dense_fwd(int32_t n, int32_t d, const float *ax, const float *am, const floa
   g.x_next = x_next;
   g.decay = decay;
   g.rows = row_list;
+  if (acc_in_p) {
+    g.c0 = d / 16;
+    g.c1 = 2 * d / 16;
+    g.acc = p;
+    return launch_gemm<EPI_FWD, 2>(g, d, as_stream(stream));
+  }
   return launch_gemm<EPI_FWD>(g, d, as_stream(stream));
 }
 
@@ -919,7 +1025,7 @@ bool dense_fwd_norm_available(int32_t d) { return d == 256 || d == 128 || d == 6
 
 int dense_fwd_norm(int32_t n, int32_t d, const float *ax, const float *am, const float *w1, const float *b1, const float *w2,
                    const float *b2, const float *p_prev, float decay, float *p, float *e, float *inv_den, void *stream, const int32_t *row_list,
-                   float *rows_out, const int32_t *rows_out_pos) {
+                   float *rows_out, const int32_t *rows_out_pos, bool acc_in_p) {
   if (int rc = check_d(d)) return rc;
   GSS_REQUIRE(n >= 0 && ax && am && w1 && b1 && w2 && b2 && p && e && inv_den, "dense_fwd_norm: null operand");
   GSS_REQUIRE(dense_fwd_norm_available(d), "dense_fwd_norm: needs d in {16, 32, 64, 128, 256}");
@@ -947,6 +1053,12 @@ int dense_fwd_norm(int32_t n, int32_t d, const float *ax, const float *am, const
   GSS_REQUIRE(!rows_out || (row_list != nullptr) != (rows_out_pos != nullptr), "dense_fwd_norm: rows_out goes with a row list or with a position map");
   g.rows_out = rows_out;
   g.rows_out_pos = rows_out_pos;
+  if (acc_in_p) {
+    g.c0 = d / 16;
+    g.c1 = 2 * d / 16;
+    g.acc = p;
+    return launch_gemm<EPI_FWD_NORM, 2>(g, d, as_stream(stream));
+  }
   return launch_gemm<EPI_FWD_NORM>(g, d, as_stream(stream));
 }
 

@@ -16,7 +16,7 @@ struct gss_csr {
   int32_t *d_long_rows = nullptr;
   int32_t max_row = 0;
   int32_t hot_own = -1, hot_halo0 = 0, hot_halo1 = 0;  // gss_csr_set_hot: operand rows [0, hot_own) and [hot_halo0, hot_halo1) are the hubs' (-1: no split)
-  int32_t seg_edges = 32;         // entries per segment of the balanced SpMM: knob spmm_seg_edges at gss_csr_create (a view: its parent's)
+  int32_t seg_edges = 32;         // entries per segment of the balanced SpMM (a view: its parent's)
   std::vector<int32_t> h_rowptr;  // host copy, used to build segment descriptors lazily
   // a VIEW (spmm.hip GiantRows): the schedule covers the listed rows / entry ranges of the borrowed arrays instead of every row of rowptr
   bool by_items = false;
@@ -114,14 +114,20 @@ int spmm_bwd2(const gss_csr *at, int32_t d, const float *u, const float *t, cons
               int32_t own_row_limit = 0);   // > 0: t and res exist for output rows below it only (the in-place transposed shard, plan.hip)
 int dense_fwd(int32_t n, int32_t d, const float *ax, const float *am, const float *w1, const float *b1, const float *w2,
               const float *b2, const float *p_prev, float decay, float *p, float *x_next, void *stream,
-              const int32_t *row_list = nullptr);  // row_list: the n tile rows are node rows row_list[0..n) of every operand; a negative
+              const int32_t *row_list = nullptr,   // row_list: the n tile rows are node rows row_list[0..n) of every operand; a negative
                                                    // entry is skipped (nothing of it is written)
+              bool acc_in_p = false);              // the second of two launches: p holds dense_fwd_first's accumulators (same bits as one launch)
+// the forward projection in two launches, so that the half that needs only AX can run beside the layer's second SpMM (plan.hip)
+bool dense_fwd_split_available(int32_t n, int32_t d);   // dense_fwd_first + acc_in_p exist for this projection (under the current knobs)
+bool dense_fwd_split_auto(int32_t n, int32_t d);        // ... and knob proj_split = -1 takes them
+int dense_fwd_first(int32_t n, int32_t d, const float *ax, const float *w1, float *acc, void *stream);   // acc = AX W1^T, raw, [n][d]
 bool dense_fwd_norm_available(int32_t d);
 int dense_fwd_norm(int32_t n, int32_t d, const float *ax, const float *am, const float *w1, const float *b1, const float *w2,
                    const float *b2, const float *p_prev, float decay, float *p, float *e, float *inv_den, void *stream,
                    const int32_t *row_list = nullptr, float *rows_out = nullptr,    // rows_out: tile row t's unit-norm row also to rows_out[t]
-                   const int32_t *rows_out_pos = nullptr);   // without a row list: node row r's unit-norm row also to rows_out[rows_out_pos[r]]
+                   const int32_t *rows_out_pos = nullptr,    // without a row list: node row r's unit-norm row also to rows_out[rows_out_pos[r]]
                                                              // where that is >= 0 (the batch-position map: E_B without a gather launch)
+                   bool acc_in_p = false);                   // as dense_fwd
 float *loss_workspace_e_b(int32_t d, int32_t b, void *ws);   // where loss_gather_rows* would put E_B for a batch of b rows
 int dense_bwd_input(int32_t n, int32_t d, const float *dp, const float *w1t, const float *w2t, const int32_t *rows,
                     float *g_ax, float *g_am, void *stream);

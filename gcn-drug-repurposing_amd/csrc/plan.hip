@@ -49,6 +49,9 @@ struct gss_plan {
   // step t+1's run on `side` underneath step t's MFMA-bound kernels, into the other half of a double buffer
   hipStream_t side;
   hipEvent_t ev_main_ready, ev_side_done;
+  // knob proj_split (one GPU, no pipeline_layer1 -- that option owns `side`): layer l's AX half of the projection runs on `side` between
+  // ev_split_go[l] (the caller's stream, after the layer's first SpMM) and ev_split_done[l] (what the caller's stream waits for)
+  std::vector<hipEvent_t> ev_split_go, ev_split_done;
   float *ax0[2], *am0[2], *m_side;
   int cur0;
   bool prefetched;
@@ -537,6 +540,21 @@ int plan_create_impl(gss_plan **out, const gss_plan_desc *desc, const gss_shard_
       delete p;
       return fail(GSS_EHIP, "plan_create: side stream/events -> %s", hipGetErrorString(e));
     }
+  } else if (P == 1 && dense_fwd_split_available(desc->n, desc->d)) {
+    // (made whatever proj_split says now: gss_plan_debug_set_option may switch it on a live plan)
+    e = hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking);
+    for (int l = 0; l < desc->num_layers && e == hipSuccess; ++l) {
+      hipEvent_t go = nullptr, done = nullptr;
+      e = hipEventCreateWithFlags(&go, hipEventDisableTiming);
+      if (e == hipSuccess) e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
+      if (go) p->ev_split_go.push_back(go);
+      if (done) p->ev_split_done.push_back(done);
+    }
+    if (e != hipSuccess) {
+      (void)hipFree(p->slab);
+      delete p;
+      return fail(GSS_EHIP, "plan_create: side stream/events -> %s", hipGetErrorString(e));
+    }
   }
   if (p->a_own || p->at_own) {
     e = hipStreamCreateWithFlags(&p->xs, hipStreamNonBlocking);
@@ -841,6 +859,7 @@ int plan_forward_impl(gss_plan *p, void *stream, const int32_t *lazy_rows = null
   for (int l = 0; l < L; ++l) {
     float *xl = p->xin[l];
     const bool cached = (l == 0 && ((D.cache_layer1 && p->layer1_valid) || have_l0));
+    bool split_l = false;   // this layer's projection in two launches (a cached layer runs no SpMM to hide the first one under)
     if (!cached) {
       // AX = A x ; M = AX (.) x      (model.py:163,168); x's boundary rows come from their owners (C1)
       if (l == 0)
@@ -893,6 +912,21 @@ int plan_forward_impl(gss_plan *p, void *stream, const int32_t *lazy_rows = null
           if (int rc = plan_hop(p, p->halo_a, split_a, xl, stream, full, own, rest)) return rc;
         }
       }
+      // knob proj_split: P = AX W1^T + AM W2^T + b, and the AX half needs nothing of the product below -- which binds on the L2 request
+      // rate and leaves the matrix pipe idle.  So that half goes to the side stream, from here (AX is complete; every earlier reader of
+      // this layer's P on the caller's stream has been passed) to the projection proper, which starts from its accumulators (kept in P).
+      // Same bits as one launch (dense.hip, PART).  With profiling on, the class times of overlapped kernels sum to more than the wall time.
+      split_l = (int)p->ev_split_go.size() == L && !lazy_l && p->P == 1 && !D.pipeline_layer1 && dense_fwd_split_available(D.n, D.d) &&
+                (K().proj_split == 1 || (K().proj_split < 0 && dense_fwd_split_auto(D.n, D.d)));
+      if (split_l) {
+        GSS_HIP(hipEventRecord(p->ev_split_go[l], as_stream(stream)));
+        GSS_HIP(hipStreamWaitEvent(p->side, p->ev_split_go[l], 0));
+        {
+          ProfScope prof_first(p, GSS_PROF_DENSE_FWD, p->side);
+          if (int rc = dense_fwd_first(D.n, D.d, p->ax[l], p->w1, p->p[l], p->side)) return rc;
+        }
+        GSS_HIP(hipEventRecord(p->ev_split_done[l], p->side));
+      }
       // AM = A M                      (model.py:169)
       {
         const int32_t *rpos = lazy_l ? p->pos : nullptr;
@@ -925,6 +959,7 @@ int plan_forward_impl(gss_plan *p, void *stream, const int32_t *lazy_rows = null
         p->l0h_ready = true;
       }
     }
+    if (split_l) GSS_HIP(hipStreamWaitEvent(as_stream(stream), p->ev_split_done[l], 0));
     PROF(GSS_PROF_DENSE_FWD);
     if (l == L - 1 && dense_fwd_norm_available(D.d)) {
       // last layer: F.normalize fused into the GEMM epilogue (no x_last round trip, no extra launch)
@@ -940,7 +975,7 @@ int plan_forward_impl(gss_plan *p, void *stream, const int32_t *lazy_rows = null
       // a full step whose batch was prepared by the first SpMM's side job: the batch members' unit-norm rows also go to E_B
       float *e_b = (p->eb_scatter_b > 0 && p->pos) ? loss_workspace_e_b(D.d, p->eb_scatter_b, p->loss_ws) : nullptr;
       if (int rc = dense_fwd_norm(D.n, D.d, p->ax[l], p->am[l], p->w1, p->b1, p->w2, p->b2, l > 0 ? p->p[l - 1] : nullptr, D.layer_decay,
-                                  p->p[l], p->emb, p->inv_den, stream, nullptr, e_b, e_b ? p->pos : nullptr))
+                                  p->p[l], p->emb, p->inv_den, stream, nullptr, e_b, e_b ? p->pos : nullptr, split_l))
         return rc;
       p->eb_rows = e_b ? p->eb_scatter_b : 0;
       return GSS_OK;
@@ -951,7 +986,7 @@ int plan_forward_impl(gss_plan *p, void *stream, const int32_t *lazy_rows = null
     // halo_recompute: layer 1's projection also produces the boundary rows of layer 2's input (l == 0 < L - 1 there)
     const int32_t n_proj = (l == 0 && p->recompute) ? (int32_t)p->rows_a : D.n;
     if (int rc = dense_fwd(listed ? lazy_b : n_proj, D.d, p->ax[l], p->am[l], p->w1, p->b1, p->w2, p->b2, l > 0 ? p->p[l - 1] : nullptr,
-                           D.layer_decay, p->p[l], xn, stream, listed ? lazy_rows : nullptr))
+                           D.layer_decay, p->p[l], xn, stream, listed ? lazy_rows : nullptr, split_l))
       return rc;
   }
   PROF(GSS_PROF_ROWNORM);
@@ -1335,6 +1370,8 @@ void gss_plan_destroy(gss_plan *p) {
   if (p->ev_halo) (void)hipEventDestroy(p->ev_halo);
   if (p->ev_main_ready) (void)hipEventDestroy(p->ev_main_ready);
   if (p->ev_side_done) (void)hipEventDestroy(p->ev_side_done);
+  for (hipEvent_t e : p->ev_split_go) (void)hipEventDestroy(e);
+  for (hipEvent_t e : p->ev_split_done) (void)hipEventDestroy(e);
   if (p->lz.h_cnt) (void)hipHostFree(p->lz.h_cnt);
   if (p->lzt.h_cnt) (void)hipHostFree(p->lzt.h_cnt);
   if (p->slab) (void)hipFree(p->slab);
@@ -1347,7 +1384,7 @@ void gss_plan_destroy(gss_plan *p) {
 // different addresses); the same plan under alternating settings does not.
 int gss_plan_debug_set_option(gss_plan *p, const char *name, int value) {
   GSS_REQUIRE(p && name, "plan_debug_set_option: null argument");
-  static const char *const kLive[] = {"gemm_variant", "spmm_slices", "spmm_pin", "gemm_ws", "spmm_list_blocks"};
+  static const char *const kLive[] = {"gemm_variant", "spmm_slices", "spmm_pin", "gemm_ws", "spmm_list_blocks", "proj_split"};
   bool ok = false;
   for (const char *k : kLive) ok = ok || strcmp(k, name) == 0;
   GSS_REQUIRE(ok, "plan_debug_set_option: only kernel-selection knobs can change on a live plan");

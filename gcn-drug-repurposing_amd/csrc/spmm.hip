@@ -250,7 +250,7 @@ __global__ __launch_bounds__(kLongThreads) void spmm_long_kernel(CsrView a, cons
 // A persistent launch (512-1024 resident workgroups looping over segment blocks, the next block's descriptor and first
 // (col, val) chunk requested under the current block's epilogue) measured 36.9 us vs 30.8 us at d = 128: the loop costs
 // more in the per-block code than the hardware dispatcher costs between workgroups.
-// debug knob "spmm_seg_edges" (applies to CSR handles created afterwards)   [knob seg_edges, common.h Knobs]
+// (segments of 32 stored entries, gss_csr::seg_edges: 16 / 24 / 48 / 64 never beat it inside the step, so the knob that swept it is gone)
 constexpr int kBalThreads = 1024;  // 512-thread workgroups measured 5-30 % slower (hub rows get half the groups)
 constexpr int kBalWaves = kBalThreads / 64;
 constexpr int kListWorkgroups = 1024;   // persistent workgroups of a list launch (two rounds of the 512 that fit the chip)
@@ -1225,7 +1225,6 @@ int gss_csr_create(gss_csr **out, int32_t n_rows, int32_t n_cols, int64_t nnz, c
   a->rowptr = d_rowptr;
   a->col = d_col;
   a->val = d_val;
-  a->seg_edges = K().seg_edges;
   std::vector<int32_t> h_long;
   for (int32_t r = 0; r < n_rows; ++r) {
     const int32_t len = h_rowptr[r + 1] - h_rowptr[r];

@@ -696,16 +696,17 @@ enum {
 int gss_plan_profile(gss_plan *p, int enable);
 int gss_plan_profile_read(gss_plan *p, double *ms_out, int64_t *count_out, void *stream);
 /* tuning/debug knobs (A/B runs inside one process; 19 of them -- round 6 removed the access-shape variants whose sweeps said "default holds" in
- * two or more rounds from the kernels): "spmm_list_blocks" = workgroups from which a ROW-FILTERED balanced SpMM (the lazy step's
+ * two or more rounds from the kernels; "spmm_seg_edges" left when "proj_split" came: the segment length is 32 entries): "spmm_list_blocks" = workgroups from which a ROW-FILTERED balanced SpMM (the lazy step's
  * top-layer products, the batch-sparse backward hop) lists the workgroups that hold a passing row and walks the list with persistent
  * workgroups instead of dispatching every workgroup (default 2048; 0 = never; same bits); "spmm_variant" = 1 (whole-row gather, wave per row) or
  * 2 (nnz-balanced segments, default); "spmm_slices" = 0 (automatic, default) or 1..8 feature slices in the balanced SpMM, "spmm_pin" = with a
  * manual "spmm_slices": slices time-separated (0, default) or pinned to XCDs (1) -- the automatic policy pins operands of <= 64 MB;
- * "spmm_hot_rows" = -1 (default: what gss_csr_set_hot declared) or a row count; "spmm_seg_edges" = entries per SpMM segment (default 32;
- * applies to gss_csr handles created afterwards); "spmm_giant" = stored entries above which a row is summed chunk by chunk across workgroups
+ * "spmm_hot_rows" = -1 (default: what gss_csr_set_hot declared) or a row count; "spmm_giant" = stored entries above which a row is summed chunk by chunk across workgroups
  * (default 32768, 0 = never; gss_csr_giant_rows); "gemm_variant" = projection tile shape: 2 (by width and row count; default), 3 (128-node
  * tiles of four waves forced), 5 (128-node tiles of eight waves forced); "gemm_ws" = -1 (default: from 32,769 rows on -- more 128-node
  * tiles than CUs) / 0 / 1: the d = 128 forward projection as the weight-stationary persistent kernel (same bits);
+ * "proj_split" = -1 (default: by size -- off) / 0 / 1: a one-GPU plan runs the AX half of a layer's forward projection on its side
+ * stream beside the layer's second SpMM and finishes it in a second launch (widths 64 / 128 / 256 below the weight-stationary row count; same bits);
  * "wgrad_wgs", "loss_wgs" = workgroups of a full-size weight-gradient launch / the loss sweep (default 256 = one per CU; set
  * before plans are created); "sparse_bits_rows" = operand rows from which a plan keeps the bitmaps of the sparsity-aware backward hops
  * (default 100000); "ppr_fused" = 1 (default) / 0 (separate update pass of the diffusion profiles);
