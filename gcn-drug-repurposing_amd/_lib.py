@@ -9,7 +9,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgssgcn.so")
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 _lib = None
 
@@ -174,6 +174,13 @@ SIGNATURES = {
     "gss_auc_rows": (C.c_int, [_I32, _I32, _P, _I64, _P, _P, _P, _P, _P, _P]),
     "gss_profile_dist": (C.c_int, [_I32, _P, _I64, _I32, _P, _I32, _P, _I32, _P, _I64, _P]),
     "gss_embedding_scores": (C.c_int, [_I32, _I32, _P, _I64, _I32, _P, _I32, _P, _I32, _P, _I64, _P]),
+    # for tests: the row-sparse SpMM modes and their bitmap builders (tests/test_gpu_sparse_ops.py)
+    "gss_spmm_bwd1_sparse_ex": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _P]),
+    "gss_spmm_bwd2_sparse_res": (C.c_int, [_P, _I32, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _I32, _P]),
+    "gss_spmm_filtered": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gss_mark_rows_and_neighbours": (C.c_int, [_P, _P, _I32, _P, _P]),
+    "gss_batch_bits": (C.c_int, [_P, _I32, _P, _I32, _P]),
+    "gss_bits_fill": (C.c_int, [_P, _I64, _I64, _P]),
 }
 
 

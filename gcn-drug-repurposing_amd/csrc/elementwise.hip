@@ -643,4 +643,7 @@ int gss_adam_step(int64_t count, float *param, const float *grad, float *exp_avg
                   float beta1, float beta2, float eps, float *wt, int32_t dim, void *stream) {
   return adam_step(count, param, grad, exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps, wt, dim, stream);
 }
+// for tests (tests/test_gpu_sparse_ops.py): the bitmap builders of the row-sparse SpMM modes, as the plan calls them
+int gss_batch_bits(const int32_t *ids, int32_t b, uint32_t *bits, int32_t set, void *stream) { return batch_bits(ids, b, bits, set, stream); }
+int gss_bits_fill(uint32_t *bits, int64_t first, int64_t last, void *stream) { return bits_fill(bits, first, last, stream); }
 }

@@ -1292,4 +1292,26 @@ int gss_spmm_bwd2(const gss_csr *at, int32_t d, const float *u, const float *t, 
                   float *dp, float *gx_out, void *stream) {
   return spmm_bwd2(at, d, u, t, p, c, res, dp, gx_out, stream);
 }
+
+// ---- for tests (tests/test_gpu_sparse_ops.py): the row-sparse modes with their full argument lists, as the plan calls them ----
+int gss_spmm_bwd1_sparse_ex(const gss_csr *at, int32_t d, const float *g_am_b, const float *g_ax_b, const int32_t *pos_col,
+                            const int32_t *pos_row, const float *x_in, const float *ax, float *u, float *t, const uint32_t *posbits,
+                            uint32_t *nzbits_out, int32_t skip_zero_rows, const uint32_t *live_rows, void *stream) {
+  GSS_REQUIRE(at, "gss_spmm_bwd1_sparse_ex: null handle");
+  return spmm_bwd1_sparse(at, d, g_am_b, g_ax_b, pos_col, pos_row, x_in, ax, u, t, stream, posbits, nzbits_out, skip_zero_rows, live_rows);
+}
+int gss_spmm_bwd2_sparse_res(const gss_csr *at, int32_t d, const float *u, const float *t, const float *p, float c, const float *res_b,
+                             const int32_t *pos_row, float *dp, float *gx_out, const uint32_t *nzbits, const float *y_in,
+                             int32_t pos_row_limit, void *stream) {
+  GSS_REQUIRE(at, "gss_spmm_bwd2_sparse_res: null handle");
+  return spmm_bwd2_sparse_res(at, d, u, t, p, c, res_b, pos_row, dp, gx_out, stream, nzbits, y_in, pos_row_limit);
+}
+int gss_spmm_filtered(const gss_csr *a, int32_t d, const float *x, float *y, const float *h, float *m, const int32_t *row_pos,
+                      const uint32_t *row_bits, const float *y_in, const uint32_t *gather_bits, void *stream) {
+  GSS_REQUIRE(a && x && y, "gss_spmm_filtered: null operand");
+  return spmm_fwd(a, d, x, y, h, m, stream, row_pos, row_bits, y_in, gather_bits);
+}
+int gss_mark_rows_and_neighbours(const gss_csr *a, const int32_t *rows, int32_t b, uint32_t *bits, void *stream) {
+  return mark_rows_and_neighbours(a, rows, b, bits, stream);
+}
 }

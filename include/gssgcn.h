@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define GSS_ABI_VERSION 14  /* 14: indication x drug scores from the embedding tensor -- gss_embedding_scores; 13: pairwise distances between diffusion profiles -- gss_profile_dist; 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
+#define GSS_ABI_VERSION 15  /* 15: entry points for tests of the row-sparse SpMM modes -- gss_spmm_bwd1_sparse_ex, gss_spmm_bwd2_sparse_res, gss_spmm_filtered, gss_mark_rows_and_neighbours, gss_batch_bits, gss_bits_fill; 14:indication x drug scores from the embedding tensor -- gss_embedding_scores; 13: pairwise distances between diffusion profiles -- gss_profile_dist; 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
 
 #define GSS_OK 0
 #define GSS_EINVAL (-22)   /* bad argument (shape, null pointer, unsupported d) */
@@ -726,6 +726,37 @@ int gss_plan_profile_read(gss_plan *p, double *ms_out, int64_t *count_out, void 
 int gss_debug_set_option(const char *name, int value);
 /* plain device-to-device copy on `stream` (lets a ctypes host read plan-owned activations) */
 int gss_memcpy_d2d(void *dst, const void *src, size_t bytes, void *stream);
+
+/* ---- FOR TESTS: the row-sparse SpMM modes and their bitmap builders, exactly as a plan's step launches them --------------------
+ * These entry points exist so that tests/test_gpu_sparse_ops.py can hold every mode to its fp64 contract (tests/sparse_hop_mirror.py)
+ * op by op; nothing in the product calls them.  Bitmaps are uint32 words, bit i = word i >> 5, bit i & 31.  All need the balanced
+ * SpMM ("spmm_variant" = 2).
+ *   gss_spmm_bwd1_sparse_ex: gss_spmm_bwd1_sparse with every optional argument.  posbits (nullable): bit c set <=> pos_col[c] >= 0.
+ *     nzbits_out (nullable, cleared over [0, n_rows) by the caller): bit r is set for every batch row and every row with a non-zero sum
+ *     -- per row, never per piece.  skip_zero_rows (needs nzbits_out): rows whose bit stays clear are not written.  live_rows
+ *     (nullable): a superset of the batch rows and the rows with an entry in a batch column; other rows are not walked (written as
+ *     zeros, or not at all under skip_zero_rows).
+ *   gss_spmm_bwd2_sparse_res: gx = t + A u; dp = c * gx (.) elu'(p) (+ res_b[pos_row[r]] where pos_row[r] >= 0); gx_out nullable.
+ *     nzbits (nullable): a clear bit c says rows c of u AND of t are zero (the neighbour is skipped, t's row is not read).  y_in
+ *     (nullable): [n_rows][d] partial sums of a first pass, added before the epilogue.  pos_row_limit > 0: t, pos_row and the residual
+ *     exist for output rows below it only; rows behind it get dp = c * (A u) (.) elu'(p).
+ *   gss_spmm_filtered: gss_spmm with row filters.  row_pos (plain product only): rows with row_pos[r] < 0 are not computed and not
+ *     written; row_bits: the same by bitmap; y_in as above; gather_bits (plain product only): columns whose bit is clear are skipped.
+ *   gss_mark_rows_and_neighbours: bits |= the listed rows and every column of their entries (negative list entries skipped).
+ *   gss_batch_bits: set != 0: bits |= ids (negative ids skipped); set == 0: the WORDS of the ids := 0 (the caller's contract: every set
+ *     bit of those words belongs to ids).
+ *   gss_bits_fill: bits [first, last) := 1, other bits untouched. */
+int gss_spmm_bwd1_sparse_ex(const gss_csr *at, int32_t d, const float *g_am_b, const float *g_ax_b, const int32_t *pos_col,
+                            const int32_t *pos_row, const float *x_in, const float *ax, float *u, float *t, const uint32_t *posbits,
+                            uint32_t *nzbits_out, int32_t skip_zero_rows, const uint32_t *live_rows, void *stream);
+int gss_spmm_bwd2_sparse_res(const gss_csr *at, int32_t d, const float *u, const float *t, const float *p, float c, const float *res_b,
+                             const int32_t *pos_row, float *dp, float *gx_out, const uint32_t *nzbits, const float *y_in,
+                             int32_t pos_row_limit, void *stream);
+int gss_spmm_filtered(const gss_csr *a, int32_t d, const float *x, float *y, const float *h, float *m, const int32_t *row_pos,
+                      const uint32_t *row_bits, const float *y_in, const uint32_t *gather_bits, void *stream);
+int gss_mark_rows_and_neighbours(const gss_csr *a, const int32_t *rows, int32_t b, uint32_t *bits, void *stream);
+int gss_batch_bits(const int32_t *ids, int32_t b, uint32_t *bits, int32_t set, void *stream);
+int gss_bits_fill(uint32_t *bits, int64_t first, int64_t last, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,6 @@
-"""-m gpu: every libgssgcn.so entry point against the numpy oracle / scipy on seeded inputs (called through
-the C ABI with ctypes, device buffers held in torch tensors)."""
+"""-m gpu: the per-op libgssgcn.so entry points of the training step against the numpy oracle / scipy on seeded inputs (called through
+the C ABI with ctypes, device buffers held in torch tensors).  The row-sparse SpMM modes (gss_spmm_bwd1_sparse[_ex],
+gss_spmm_bwd2_sparse_res, gss_spmm_filtered), their bitmap builders and gss_scatter_add_rows are in test_gpu_sparse_ops.py."""
 import ctypes as C
 
 import numpy as np
@@ -8,6 +9,7 @@ import scipy.sparse as sp
 
 from conftest import golden_batches, golden_csr, golden_params, load_golden
 from oracle import gss_oracle as O
+from sparse_hop_cases import random_graph
 
 pytestmark = pytest.mark.gpu
 
@@ -41,21 +43,6 @@ def rel_err(got, ref):
     got = np.asarray(got, np.float64)
     ref = np.asarray(ref, np.float64)
     return np.abs(got - ref).max() / max(np.abs(ref).max(), 1e-30)
-
-
-def random_graph(rng, n, avg_deg, hub_rows=(), hub_deg=0, empty_rows=()):
-    m = n * avg_deg
-    r = rng.randint(0, n, m)
-    c = rng.randint(0, n, m)
-    for h in hub_rows:
-        r = np.concatenate([r, np.full(hub_deg, h)])
-        c = np.concatenate([c, rng.choice(n, hub_deg, replace=False)])
-    keep = ~np.isin(r, list(empty_rows))
-    r, c = r[keep], c[keep]
-    a = sp.csr_matrix((rng.uniform(0.1, 1.0, len(r)), (r, c)), shape=(n, n))
-    a.sum_duplicates()
-    a.sort_indices()
-    return a
 
 
 # ---------------------------------------------------------------- K11
