@@ -9,7 +9,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgssgcn.so")
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 _lib = None
 
@@ -172,6 +172,8 @@ SIGNATURES = {
     "gss_paths_between": (C.c_int, [_I32, _I32, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gss_paths_between_fill": (C.c_int, [_I32, _I32, _P, _P, _P, _I32, _P, _P, _P, _I32, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P]),
     "gss_auc_rows": (C.c_int, [_I32, _I32, _P, _I64, _P, _P, _P, _P, _P, _P]),
+    "gss_rank_metrics_workspace_bytes": (_SZ, [_I32, _I32]),
+    "gss_rank_metrics_rows": (C.c_int, [_I32, _I32, _P, _I64, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "gss_profile_dist": (C.c_int, [_I32, _P, _I64, _I32, _P, _I32, _P, _I32, _P, _I64, _P]),
     "gss_embedding_scores": (C.c_int, [_I32, _I32, _P, _I64, _I32, _P, _I32, _P, _I32, _P, _I64, _P]),
     # for tests: the row-sparse SpMM modes and their bitmap builders (tests/test_gpu_sparse_ops.py)

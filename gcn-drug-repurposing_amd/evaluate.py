@@ -8,6 +8,9 @@ the graph and on a single-class label vector; here such indications are skipped 
 nodes are left out (consumer.indication_aucs' rules).  Scores of the CLI stay host fp64 (np.matmul per indication, predict.py's arithmetic; a
 gather from the profiles for diffusion); the ranking statistic of every indication runs in one device launch (csrc/auc.hip).  DESIGN.md
 section 9.4 has the contract decisions and the measurements.
+
+--metrics adds average precision and recall@K beside the AUC (csrc/rank_metrics.hip: all three in one launch in place of auc.hip's;
+DESIGN.md section 9.8).  Without it nothing here launches or prints anything it did not before.
 """
 from __future__ import annotations
 
@@ -16,6 +19,7 @@ import contextlib
 import csv
 import json
 import os
+import re
 import sys
 import time
 import warnings
@@ -29,6 +33,7 @@ from .predict import PredictError, _get, compare_setting, diffusion_profiles, di
 METHODS = ("diffusion", "node2vec", "gcn")
 PER_INDICATION_HEADER = ["indication", "name", "positives", "negatives", "auc"]
 MAX_COLS = 16384          # drugs per row: csrc/auc.hip sorts a row's keys in one workgroup's LDS
+MAX_CUTS = 8              # distinct K of recall@K in one launch (csrc/rank_metrics.hip)
 
 
 def parse_args(argv=None):
@@ -40,6 +45,9 @@ def parse_args(argv=None):
     p.add_argument("--seed", default=0, type=int, help="seed of the node2vec walks / skip-gram when the eval embedding file is generated")
     p.add_argument("--per-indication", default=None, type=str,
                    help="also write a TSV with one row per evaluated indication: id, name, positives, negatives, AUC")
+    p.add_argument("--metrics", default=None, type=str,
+                   help="comma-separated ranking statistics to report after the AUC line, one line each: ap (average precision), "
+                        f"recall@K (K >= 1, at most {MAX_CUTS} distinct K), auc; --per-indication gains one column per metric")
     return p.parse_args(argv)
 
 
@@ -88,6 +96,138 @@ def format_line(aucs):
     return f"median auc: {np.median(a)}, mean auc: {a.mean()}"
 
 
+# ---- metric names ------------------------------------------------------------------------------------------------------------------------
+
+_RECALL = re.compile(r"^recall@([0-9]+)$")
+
+
+def parse_metric(name):
+    """'auc' | 'ap' | 'recall@K' (K >= 1) -> (kind, K or None); anything else is refused by name"""
+    name = str(name)
+    if name in ("auc", "ap"):
+        return name, None
+    m = _RECALL.match(name)
+    if m and int(m.group(1)) >= 1:
+        return "recall", int(m.group(1))
+    raise PredictError(f"metric {name!r} is unknown; choose auc, ap or recall@K with an integer K >= 1")
+
+
+def parse_metrics(spec):
+    """a comma-separated string, or a sequence of names -> the list of names, in the order given: every name known, none given twice, at
+    most MAX_CUTS distinct K"""
+    names = [n.strip() for n in spec.split(",")] if isinstance(spec, str) else [str(n) for n in spec]
+    if isinstance(spec, str) and names == [""]:
+        raise PredictError("--metrics is empty; name auc, ap or recall@K")
+    seen = []
+    for n in names:
+        kind, k = parse_metric(n)
+        canon = n if kind != "recall" else f"recall@{k}"
+        if canon in seen:
+            raise PredictError(f"metric {canon!r} is given twice")
+        seen.append(canon)
+    if len(metric_cuts(seen)) > MAX_CUTS:
+        raise PredictError(f"{len(metric_cuts(seen))} distinct K of recall@K are above the limit of {MAX_CUTS} in one evaluation")
+    return seen
+
+
+def metric_cuts(metrics):
+    """the distinct K of the recall@K among metrics, in the order of first appearance"""
+    ks = []
+    for n in metrics:
+        kind, k = parse_metric(n)
+        if kind == "recall" and k not in ks:
+            ks.append(k)
+    return tuple(ks)
+
+
+def metric_arrays(metrics, ks, auc, ap, hits, n_pos):
+    """{name: fp64 [R]} in the order of metrics; recall@K = hits / P (the one division the kernel leaves to the caller), NaN where the
+    kernel wrote NaN"""
+    out = {}
+    hits = np.asarray(hits, np.float64).reshape(len(auc), len(ks))
+    for n in metrics:
+        kind, k = parse_metric(n)
+        if kind == "auc":
+            out[n] = np.asarray(auc, np.float64)
+        elif kind == "ap":
+            out[n] = np.asarray(ap, np.float64)
+        else:
+            with np.errstate(divide="ignore", invalid="ignore"):
+                out[n] = hits[:, ks.index(k)] / np.asarray(n_pos, np.float64)
+    return out
+
+
+def format_metric_line(name, values):
+    """the AUC line's f-string with the metric's name"""
+    a = np.asarray(values, dtype=np.float64)
+    return f"median {name}: {np.median(a)}, mean {name}: {a.mean()}"
+
+
+def _device_inputs(who, scores, pos_ptr, pos_col):
+    """the shape checks device_aucs and device_metrics share, on the host -> (scores, ptr, col, on_device)"""
+    import torch
+    on_device = isinstance(scores, torch.Tensor)
+    if on_device:
+        if scores.dim() != 2 or scores.dtype != torch.float64 or not scores.is_cuda:
+            raise PredictError(f"{who}: device scores must be an fp64 matrix [R, C] on the GPU")
+        s = scores.contiguous()
+    else:
+        s = np.ascontiguousarray(scores, dtype=np.float64)
+    ptr = np.ascontiguousarray(pos_ptr, dtype=np.int32)
+    col = np.ascontiguousarray(pos_col, dtype=np.int32)
+    if len(s.shape) != 2 or s.shape[1] < 1 or ptr.shape != (s.shape[0] + 1,) or ptr[0] != 0 or np.any(np.diff(ptr) < 0) or ptr[-1] != len(col):
+        raise PredictError(f"{who}: scores {s.shape} and the positives' row pointer ({len(ptr)} entries over {len(col)}) disagree")
+    if s.shape[1] > MAX_COLS:
+        raise PredictError(f"{s.shape[1]} drugs per indication is above the limit of {MAX_COLS} (one workgroup sorts a row in LDS)")
+    return s, ptr, col, on_device
+
+
+def check_cuts(who, ks):
+    """-> the cut-offs as a host int32 array; at most MAX_CUTS, every one >= 1"""
+    ks = [int(k) for k in ks]
+    if len(ks) > MAX_CUTS:
+        raise PredictError(f"{who}: {len(ks)} cut-offs are above the limit of {MAX_CUTS}")
+    if any(k < 1 for k in ks):
+        raise PredictError(f"{who}: cut-off {min(ks)} is below 1")
+    return np.asarray(ks, dtype=np.int32)
+
+
+def device_metrics(scores, pos_ptr, pos_col, ks, timings=None):
+    """device_aucs with average precision and the hits at every cut-off of ks beside the AUC, all in one launch (csrc/rank_metrics.hip):
+    -> host (auc [R], ap [R], hits [R, len(ks)], n_pos [R], n_neg [R]); NaN in auc, ap and hits where a row has one class.  The AUCs are
+    the bits device_aucs returns.  No CPU fallback; scores on the host or an fp64 device tensor; timings as device_aucs."""
+    import torch
+
+    from . import _lib
+    s, ptr, col, on_device = _device_inputs("device_metrics", scores, pos_ptr, pos_col)
+    h_ks = check_cuts("device_metrics", ks)
+    R, nk = s.shape[0], len(h_ks)
+    if R == 0:
+        return np.zeros(0), np.zeros(0), np.zeros((0, nk)), np.zeros(0, np.int32), np.zeros(0, np.int32)
+    t = {} if timings is None else timings
+    lib = _lib.load()
+    dev = torch.device("cuda")
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    d_s = s if on_device else torch.from_numpy(s).to(dev)
+    d_ptr = torch.from_numpy(ptr).to(dev)
+    d_col = torch.from_numpy(col if len(col) else np.zeros(1, np.int32)).to(dev)
+    auc = torch.empty(R, dtype=torch.float64, device=dev)
+    ap = torch.empty(R, dtype=torch.float64, device=dev)
+    hits = torch.empty(R, max(nk, 1), dtype=torch.float64, device=dev)
+    n_pos = torch.empty(R, dtype=torch.int32, device=dev)
+    n_neg = torch.empty(R, dtype=torch.int32, device=dev)
+    ws_bytes = lib.gss_rank_metrics_workspace_bytes(R, s.shape[1])
+    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    _lib.check(lib.gss_rank_metrics_rows(R, s.shape[1], _lib.ptr(d_s), s.shape[1], _lib.ptr(d_ptr), _lib.ptr(d_col), nk,
+                                         h_ks.ctypes.data if nk else None, _lib.ptr(auc), _lib.ptr(ap), _lib.ptr(hits), _lib.ptr(n_pos),
+                                         _lib.ptr(n_neg), _lib.ptr(ws), ws_bytes, _lib.current_stream()), "gss_rank_metrics_rows")   # synchronises
+    t["upload_s"], t["kernel_s"] = t1 - t0, time.perf_counter() - t1
+    return auc.cpu().numpy(), ap.cpu().numpy(), hits.cpu().numpy()[:, :nk], n_pos.cpu().numpy(), n_neg.cpu().numpy()
+
+
 def device_aucs(scores, pos_ptr, pos_col, timings=None):
     """one device launch: host scores fp64 [R, C] and the positives as a CSR -> host (auc [R], n_pos [R], n_neg [R]); NaN AUC where a
     row has one class.  No CPU fallback.  timings: upload_s / kernel_s (host clock around synchronised work).  Scores that are already a
@@ -95,19 +235,7 @@ def device_aucs(scores, pos_ptr, pos_col, timings=None):
     import torch
 
     from . import _lib
-    on_device = isinstance(scores, torch.Tensor)
-    if on_device:
-        if scores.dim() != 2 or scores.dtype != torch.float64 or not scores.is_cuda:
-            raise PredictError("device_aucs: device scores must be an fp64 matrix [R, C] on the GPU")
-        s = scores.contiguous()
-    else:
-        s = np.ascontiguousarray(scores, dtype=np.float64)
-    ptr = np.ascontiguousarray(pos_ptr, dtype=np.int32)
-    col = np.ascontiguousarray(pos_col, dtype=np.int32)
-    if len(s.shape) != 2 or s.shape[1] < 1 or ptr.shape != (s.shape[0] + 1,) or ptr[0] != 0 or np.any(np.diff(ptr) < 0) or ptr[-1] != len(col):
-        raise PredictError(f"device_aucs: scores {s.shape} and the positives' row pointer ({len(ptr)} entries over {len(col)}) disagree")
-    if s.shape[1] > MAX_COLS:
-        raise PredictError(f"{s.shape[1]} drugs per indication is above the limit of {MAX_COLS} (one workgroup sorts a row in LDS)")
+    s, ptr, col, on_device = _device_inputs("device_aucs", scores, pos_ptr, pos_col)
     R = s.shape[0]
     if R == 0:
         return np.zeros(0), np.zeros(0, np.int32), np.zeros(0, np.int32)
@@ -184,12 +312,15 @@ def label_rows(inds, drugs, positives):
 
 
 class Result:
-    def __init__(self, inds, auc, n_pos, n_neg, skipped, unknown, drugs=None, scores=None):
+    def __init__(self, inds, auc, n_pos, n_neg, skipped, unknown, drugs=None, scores=None, ap=None, metrics=None):
         self.indications, self.auc, self.n_pos, self.n_neg = inds, auc, n_pos, n_neg
+        self.ap = ap                               # average precision per indication when metrics were asked for, else None
+        self.metrics = dict(metrics or {})         # {name: fp64 [indications]} of the requested metrics, in the order asked
         self.drugs, self.scores = drugs, scores    # what was ranked: scores [indications][drugs] (a device tensor under diffusion.compare = a metric)
         self.skipped, self.unknown_pairs = skipped, unknown
         self.kept = [k for k in range(len(inds)) if n_pos[k] > 0 and n_neg[k] > 0]
         self.line = format_line(auc[self.kept])
+        self.metric_lines = [format_metric_line(name, v[self.kept]) for name, v in self.metrics.items()]   # over the AUC line's indications
 
 
 def skip_report(res, labels):
@@ -209,15 +340,19 @@ def skip_report(res, labels):
 def write_per_indication(path, g, res):
     with open(path, "w", newline="") as f:
         w = csv.writer(f, delimiter="\t", lineterminator="\n")
-        w.writerow(PER_INDICATION_HEADER)
+        w.writerow(PER_INDICATION_HEADER + list(res.metrics))
         for k in res.kept:
             i = res.indications[k]
-            w.writerow([i, display(g, i), int(res.n_pos[k]), int(res.n_neg[k]), repr(float(res.auc[k]))])
+            w.writerow([i, display(g, i), int(res.n_pos[k]), int(res.n_neg[k]), repr(float(res.auc[k]))]
+                       + [repr(float(v[k])) for v in res.metrics.values()])
 
 
-def run(s, seed=0, per_indication=None, auc_source=device_aucs, timings=None, err=None):
+def run(s, seed=0, per_indication=None, auc_source=device_aucs, timings=None, err=None, metrics=(), metric_source=device_metrics):
     """evaluate_auc.main on Settings s -> Result (per-indication AUCs, counts, skipped indications by reason, the stdout line).
-    auc_source(scores, pos_ptr, pos_col) -> (auc, n_pos, n_neg), NaN where a row has one class."""
+    auc_source(scores, pos_ptr, pos_col) -> (auc, n_pos, n_neg), NaN where a row has one class.  With metrics (names parse_metrics
+    accepts) the one call is metric_source(scores, pos_ptr, pos_col, ks) -> (auc, ap, hits [R, len(ks)], n_pos, n_neg) instead, and the
+    Result carries ap, the metrics' arrays and one line per metric."""
+    metrics = parse_metrics(metrics) if metrics else []
     err = sys.stderr if err is None else err
     t = {} if timings is None else timings
     t0 = time.perf_counter()
@@ -236,7 +371,14 @@ def run(s, seed=0, per_indication=None, auc_source=device_aucs, timings=None, er
     pos_ptr, pos_col, listed, unknown = label_rows(inds, drugs, positives)
     t2 = time.perf_counter()
     t["scores_s"] = t2 - t1
-    auc, n_pos, n_neg = auc_source(scores, pos_ptr, pos_col)
+    ap = values = None
+    if metrics:
+        ks = metric_cuts(metrics)
+        auc, ap, hits, n_pos, n_neg = metric_source(scores, pos_ptr, pos_col, ks)
+        ap = np.asarray(ap, np.float64)
+        values = metric_arrays(metrics, ks, auc, ap, hits, n_pos)
+    else:
+        auc, n_pos, n_neg = auc_source(scores, pos_ptr, pos_col)
     t["auc_s"] = time.perf_counter() - t2
     skipped = {"no_row": [], "no_known_drug": [], "all_positive": []}
     for k, i in enumerate(inds):
@@ -244,7 +386,7 @@ def run(s, seed=0, per_indication=None, auc_source=device_aucs, timings=None, er
             skipped["no_known_drug" if listed[i] else "no_row"].append(i)
         elif n_neg[k] == 0:
             skipped["all_positive"].append(i)
-    res = Result(inds, np.asarray(auc, np.float64), np.asarray(n_pos), np.asarray(n_neg), skipped, unknown, drugs, scores)
+    res = Result(inds, np.asarray(auc, np.float64), np.asarray(n_pos), np.asarray(n_neg), skipped, unknown, drugs, scores, ap, values)
     for line in skip_report(res, s.labels):
         print(line, file=err)
     if not res.kept:
@@ -261,7 +403,8 @@ class DeviceEvaluator:
     """The gcn / node2vec branch of run() for embeddings that are a device tensor: built once from the MSI tables (the directory of
     networks.protein_to_protein, as Settings.tables), networks.drug_to_indication and the node names of an embedding file (row k of the
     tensor is names[k]); score(emb) then runs gss_embedding_scores and gss_auc_rows on the device and brings back the AUCs and the counts
-    alone.  The lists are run()'s: drugs and indications in g.names order, the positives of label_rows.  DESIGN.md section 9.7.
+    alone (with metrics: gss_rank_metrics_rows in place of gss_auc_rows, and the average precisions and hits too).  The lists are run()'s:
+    drugs and indications in g.names order, the positives of label_rows.  DESIGN.md sections 9.7 and 9.8.
 
     Everything that can be wrong with the inputs is found on the host, before upload() touches the GPU."""
 
@@ -307,6 +450,10 @@ class DeviceEvaluator:
         self.d_auc = torch.empty(R, dtype=torch.float64, device=dev)
         self.d_pos = torch.empty(R, dtype=torch.int32, device=dev)
         self.d_neg = torch.empty(R, dtype=torch.int32, device=dev)
+        # score(metrics=...): average precision, hits at up to MAX_CUTS cut-offs and the sorted positives' parking space of csrc/rank_metrics.hip
+        self.d_ap = torch.empty(R, dtype=torch.float64, device=dev)
+        self.d_hits = torch.empty(R * MAX_CUTS, dtype=torch.float64, device=dev)
+        self.d_work = torch.empty(R * C, dtype=torch.int64, device=dev)
         self.device = self.d_rows.device      # with its index, as a tensor's device has it
 
     def check_tensor(self, emb, d=None):
@@ -327,13 +474,17 @@ class DeviceEvaluator:
             raise PredictError(f"DeviceEvaluator.score: emb has strides {tuple(emb.stride())}; its rows must be contiguous")
         return d
 
-    def score(self, emb, d=None, timings=None):
+    def score(self, emb, d=None, timings=None, metrics=()):
         """emb: device fp32 [N, >= d], row k = names[k] (d: the leading columns that count; the zero padding behind them changes no bit)
         -> Result.  Result.scores is the evaluator's own device buffer [indications][drugs], which the next score() overwrites: clone it to
-        keep it.  timings: scores_s / auc_s / host_s (host clock around synchronised calls)."""
+        keep it.  timings: scores_s / auc_s / host_s (host clock around synchronised calls).  metrics: names parse_metrics accepts; the
+        Result then carries them (run()'s rules), out of one launch of gss_rank_metrics_rows in place of gss_auc_rows."""
         import torch
 
         from . import _lib
+        metrics = parse_metrics(metrics) if metrics else []
+        ks = metric_cuts(metrics)
+        h_ks = check_cuts("DeviceEvaluator.score", ks)
         d = self.check_tensor(emb, d)
         if self.device is None:
             self.upload(emb.device)
@@ -347,31 +498,46 @@ class DeviceEvaluator:
             _lib.check(lib.gss_embedding_scores(self.n, d, _lib.ptr(emb), emb.stride(0), R, _lib.ptr(self.d_rows), C, _lib.ptr(self.d_cols),
                                                 int(self.normalize), _lib.ptr(self.d_scores), C, _lib.current_stream()), "gss_embedding_scores")
             t1 = time.perf_counter()
-            _lib.check(lib.gss_auc_rows(R, C, _lib.ptr(self.d_scores), C, _lib.ptr(self.d_ptr), _lib.ptr(self.d_col), _lib.ptr(self.d_auc),
-                                        _lib.ptr(self.d_pos), _lib.ptr(self.d_neg), _lib.current_stream()), "gss_auc_rows")   # both synchronise
+            if metrics:
+                _lib.check(lib.gss_rank_metrics_rows(R, C, _lib.ptr(self.d_scores), C, _lib.ptr(self.d_ptr), _lib.ptr(self.d_col), len(ks),
+                                                     h_ks.ctypes.data if len(ks) else None, _lib.ptr(self.d_auc), _lib.ptr(self.d_ap),
+                                                     _lib.ptr(self.d_hits), _lib.ptr(self.d_pos), _lib.ptr(self.d_neg), _lib.ptr(self.d_work),
+                                                     self.d_work.numel() * 8, _lib.current_stream()), "gss_rank_metrics_rows")
+            else:
+                _lib.check(lib.gss_auc_rows(R, C, _lib.ptr(self.d_scores), C, _lib.ptr(self.d_ptr), _lib.ptr(self.d_col), _lib.ptr(self.d_auc),
+                                            _lib.ptr(self.d_pos), _lib.ptr(self.d_neg), _lib.current_stream()), "gss_auc_rows")   # both synchronise
         t2 = time.perf_counter()
         auc, n_pos, n_neg = self.d_auc.cpu().numpy(), self.d_pos.cpu().numpy(), self.d_neg.cpu().numpy()
+        ap = values = None
+        if metrics:
+            ap = self.d_ap.cpu().numpy()
+            hits = self.d_hits[:R * len(ks)].cpu().numpy().reshape(R, len(ks))
+            values = metric_arrays(metrics, ks, auc, ap, hits, n_pos)
         skipped = {"no_row": [], "no_known_drug": [], "all_positive": []}
         for k, i in enumerate(self.indications):
             if n_pos[k] == 0:
                 skipped["no_known_drug" if self.listed[i] else "no_row"].append(i)
             elif n_neg[k] == 0:
                 skipped["all_positive"].append(i)
-        res = Result(self.indications, auc, n_pos, n_neg, skipped, self.unknown_pairs, self.drugs, self.d_scores)
+        res = Result(self.indications, auc, n_pos, n_neg, skipped, self.unknown_pairs, self.drugs, self.d_scores, ap, values)
         t["scores_s"], t["auc_s"], t["host_s"] = t1 - t0, t2 - t1, time.perf_counter() - t2
         return res
 
 
-def main(argv=None):
+def main(argv=None, auc_source=device_aucs, metric_source=device_metrics):
+    """the command line; the two sources are run()'s (the host tests put their mirrors there)"""
     args = parse_args(argv)
     try:
+        metrics = parse_metrics(args.metrics) if args.metrics is not None else []
         s = Settings(load_config(args.config))
     except (PredictError, OSError, json.JSONDecodeError) as e:
         print(f"evaluate_auc: {e}", file=sys.stderr)
         sys.exit(2)
     try:
-        res = run(s, args.seed, args.per_indication)
+        res = run(s, args.seed, args.per_indication, auc_source=auc_source, metrics=metrics, metric_source=metric_source)
     except (PredictError, OSError) as e:
         print(f"evaluate_auc: {e}", file=sys.stderr)
         sys.exit(2)
     print(res.line)
+    for line in res.metric_lines:
+        print(line)

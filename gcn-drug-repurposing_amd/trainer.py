@@ -8,7 +8,8 @@ Flags the reference parses but never uses (--dataset, --data-path, --report-hard
 are accepted and ignored.  New optional flags: --adj-file (weighted edgelist / .sif adjacency instead of the
 kNN graph), --out, --cache-layer1, --batch-file (replay recorded batches), --log-loss, --checkpoint / --resume, and --eval-config with
 --eval-every / --eval-log / --keep-best / --patience: the per-indication ROC-AUC of evaluate_auc.py's gcn method on the embeddings of an
-epoch, taken on the device where they lie (evaluate.DeviceEvaluator), as the run's model-selection signal.
+epoch, taken on the device where they lie (evaluate.DeviceEvaluator), as the run's model-selection signal; --eval-metric / --eval-stat
+select by the average precision or a recall@K instead, and by the mean instead of the median.
 """
 from __future__ import annotations
 
@@ -77,17 +78,30 @@ def build_parser():
                    help="an evaluate_auc.py config: score the embeddings of every eval epoch by per-indication ROC-AUC on the GPU "
                         "(its networks.protein_to_protein and networks.drug_to_indication; the node names are --emb-file's)")
     p.add_argument('--eval-every', type=int, default=1, help='epochs E, 2E, ... and the last one are eval epochs (default 1)')
-    p.add_argument('--eval-log', default=None, help='TSV with one row per eval epoch: epoch, median_auc, mean_auc, indications, seconds')
+    p.add_argument('--eval-log', default=None, help='TSV with one row per eval epoch: epoch, median_auc, mean_auc, indications, seconds '
+                   '(+ median_<metric>, mean_<metric> with an --eval-metric other than auc)')
     p.add_argument('--keep-best', default=None,
-                   help="write the embeddings of every eval epoch whose median AUC is strictly above all earlier ones to this file "
+                   help="write the embeddings of every eval epoch whose median AUC (or --eval-stat of --eval-metric) is strictly above all earlier ones to this file "
                         "(graph_embs.txt format; a tie keeps the earlier file)")
     p.add_argument('--patience', type=int, default=None,
-                   help='stop after this many (>= 1) consecutive eval epochs without a strict improvement of the median AUC')
+                   help='stop after this many (>= 1) consecutive eval epochs without a strict improvement of the median AUC (or --eval-stat of --eval-metric)')
+    p.add_argument('--eval-metric', default=None,
+                   help="the metric --keep-best and --patience follow: auc (default), ap (average precision) or recall@K (K >= 1); "
+                        "a metric other than auc gets an eval line and two --eval-log columns of its own")
+    p.add_argument('--eval-stat', default=None, choices=EVAL_STATS,
+                   help="the statistic of --eval-metric over the indications that --keep-best and --patience follow: median (default) "
+                        "or mean (the median of a recall over indications that list one or two drugs is nearly always 0 or 1)")
     return p
 
 
-EVAL_FLAGS = ("eval_config", "eval_every", "eval_log", "keep_best", "patience")
+EVAL_STATS = ("median", "mean")
+EVAL_FLAGS = ("eval_config", "eval_every", "eval_log", "keep_best", "patience", "eval_metric", "eval_stat")
 EVAL_LOG_HEADER = ["epoch", "median_auc", "mean_auc", "indications", "seconds"]
+
+
+def eval_log_header(metric):
+    """the --eval-log columns: a metric other than auc adds its median and mean"""
+    return EVAL_LOG_HEADER + ([] if metric == "auc" else [f"median_{metric}", f"mean_{metric}"])
 
 
 def parse_args(argv=None):
@@ -99,9 +113,19 @@ def parse_args(argv=None):
         p.error(f"--patience {args.patience} must be >= 1")
     if args.eval_config is None:
         for flag, given in (("--keep-best", args.keep_best is not None), ("--eval-log", args.eval_log is not None),
-                            ("--patience", args.patience is not None)):
+                            ("--patience", args.patience is not None), ("--eval-metric", args.eval_metric is not None),
+                            ("--eval-stat", args.eval_stat is not None)):
             if given:
                 p.error(f"{flag} needs --eval-config (there is nothing to evaluate without it)")
+    if args.eval_metric is not None:
+        from .evaluate import parse_metrics
+        from .predict import PredictError
+        try:
+            args.eval_metric = parse_metrics([args.eval_metric])[0]
+        except PredictError as e:
+            p.error(f"--eval-metric: {e}")
+    args.eval_metric = "auc" if args.eval_metric is None else args.eval_metric
+    args.eval_stat = "median" if args.eval_stat is None else args.eval_stat
     return args
 
 
@@ -118,6 +142,13 @@ def build_evaluator(args):
             raise PredictError("--eval-config needs --emb-file (its node names say which row is which drug and indication)")
         cfg = load_config(args.eval_config)
         ppi, labels = _get(cfg, "networks", "protein_to_protein"), _get(cfg, "networks", "drug_to_indication")
+        if args.eval_log and os.path.exists(args.eval_log) and os.path.getsize(args.eval_log) > 0:
+            with open(args.eval_log) as f:
+                first = f.readline().rstrip("\n")
+            want = "\t".join(eval_log_header(args.eval_metric))
+            if first != want:
+                raise PredictError(f"--eval-log {args.eval_log} exists with the header {first!r}; this run (--eval-metric {args.eval_metric}) "
+                                   f"writes {want!r} and will not append to it")
         names, X = embio.read_embs(args.emb_file)
         return DeviceEvaluator(ppi, labels, names, normalize=True, source=args.emb_file, upload=False), (names, X)
     except (PredictError, OSError, ValueError) as e:
@@ -305,7 +336,10 @@ def main(argv=None):
     beta_score = args.beta
     itr = 0
     step_no = 0
-    best_median, best_epoch, stale = -np.inf, 0, 0     # --eval-config: the best median AUC so far, its epoch, eval epochs since
+    # --eval-config: the best value so far of the selected statistic (--eval-stat) of the selected metric (--eval-metric; the median AUC
+    # by default, hence the name), its epoch, eval epochs since
+    best_median, best_epoch, stale = -np.inf, 0, 0
+    selection = (args.eval_metric, args.eval_stat)
     # what a resumed run must share with the run that wrote the checkpoint to be its continuation
     hyper = {"lr": args.lr, "alpha": args.alpha, "layer_decay": args.layer_decay, "batch_size": float(bsz),
              "seed": float(args.seed or 0), "init_weights": args.init_weights}
@@ -324,6 +358,10 @@ def main(argv=None):
         engine.load_state_dict(z)
         itr, step_no, beta_score = int(z["epoch"]), int(z["step"]), float(z["beta"])
         if evaluator is not None and "eval_best_median" in z.files:
+            saved = (str(z["eval_metric"]), str(z["eval_stat"])) if "eval_metric" in z.files else ("auc", "median")
+            if saved != selection:
+                raise Exception(f"{args.resume} was written with --eval-metric {saved[0]} --eval-stat {saved[1]}; its best value so far "
+                                f"cannot be continued with --eval-metric {selection[0]} --eval-stat {selection[1]}")
             best_median, best_epoch, stale = float(z["eval_best_median"]), int(z["eval_best_epoch"]), int(z["eval_stale"])
         torch.set_rng_state(torch.from_numpy(z["torch_rng"].copy()))     # the sampler continues its permutation stream
         engine.forward()                                     # the embeddings a finished run writes come from a forward
@@ -370,17 +408,23 @@ def main(argv=None):
             torch.cuda.synchronize()
             t_eval = time.time()
             emb_now = full_embeddings()
-            res = evaluator.score(emb_now, d)
+            res = evaluator.score(emb_now, d, metrics=() if args.eval_metric == "auc" else (args.eval_metric,))
             score_s = time.time() - t_eval
             median, mean = float(np.median(res.auc[res.kept])), float(res.auc[res.kept].mean())
             eval_line = f"eval {itr} {res.line}"
+            selected, extra_cols = {"median": median, "mean": mean}[args.eval_stat], []
+            if args.eval_metric != "auc":
+                v = res.metrics[args.eval_metric][res.kept]
+                m_median, m_mean = float(np.median(v)), float(v.mean())
+                eval_line += f"\neval {itr} {res.metric_lines[0]}"
+                selected, extra_cols = {"median": m_median, "mean": m_mean}[args.eval_stat], [repr(m_median), repr(m_mean)]
             if not evaluator.reported:
                 from .evaluate import skip_report
                 for line in skip_report(res, evaluator.labels):
                     print(line.replace("evaluate_auc:", "train: eval:", 1), file=sys.stderr)
                 evaluator.reported = True
-            if median > best_median:
-                best_median, best_epoch, stale = median, itr, 0
+            if selected > best_median:
+                best_median, best_epoch, stale = selected, itr, 0
                 if args.keep_best:
                     embio.write_graph_embs(args.keep_best, emb_now.cpu().numpy()[:, :d])
             else:
@@ -389,8 +433,8 @@ def main(argv=None):
                 fresh = not os.path.exists(args.eval_log) or os.path.getsize(args.eval_log) == 0
                 with open(args.eval_log, "a") as f:
                     if fresh:
-                        f.write("\t".join(EVAL_LOG_HEADER) + "\n")
-                    f.write("\t".join([str(itr), repr(median), repr(mean), str(len(res.kept)), repr(score_s)]) + "\n")
+                        f.write("\t".join(eval_log_header(args.eval_metric)) + "\n")
+                    f.write("\t".join([str(itr), repr(median), repr(mean), str(len(res.kept)), repr(score_s)] + extra_cols) + "\n")
             stop = args.patience is not None and stale >= args.patience and itr < args.epochs
             eval_s = time.time() - t_eval              # kept out of the epoch time of the `iter` line
         if args.checkpoint and rank == 0:          # weights and optimizer state are replicated: rank 0's copy is the job's
@@ -398,7 +442,8 @@ def main(argv=None):
             tmp = args.checkpoint + ".tmp.npz"
             np.savez(tmp, epoch=itr, beta=float(beta_score), n=n, d=d_pad, num_layers=args.num_layers,
                      torch_rng=torch.get_rng_state().numpy(), **{"hp_" + k: v for k, v in hyper.items()}, **sd,
-                     **({} if evaluator is None else {"eval_best_median": best_median, "eval_best_epoch": best_epoch, "eval_stale": stale}))
+                     **({} if evaluator is None else {"eval_best_median": best_median, "eval_best_epoch": best_epoch, "eval_stale": stale}),
+                     **({} if evaluator is None or selection == ("auc", "median") else {"eval_metric": selection[0], "eval_stat": selection[1]}))
             os.replace(tmp, args.checkpoint)
         if args.log_loss:
             print(f"iter {itr} loss {float(engine.loss.item()):.8f} time {time.time() - start_time - eval_s:.4f}s")

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define GSS_ABI_VERSION 15  /* 15: entry points for tests of the row-sparse SpMM modes -- gss_spmm_bwd1_sparse_ex, gss_spmm_bwd2_sparse_res, gss_spmm_filtered, gss_mark_rows_and_neighbours, gss_batch_bits, gss_bits_fill; 14:indication x drug scores from the embedding tensor -- gss_embedding_scores; 13: pairwise distances between diffusion profiles -- gss_profile_dist; 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
+#define GSS_ABI_VERSION 16  /* 16: ROC-AUC, average precision and hits@k per row in one launch -- gss_rank_metrics_rows, gss_rank_metrics_workspace_bytes; 15: entry points for tests of the row-sparse SpMM modes -- gss_spmm_bwd1_sparse_ex, gss_spmm_bwd2_sparse_res, gss_spmm_filtered, gss_mark_rows_and_neighbours, gss_batch_bits, gss_bits_fill; 14:indication x drug scores from the embedding tensor -- gss_embedding_scores; 13: pairwise distances between diffusion profiles -- gss_profile_dist; 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
 
 #define GSS_OK 0
 #define GSS_EINVAL (-22)   /* bad argument (shape, null pointer, unsupported d) */
@@ -448,6 +448,28 @@ int gss_paths_between_fill(int32_t n, int32_t ns, const int32_t *sources, const 
  * its row, and a pos_ptr that is not a row pointer (0 first, non-decreasing, at most C per row); the outputs are then unspecified. */
 int gss_auc_rows(int32_t R, int32_t C, const double *scores, int64_t ld, const int32_t *pos_ptr, const int32_t *pos_col, double *auc,
                  int32_t *n_pos, int32_t *n_neg, void *stream);
+
+/* ---- ROC-AUC, average precision and hits@k per query row: the three ranking statistics of drug-indication prediction
+ * gss_rank_metrics_rows: scores, pos_ptr and pos_col as gss_auc_rows takes them; h_ks: nk cut-offs on the HOST, 0 <= nk <= 8, every
+ * k >= 1 -> device auc [R], ap [R], hits [R][nk] fp64, n_pos [R], n_neg [R] int32.  A row has P positives and N negatives; scores compare
+ * as in gss_auc_rows (-0.0 and +0.0 are one value) and a tie group is a maximal set of equal scores.
+ *   auc   the bits gss_auc_rows writes for the row (the same integer counts, one division).
+ *   ap    sklearn.metrics.average_precision_score: (1 / P) sum over the tie groups g that hold a positive, in descending score, of
+ *         pos_g TP_g / (TP_g + FP_g), TP_g / FP_g the positives / negatives down to and including g.  Each term is an exact integer
+ *         product and one division; the terms are added in an order fixed by the sorted scores.
+ *   hits  the expected number of positives among the top k' = min(k, C) when ties are broken uniformly at random: with the group that
+ *         holds rank k' having `above` items strictly before it (A of them positive), g items and pos_g positives, slots = k' - above,
+ *         hits = A + pos_g if slots == g, else fl(A + fl((pos_g slots) / g)).  recall@k = hits / P is the caller's division.
+ * A row with P = 0 or N = 0 gets NaN in auc, ap and every hits word, and its counts.  Every output depends only on the row's multiset
+ * of (score, label) pairs: permuting the columns or a row's pos_col entries changes no bit, and no result goes through an atomic.
+ * One workgroup per row sorts the positives' keys in LDS, parks them in `workspace` (device, 8-byte aligned, at least
+ * gss_rank_metrics_workspace_bytes(R, C) = 8 R C bytes; nothing is allocated inside) and sorts the negatives' keys in the same LDS, so
+ * 1 <= C <= 16384 with any P.  Synchronises the stream and refuses what gss_auc_rows refuses, in its words behind "rank_metrics_rows:",
+ * and also nk outside 0..8, a cut-off below 1 and a workspace that is too small; the outputs are then unspecified. */
+size_t gss_rank_metrics_workspace_bytes(int32_t R, int32_t C);
+int gss_rank_metrics_rows(int32_t R, int32_t C, const double *scores, int64_t ld, const int32_t *pos_ptr, const int32_t *pos_col, int32_t nk,
+                          const int32_t *h_ks, double *auc, double *ap, double *hits, int32_t *n_pos, int32_t *n_neg, void *workspace,
+                          size_t workspace_bytes, void *stream);
 
 /* ---- pairwise distances between diffusion profiles (multiscale/README.md, overview (c): "by comparing the diffusion profiles of a drug and
  * a disease ...")
