@@ -9,7 +9,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgssgcn.so")
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 _lib = None
 
@@ -151,6 +151,7 @@ SIGNATURES = {
     "gss_ppr_device_bytes": (_SZ, [_P]),
     "gss_ppr_check_guards": (C.c_int, [_P]),
     "gss_ppr_run": (C.c_int, [_P, _D, _D, _I32, _P, _P, _P]),
+    "gss_ppr_set_knockout": (C.c_int, [_P, _P, _I64, _P, _P, _P, _I64, _P, _P]),
     "gss_ppr_spmm": (C.c_int, [_P, _P, _P, _P]),
     "gss_walk_prefix": (C.c_int, [_I32, _P, _P, _P, _P]),
     "gss_node2vec_walks": (C.c_int, [_I32, _P, _P, _P, _P, _I64, _P, _I32, _D, _D, C.c_uint64, _P, _P, _P]),
@@ -175,6 +176,8 @@ SIGNATURES = {
     "gss_rank_metrics_workspace_bytes": (_SZ, [_I32, _I32]),
     "gss_rank_metrics_rows": (C.c_int, [_I32, _I32, _P, _I64, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "gss_profile_dist": (C.c_int, [_I32, _P, _I64, _I32, _P, _I32, _P, _I32, _P, _I64, _P]),
+    "gss_profile_dist_pairs_workspace_bytes": (_SZ, [_I32, _I32]),
+    "gss_profile_dist_pairs": (C.c_int, [_I32, _P, _I64, _I32, _P, _P, _I32, _P, _P, _SZ, _P]),
     "gss_embedding_scores": (C.c_int, [_I32, _I32, _P, _I64, _I32, _P, _I32, _P, _I32, _P, _I64, _P]),
     # for tests: the row-sparse SpMM modes and their bitmap builders (tests/test_gpu_sparse_ops.py)
     "gss_spmm_bwd1_sparse_ex": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _P]),

@@ -42,6 +42,13 @@ struct gss_ppr {
   double *err_corr;   // [kpad]: correction of the column errors for the override entries (x was scaled in place during the product)
   int32_t n_segblocks;
   bool fused;
+  // per-column knock-outs (gss_ppr_set_knockout; the caller owns the lists): nothing below is read while has_ko is false
+  bool has_ko;
+  const int32_t *dead;                                     // [k]: row forced to 0 after the product (-1 = none)
+  int64_t n_grp, n_corr;
+  const int32_t *corr_ptr, *corr_grp_row, *corr_grp_col;   // groups sorted by (column, row); entries [corr_ptr[g], corr_ptr[g + 1])
+  const int32_t *corr_src;
+  const double *corr_val;
 };
 
 namespace gss {
@@ -399,6 +406,59 @@ __global__ __launch_bounds__(256) void ppr_ovr_fix_kernel(double *__restrict__ x
   if (lane == 0) err_corr[c] = corr;
 }
 
+// fused update, knock-out columns, after ppr_ovr_restore_kernel (x_cur unscaled again) and ppr_ovr_fix_kernel (err_corr[c] written where
+// the handle has overrides).  One wave per column; the column's groups are the run of corr_grp_col equal to c (sorted: two binary searches).
+//   correction  group (j, c): y[j][c] += sum_e corr_val[e] x_cur[corr_src[e]][c], entries in list order, one lane per group; the epilogue
+//               has already turned y into x_new = alpha (y + ...), so the sum enters as alpha * sum;
+//   dead entry  the shared matrix still delivers i -> dead[c]: x_new[dead[c]][c] = 0.
+// The column error takes |new - x_cur| - |what the epilogue wrote - x_cur| per touched entry: lanes stride the groups, shuffle tree, the
+// dead entry last.  A column without groups and with dead[c] = -1 is left alone (err_corr[c] too where ppr_ovr_fix_kernel writes it, else
+// it is set to 0, the value gss_ppr_create gave it); a converged column too (its copy
+// already carries the final values, the dead entry's 0 among them).
+__global__ __launch_bounds__(256) void ppr_knockout_kernel(double *__restrict__ x_nxt, const double *__restrict__ x_cur,
+                                                           const int32_t *__restrict__ dead, int n_grp, const int32_t *__restrict__ corr_ptr,
+                                                           const int32_t *__restrict__ grp_row, const int32_t *__restrict__ grp_col,
+                                                           const int32_t *__restrict__ corr_src, const double *__restrict__ corr_val,
+                                                           const int32_t *__restrict__ done, int k, int kpad, double alpha, int has_ovr,
+                                                           double *__restrict__ err_corr) {
+  const int lane = threadIdx.x & 63;
+  const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (c >= k || done[c] != 0) return;
+  auto lower = [&](int col) {   // first group whose column is >= col
+    int lo = 0, hi = n_grp;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (grp_col[mid] < col) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+  };
+  const int g0 = lower(c), g1 = lower(c + 1);
+  const int dr = dead[c];
+  if (g0 == g1 && dr < 0) {   // without overrides nobody else writes err_corr[c]: lists set anew on the handle may have left this column
+    if (!has_ovr && lane == 0) err_corr[c] = 0.0;
+    return;
+  }
+  double corr = 0.0;
+  for (int gi = g0 + lane; gi < g1; gi += 64) {
+    double sum = 0.0;
+    for (int e = corr_ptr[gi]; e < corr_ptr[gi + 1]; ++e) sum += corr_val[e] * x_cur[(size_t)corr_src[e] * kpad + c];
+    const size_t i = (size_t)grp_row[gi] * kpad + c;
+    const double xo = x_cur[i], xn = x_nxt[i], fixed = xn + alpha * sum;
+    x_nxt[i] = fixed;
+    corr += fabs(fixed - xo) - fabs(xn - xo);
+  }
+  corr = wave_sum_d(corr);
+  if (lane == 0) {
+    if (dr >= 0) {
+      const size_t i = (size_t)dr * kpad + c;
+      const double xo = x_cur[i], xn = x_nxt[i];
+      x_nxt[i] = 0.0;
+      corr += fabs(0.0 - xo) - fabs(xn - xo);
+    }
+    err_corr[c] = (has_ovr ? err_corr[c] : 0.0) + corr;
+  }
+}
+
 __global__ void ppr_finish_fused_kernel(const double *__restrict__ part_e, int n_blocks, const double *__restrict__ err_corr, int k, int kpad,
                                         double thr, int it, int32_t *__restrict__ done, int32_t *__restrict__ iters, int32_t *__restrict__ n_active) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -469,6 +529,10 @@ int gss_ppr_create(gss_ppr **out, const gss_ppr_desc *desc) {
   p->d = D;
   p->csr = nullptr;
   p->slab = nullptr;
+  p->has_ko = false;
+  p->dead = p->corr_ptr = p->corr_grp_row = p->corr_grp_col = p->corr_src = nullptr;
+  p->corr_val = nullptr;
+  p->n_grp = p->n_corr = 0;
   // structure-only CSR handle for the segment schedule (its value pointer is never read as float)
   if (int rc = gss_csr_create(&p->csr, D.n, D.n, D.nnz, D.h_rowptr, D.t_rowptr, D.t_col, reinterpret_cast<const float *>(D.t_val))) {
     delete p;
@@ -571,6 +635,60 @@ int gss_ppr_check_guards(gss_ppr *p) {
   return GSS_OK;
 }
 
+int gss_ppr_set_knockout(gss_ppr *p, const int32_t *dead, int64_t n_grp, const int32_t *corr_ptr, const int32_t *corr_grp_row,
+                         const int32_t *corr_grp_col, int64_t n_corr, const int32_t *corr_src, const double *corr_val) {
+  GSS_REQUIRE(p, "ppr_set_knockout: null handle");
+  GSS_REQUIRE(p->fused, "ppr_set_knockout: knock-outs need the fused update (ppr_fused = 1 and gss_ppr_desc.ovr_ptr); this handle has the "
+                        "separate update pass");
+  GSS_REQUIRE(dead, "ppr_set_knockout: dead is null");
+  GSS_REQUIRE(n_grp >= 0 && n_grp < (1ll << 31) && n_corr >= 0 && n_corr < (1ll << 31), "ppr_set_knockout: n_grp=%lld, n_corr=%lld must be in [0, 2^31)",
+              (long long)n_grp, (long long)n_corr);
+  GSS_REQUIRE(n_grp == 0 || (corr_ptr && corr_grp_row && corr_grp_col), "ppr_set_knockout: correction group lists missing");
+  GSS_REQUIRE(n_corr == 0 || (corr_src && corr_val), "ppr_set_knockout: correction entry lists missing");
+  GSS_REQUIRE(n_grp > 0 || n_corr == 0, "ppr_set_knockout: n_corr=%lld entries without a group", (long long)n_corr);
+  const gss_ppr_desc &D = p->d;
+  GSS_HIP(hipDeviceSynchronize());
+  std::vector<int32_t> h_dead(D.k), h_start(D.k), h_ptr(n_grp ? n_grp + 1 : 0), h_row(n_grp), h_col(n_grp), h_src(n_corr);
+  GSS_HIP(hipMemcpy(h_dead.data(), dead, (size_t)D.k * 4, hipMemcpyDeviceToHost));
+  GSS_HIP(hipMemcpy(h_start.data(), D.start, (size_t)D.k * 4, hipMemcpyDeviceToHost));
+  if (n_grp) {
+    GSS_HIP(hipMemcpy(h_ptr.data(), corr_ptr, (size_t)(n_grp + 1) * 4, hipMemcpyDeviceToHost));
+    GSS_HIP(hipMemcpy(h_row.data(), corr_grp_row, (size_t)n_grp * 4, hipMemcpyDeviceToHost));
+    GSS_HIP(hipMemcpy(h_col.data(), corr_grp_col, (size_t)n_grp * 4, hipMemcpyDeviceToHost));
+  }
+  if (n_corr) GSS_HIP(hipMemcpy(h_src.data(), corr_src, (size_t)n_corr * 4, hipMemcpyDeviceToHost));
+  for (int c = 0; c < D.k; ++c) {
+    GSS_REQUIRE(h_dead[c] >= -1 && h_dead[c] < D.n, "ppr_set_knockout: dead[%d] = %d is outside [-1, n=%d)", c, h_dead[c], D.n);
+    GSS_REQUIRE(h_dead[c] != h_start[c], "ppr_set_knockout: dead[%d] = %d is the column's own start node", c, h_dead[c]);
+  }
+  if (n_grp) {
+    GSS_REQUIRE(h_ptr[0] == 0 && h_ptr[n_grp] == n_corr, "ppr_set_knockout: corr_ptr runs from %d to %d, not from 0 to n_corr=%lld", h_ptr[0],
+                h_ptr[n_grp], (long long)n_corr);
+    for (int64_t g = 0; g < n_grp; ++g) {
+      GSS_REQUIRE(h_ptr[g] <= h_ptr[g + 1], "ppr_set_knockout: corr_ptr decreases at group %lld", (long long)g);
+      GSS_REQUIRE(h_col[g] >= 0 && h_col[g] < D.k, "ppr_set_knockout: corr_grp_col[%lld] = %d is outside [0, k=%d)", (long long)g, h_col[g], D.k);
+      GSS_REQUIRE(h_row[g] >= 0 && h_row[g] < D.n, "ppr_set_knockout: corr_grp_row[%lld] = %d is outside [0, n=%d)", (long long)g, h_row[g], D.n);
+      GSS_REQUIRE(g == 0 || h_col[g - 1] < h_col[g] || (h_col[g - 1] == h_col[g] && h_row[g - 1] < h_row[g]),
+                  "ppr_set_knockout: correction group %lld is not above its predecessor in (column, row) order", (long long)g);
+      GSS_REQUIRE(h_row[g] != h_start[h_col[g]], "ppr_set_knockout: correction group %lld sits on the start node of its column %d (keep_* carries "
+                                                 "the start's in-edges)", (long long)g, h_col[g]);
+      GSS_REQUIRE(h_row[g] != h_dead[h_col[g]], "ppr_set_knockout: correction group %lld sits on the dead row of its column %d", (long long)g, h_col[g]);
+    }
+    for (int64_t e = 0; e < n_corr; ++e)
+      GSS_REQUIRE(h_src[e] >= 0 && h_src[e] < D.n, "ppr_set_knockout: corr_src[%lld] = %d is outside [0, n=%d)", (long long)e, h_src[e], D.n);
+  }
+  p->dead = dead;
+  p->n_grp = n_grp;
+  p->n_corr = n_corr;
+  p->corr_ptr = corr_ptr;
+  p->corr_grp_row = corr_grp_row;
+  p->corr_grp_col = corr_grp_col;
+  p->corr_src = corr_src;
+  p->corr_val = corr_val;
+  p->has_ko = true;
+  return GSS_OK;
+}
+
 int gss_ppr_spmm(gss_ppr *p, const double *x, double *y, void *stream) {
   GSS_REQUIRE(p && x && y, "ppr_spmm: null argument");
   return ppr_spmm_launch(p, x, y, as_stream(stream));
@@ -626,6 +744,11 @@ int gss_ppr_run(gss_ppr *p, double alpha, double tol, int32_t max_iter, double *
         hipLaunchKernelGGL(ppr_ovr_fix_kernel, dim3(ceil_div(D.k, 4)), dim3(256), 0, st, nxt, D.ovr_ptr, D.ovr_row, D.ovr_ratio, p->stash_o, p->done, D.k,
                            D.kpad, p->err_corr);
         GSS_LAUNCH_CHECK("ppr_ovr_fix_kernel");
+      }
+      if (p->has_ko) {
+        hipLaunchKernelGGL(ppr_knockout_kernel, dim3(ceil_div(D.k, 4)), dim3(256), 0, st, nxt, cur, p->dead, (int)p->n_grp, p->corr_ptr, p->corr_grp_row,
+                           p->corr_grp_col, p->corr_src, p->corr_val, p->done, D.k, D.kpad, alpha, D.n_ovr > 0 ? 1 : 0, p->err_corr);
+        GSS_LAUNCH_CHECK("ppr_knockout_kernel");
       }
       hipLaunchKernelGGL(ppr_finish_fused_kernel, dim3(ceil_div(D.k, 64)), dim3(64), 0, st, p->part_e, p->n_segblocks, p->err_corr, D.k, D.kpad, thr, it,
                          p->done, p->iters, p->n_active);

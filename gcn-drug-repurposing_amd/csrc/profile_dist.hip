@@ -229,6 +229,112 @@ __global__ __launch_bounds__(kPdThreads) void pd_diff_kernel(int32_t n, const do
   }
 }
 
+// ---- listed pairs (gss_profile_dist_pairs) ----------------------------------------------------------------------------------------------------
+// T distances, not T x T: a bandwidth kernel.  A list may name a column many times (a screen's baselines are in three of a gene's four pairs);
+// those rereads are of the row block's own 32 rows, which stay in cache while the wave sweeps the list, so nothing is staged in LDS.
+// A wave owns the kPpRows rows of row block rb and sweeps the pair list, lane = pair: at one row the 64 lanes read 64 pairs' entries, which
+// sit next to each other in that row of x when the listed columns do (x is row-major: down a column nothing coalesces, across the list it
+// does).  A pair whose two columns are neighbours in an aligned 16 bytes takes both with one load.  Every lane adds its block's rows in order
+// and writes one partial per sum to part[sum][rb][t]; pp_finish_kernel adds the blocks 0, 1, ... in order.  The order of every sum therefore
+// depends on n alone: a pair's bits do not depend on its place in the list or on the list's length, and the terms do not depend on the
+// order of a and b.
+constexpr int kPpRows = 32;       // rows per row block
+constexpr int kPpWaves = 4;       // row blocks per workgroup
+constexpr int kPpStatusBytes = 256;
+enum { kPpSums = 5, kPpDot = 6 };   // modes beside the three difference metrics: column sums (for the means), centred dot and norms
+
+template <int kMode>
+__global__ __launch_bounds__(64 * kPpWaves) void pp_partial_kernel(int32_t n, const double *__restrict__ x, int64_t ld, int32_t T,
+                                                                    const int32_t *__restrict__ col_a, const int32_t *__restrict__ col_b,
+                                                                    const double *__restrict__ mean, int32_t n_blk, int vec_ok,
+                                                                    double *__restrict__ part) {
+  const int lane = threadIdx.x & 63;
+  const int32_t rb = blockIdx.x * kPpWaves + (threadIdx.x >> 6);
+  if (rb >= n_blk) return;   // wave-uniform; the kernel has no barrier
+  const int32_t r0 = rb * kPpRows, rows = min(kPpRows, n - r0);
+  const size_t plane = (size_t)n_blk * T;
+  for (int32_t t = lane; t < T; t += 64) {
+    const int32_t ca = col_a[t], cb = col_b[t], lo = min(ca, cb);
+    const bool both = vec_ok && (lo & 1) == 0 && (ca - cb == 1 || cb - ca == 1);   // the two columns share an aligned 16 bytes of every row
+    const bool a_first = ca < cb;
+    const double *pa = x + (int64_t)r0 * ld + ca, *pb = x + (int64_t)r0 * ld + cb, *pl = x + (int64_t)r0 * ld + lo;
+    double ma = 0.0, mb = 0.0;
+    if (kMode == kPpDot && mean) {
+      ma = mean[t];
+      mb = mean[T + t];
+    }
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    auto add = [&](double a, double b) {
+      if (kMode == kPpSums) {
+        s0 += a;
+        s1 += b;
+      } else if (kMode == kPpDot) {
+        const double da = a - ma, db = b - mb;
+        s0 += da * db;
+        s1 += da * da;
+        s2 += db * db;
+      } else {
+        s0 += pd_term<kMode>(a, b);
+      }
+    };
+    auto sweep = [&](int cnt) {
+      if (both) {
+#pragma unroll 8
+        for (int r = 0; r < cnt; ++r) {
+          const double2 v = *reinterpret_cast<const double2 *>(pl + (int64_t)r * ld);
+          add(a_first ? v.x : v.y, a_first ? v.y : v.x);
+        }
+      } else {
+#pragma unroll 8
+        for (int r = 0; r < cnt; ++r) add(pa[(int64_t)r * ld], pb[(int64_t)r * ld]);
+      }
+    };
+    if (rows == kPpRows) sweep(kPpRows);
+    else sweep(rows);
+    const size_t at = (size_t)rb * T + t;
+    part[at] = s0;
+    if (kMode == kPpSums || kMode == kPpDot) part[plane + at] = s1;
+    if (kMode == kPpDot) part[2 * plane + at] = s2;
+  }
+}
+
+// one thread per pair: the blocks' partials in block order, then the metric's last step (kPpSums: the two means into mean[t], mean[T + t])
+template <int kMode>
+__global__ __launch_bounds__(kPdThreads) void pp_finish_kernel(int32_t n, int32_t T, int32_t n_blk, const double *__restrict__ part,
+                                                                double *__restrict__ mean, double *__restrict__ out) {
+  const int32_t t = blockIdx.x * kPdThreads + threadIdx.x;
+  if (t >= T) return;
+  const size_t plane = (size_t)n_blk * T;
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+  for (int32_t b = 0; b < n_blk; ++b) {
+    const size_t at = (size_t)b * T + t;
+    s0 += part[at];
+    if (kMode == kPpSums || kMode == kPpDot) s1 += part[plane + at];
+    if (kMode == kPpDot) s2 += part[2 * plane + at];
+  }
+  if (kMode == kPpSums) {
+    mean[t] = s0 / (double)n;
+    mean[T + t] = s1 / (double)n;
+  } else if (kMode == kPpDot) {   // as pd_dot_kernel: 0 / 0 = NaN for a zero (constant) vector, which the clip passes on
+    double cs = s0 / (sqrt(s1) * sqrt(s2));
+    if (fabs(cs) > 1.0) cs = copysign(1.0, cs);
+    out[t] = 1.0 - cs;
+  } else {
+    out[t] = kMode == GSS_DIST_EUCLIDEAN ? sqrt(s0) : s0;
+  }
+}
+
+template <int kMode>
+int pp_run(int32_t n, const double *x, int64_t ld, int32_t T, const int32_t *col_a, const int32_t *col_b, const double *mean_in, double *mean_out,
+           int32_t n_blk, int vec_ok, double *part, double *out, hipStream_t st) {
+  hipLaunchKernelGGL(pp_partial_kernel<kMode>, dim3(ceil_div(n_blk, kPpWaves)), dim3(64 * kPpWaves), 0, st, n, x, ld, T, col_a, col_b, mean_in,
+                     n_blk, vec_ok, part);
+  GSS_LAUNCH_CHECK("pp_partial_kernel");
+  hipLaunchKernelGGL(pp_finish_kernel<kMode>, dim3(ceil_div(T, kPdThreads)), dim3(kPdThreads), 0, st, n, T, n_blk, part, mean_out, out);
+  GSS_LAUNCH_CHECK("pp_finish_kernel");
+  return GSS_OK;
+}
+
 struct DeviceScratch {   // freed on every way out of the call
   void *p = nullptr;
   ~DeviceScratch() {
@@ -307,6 +413,63 @@ int gss_profile_dist(int32_t n, const double *x, int64_t ld, int32_t na, const i
   }
   if (ws.p) GSS_HIP(hipStreamSynchronize(st));   // the scratch is freed on return: its readers have to be done
   return GSS_OK;
+}
+
+// workspace: the status words of the column check, the two means of every pair (correlation), three planes of [row blocks][T] partial sums
+size_t gss_profile_dist_pairs_workspace_bytes(int32_t n, int32_t T) {
+  if (n < 1 || T < 0) return 0;
+  const size_t n_blk = (size_t)ceil_div(n, kPpRows);
+  return kPpStatusBytes + sizeof(double) * (2 * (size_t)T + 3 * n_blk * (size_t)T);
+}
+
+int gss_profile_dist_pairs(int32_t n, const double *x, int64_t ld, int32_t T, const int32_t *col_a, const int32_t *col_b, int32_t metric,
+                           double *out, void *workspace, size_t workspace_bytes, void *stream) {
+  GSS_REQUIRE(n >= 1, "profile_dist_pairs: n=%d rows must be >= 1", n);
+  GSS_REQUIRE(T >= 0 && T <= kPdMaxList, "profile_dist_pairs: T=%d pairs must be in [0, %d]", T, kPdMaxList);
+  GSS_REQUIRE(metric >= GSS_DIST_CITYBLOCK && metric <= GSS_DIST_CORRELATION,
+              "profile_dist_pairs: metric %d is unknown (0 cityblock, 1 euclidean, 2 canberra, 3 cosine, 4 correlation)", metric);
+  GSS_REQUIRE(ld >= 1, "profile_dist_pairs: ld=%lld must be >= 1", (long long)ld);
+  if (T == 0) return GSS_OK;
+  GSS_REQUIRE(x != nullptr, "profile_dist_pairs: x is null");
+  GSS_REQUIRE(col_a != nullptr, "profile_dist_pairs: col_a is null");
+  GSS_REQUIRE(col_b != nullptr, "profile_dist_pairs: col_b is null");
+  GSS_REQUIRE(out != nullptr, "profile_dist_pairs: out is null");
+  GSS_REQUIRE(workspace != nullptr, "profile_dist_pairs: workspace is null");
+  GSS_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "profile_dist_pairs: workspace is not 8-byte aligned");
+  const size_t want = gss_profile_dist_pairs_workspace_bytes(n, T);
+  GSS_REQUIRE(workspace_bytes >= want, "profile_dist_pairs: workspace of %zu bytes is below the %zu that n=%d, T=%d need", workspace_bytes, want,
+              n, T);
+  hipStream_t st = as_stream(stream);
+  uint32_t *status = static_cast<uint32_t *>(workspace);   // nothing reads x through a list before every entry of it is known to be a column of x
+  GSS_HIP(hipMemsetAsync(status, 0xff, 8, st));
+  hipLaunchKernelGGL(pd_check_cols_kernel, dim3(ceil_div(T, kPdThreads)), dim3(kPdThreads), 0, st, T, col_a, T, col_b, ld, status);
+  GSS_LAUNCH_CHECK("pd_check_cols_kernel");
+  uint32_t h[2] = {kNoBad, kNoBad};
+  GSS_HIP(hipMemcpyAsync(h, status, 8, hipMemcpyDeviceToHost, st));
+  GSS_HIP(hipStreamSynchronize(st));
+  for (int s = 0; s < 2; ++s) {
+    if (h[s] == kNoBad) continue;
+    int32_t c = 0;
+    GSS_HIP(hipMemcpy(&c, (s == 0 ? col_a : col_b) + h[s], 4, hipMemcpyDeviceToHost));
+    return fail(GSS_EINVAL, "profile_dist_pairs: col_%c[%u] = %d is outside [0, ld=%lld)", s == 0 ? 'a' : 'b', h[s], c, (long long)ld);
+  }
+  const int32_t n_blk = ceil_div(n, kPpRows);
+  double *mean = reinterpret_cast<double *>(static_cast<char *>(workspace) + kPpStatusBytes), *part = mean + 2 * (size_t)T;
+  const int vec_ok = (ld & 1) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+  switch (metric) {
+    case GSS_DIST_CITYBLOCK:
+      return pp_run<GSS_DIST_CITYBLOCK>(n, x, ld, T, col_a, col_b, nullptr, nullptr, n_blk, vec_ok, part, out, st);
+    case GSS_DIST_EUCLIDEAN:
+      return pp_run<GSS_DIST_EUCLIDEAN>(n, x, ld, T, col_a, col_b, nullptr, nullptr, n_blk, vec_ok, part, out, st);
+    case GSS_DIST_CANBERRA:
+      return pp_run<GSS_DIST_CANBERRA>(n, x, ld, T, col_a, col_b, nullptr, nullptr, n_blk, vec_ok, part, out, st);
+    case GSS_DIST_COSINE:
+      return pp_run<kPpDot>(n, x, ld, T, col_a, col_b, nullptr, nullptr, n_blk, vec_ok, part, out, st);
+    default: {
+      const int rc = pp_run<kPpSums>(n, x, ld, T, col_a, col_b, nullptr, mean, n_blk, vec_ok, part, out, st);
+      return rc != GSS_OK ? rc : pp_run<kPpDot>(n, x, ld, T, col_a, col_b, mean, nullptr, n_blk, vec_ok, part, out, st);
+    }
+  }
 }
 
 }  // extern "C"

@@ -242,6 +242,50 @@ def compare_profiles(profiles, rows, cols, metric, device="cuda"):
     return out
 
 
+def compare_profile_pairs(profiles, col_a, col_b, metric, device="cuda"):
+    """distance between listed pairs of diffusion profiles -> device tensor fp64 [T], entry t = scipy.spatial.distance's value of `metric`
+    (one of METRICS) for profiles col_a[t] and col_b[t] (gss_profile_dist_pairs: T distances for the price of T, where compare_profiles
+    would compute T x T and keep the diagonal).  `profiles` is the device tensor PprEngine.run returned (x [N][kpad], profile c in column c,
+    used in place) or a host array [K][N] (uploaded once; the lists index its rows).  Pairs may repeat and come in any order; an entry's bits
+    do not depend on the rest of the list.  No CPU fallback."""
+    metric_id = check_metric(metric)
+    import torch
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.GssError("profile distances run on the GPU only (no CPU fallback)")
+    if isinstance(profiles, torch.Tensor):
+        x = profiles
+        if (x.dim() != 2 or x.dtype != torch.float64 or not x.is_cuda or x.shape[1] < 1 or (x.shape[1] > 1 and x.stride(1) != 1)
+                or (x.shape[0] > 1 and x.stride(0) < x.shape[1])):
+            raise ValueError("compare_profile_pairs: a profile tensor must be a device fp64 matrix [N][columns] with unit column stride and "
+                             "a row stride of at least its width")
+    else:
+        host = np.ascontiguousarray(profiles, dtype=np.float64)
+        if host.ndim != 2:
+            raise ValueError(f"compare_profile_pairs: a host profile array must be [K][N], not {host.shape}")
+        x = torch.from_numpy(host).to(dev).t().contiguous()
+    if col_a is None or col_b is None:
+        raise ValueError("compare_profile_pairs: col_a and col_b must list the pairs")
+    width = x.shape[1]
+    ca, cb = _column_list("col_a", col_a, width), _column_list("col_b", col_b, width)
+    if len(ca) != len(cb):
+        raise ValueError(f"compare_profile_pairs: col_a lists {len(ca)} profiles and col_b {len(cb)}")
+    out = torch.empty(len(ca), dtype=torch.float64, device=x.device)
+    if len(ca) == 0:
+        return out
+    if x.shape[0] < 1:
+        raise ValueError("compare_profile_pairs: the profiles are empty")
+    ld = x.stride(0) if x.shape[0] > 1 else x.shape[1]
+    lib = _lib.load()
+    with torch.cuda.device(x.device):
+        need = int(lib.gss_profile_dist_pairs_workspace_bytes(x.shape[0], len(ca)))
+        ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=x.device)
+        da, db = torch.from_numpy(ca).to(x.device), torch.from_numpy(cb).to(x.device)
+        _lib.check(lib.gss_profile_dist_pairs(x.shape[0], x.data_ptr(), ld, len(ca), da.data_ptr(), db.data_ptr(), metric_id, out.data_ptr(),
+                                              ws.data_ptr(), need, _lib.current_stream()), "gss_profile_dist_pairs")
+    return out
+
+
 def diffusion_profiles(m0, starts, proteins_of, alpha, max_iter, tol, device="cuda", max_columns=4096):
     """p_visit vectors of the given start nodes -> (profiles [K][N] fp64, iterations [K]).
     m0[u, v] = weight of edge u -> v (nx.to_scipy_sparse_matrix of the weighted MSI, diffusion_profiles.py:22-28)."""

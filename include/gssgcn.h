@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define GSS_ABI_VERSION 16  /* 16: ROC-AUC, average precision and hits@k per row in one launch -- gss_rank_metrics_rows, gss_rank_metrics_workspace_bytes; 15: entry points for tests of the row-sparse SpMM modes -- gss_spmm_bwd1_sparse_ex, gss_spmm_bwd2_sparse_res, gss_spmm_filtered, gss_mark_rows_and_neighbours, gss_batch_bits, gss_bits_fill; 14:indication x drug scores from the embedding tensor -- gss_embedding_scores; 13: pairwise distances between diffusion profiles -- gss_profile_dist; 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
+#define GSS_ABI_VERSION 17  /* 17: gene knock-outs per column of the diffusion profiles -- gss_ppr_set_knockout; distances of listed column pairs of the profile matrix -- gss_profile_dist_pairs, gss_profile_dist_pairs_workspace_bytes; 16: ROC-AUC, average precision and hits@k per row in one launch -- gss_rank_metrics_rows, gss_rank_metrics_workspace_bytes; 15: entry points for tests of the row-sparse SpMM modes -- gss_spmm_bwd1_sparse_ex, gss_spmm_bwd2_sparse_res, gss_spmm_filtered, gss_mark_rows_and_neighbours, gss_batch_bits, gss_bits_fill; 14:indication x drug scores from the embedding tensor -- gss_embedding_scores; 13: pairwise distances between diffusion profiles -- gss_profile_dist; 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
 
 #define GSS_OK 0
 #define GSS_EINVAL (-22)   /* bad argument (shape, null pointer, unsupported d) */
@@ -296,6 +296,26 @@ int gss_ppr_check_guards(gss_ppr *p);
  * GSS_ENOTCONV (x holds the last iterate) if some column needs more than max_iter iterations -- where the reference
  * raises (:90).  Synchronises the stream once per iteration (reads the number of unconverged columns). */
 int gss_ppr_run(gss_ppr *p, double alpha, double tol, int32_t max_iter, double *x, int32_t *iters_out, void *stream);
+/* per-column knock-outs: column c is the profile of start[c] on the graph in which node dead[c] has lost all its edges before the
+ * weighting (msi.graph.remove_edges_from(in_edges(g) + out_edges(g)), then weight_graph; g stays in the node list, so n, 1 / n and n tol
+ * do not change).  The rows of g's neighbours change (a neighbour's remaining protein-class edges grow, its other classes keep their
+ * share of a new row sum); the caller expresses that per column on the shared M':
+ *   - through the lists of gss_ppr_desc: an override with the factor of the row's protein-class entries, ratio 0 + zero_* for a row that
+ *     lost everything and for g's own row, the start's sel_* / keep_* / start_dangling rebuilt without g;
+ *   - corr_*: y[corr_grp_row[q]][corr_grp_col[q]] += sum_e corr_val[e] * x[corr_src[e]][corr_grp_col[q]] over the entries
+ *     e in [corr_ptr[q], corr_ptr[q + 1]) of group q, in list order, with the unscaled x: the other successors of such a row, whose factor
+ *     differs from the override's.  Groups are sorted by (column, row), unique, never on the column's start or dead row;
+ *   - dead [k] (-1 = none): the shared matrix still delivers i -> g, so x_new[dead[c]][c] is forced to 0 after the product and the column's
+ *     L1 error is corrected by |0 - x_prev| - |computed - x_prev|.
+ * One wave per column sums in a fixed order, without atomics: runs are bit-equal; a column with dead[c] = -1 and no group has the bits it
+ * has without this call, and a handle on which it was never called runs the launches it ran before.  The handle keeps the POINTERS (device,
+ * owned by the caller, alive until the handle is destroyed) and needs no buffer of its own for them.  Synchronises the device and validates
+ * on the host, refusing by name (GSS_EINVAL): a handle without the fused update (gss_ppr_desc.ovr_ptr missing or knob ppr_fused = 0 at
+ * gss_ppr_create), a null dead, missing lists, dead[c] outside [-1, n) or equal to start[c], corr_ptr not running from 0 to n_corr or
+ * decreasing, a group column outside [0, k) / row outside [0, n), groups out of (column, row) order, a group on its column's start or
+ * dead row, a source outside [0, n). */
+int gss_ppr_set_knockout(gss_ppr *p, const int32_t *dead, int64_t n_grp, const int32_t *corr_ptr, const int32_t *corr_grp_row,
+                         const int32_t *corr_grp_col, int64_t n_corr, const int32_t *corr_src, const double *corr_val);
 /* one product y = M'^T x on the handle's schedule (fp64; the kernel the iteration is built on) */
 int gss_ppr_spmm(gss_ppr *p, const double *x, double *y, void *stream);
 
@@ -497,6 +517,24 @@ int gss_rank_metrics_rows(int32_t R, int32_t C, const double *scores, int64_t ld
 #define GSS_DIST_CORRELATION 4
 int gss_profile_dist(int32_t n, const double *x, int64_t ld, int32_t na, const int32_t *cols_a, int32_t nb, const int32_t *cols_b,
                      int32_t metric, double *out, int64_t ld_out, void *stream);
+
+/* gss_profile_dist_pairs: the same x and the same five metrics for T listed pairs instead of a matrix: device int32 col_a [T], col_b [T]
+ * -> device fp64 out [T], out[t] = dist(x[:, col_a[t]], x[:, col_b[t]]), with the definitions above (NaN of a zero / constant vector,
+ * Canberra's 0 / 0 term = 0, correlation in two passes: the means first).  A screen that needs T distances pays for T, not for T x T.
+ * A bandwidth kernel: a wave owns 32 rows and sweeps the pair list, lane = pair, so the reads of one row coalesce where the listed columns
+ * are neighbours in x, and a pair whose two columns share an aligned 16 bytes (columns 2 j and 2 j + 1 in either order, ld even, x 16-byte
+ * aligned) takes both with one load.  Partial sums go to [row blocks][T] in the workspace and are added in block order, without atomics.  The
+ * order of every sum depends on n alone: two runs are bit-equal, permuting the pair list permutes out bit for bit, a pair has the same bits
+ * alone and inside a longer list, out(a, b) == out(b, a) bit for bit, and cityblock / euclidean / canberra of a column with itself is
+ * exactly 0.0.  The bits are not those of gss_profile_dist, which sums in another order.
+ * workspace: device, 8-byte aligned, at least gss_profile_dist_pairs_workspace_bytes(n, T) bytes (0 for n < 1 or T < 0); nothing is
+ * allocated inside.  T = 0 is a no-op.  Refuses (GSS_EINVAL, by name in gss_last_error): n < 1, T < 0 or above 2^21, an unknown metric,
+ * ld < 1, a null x, col_a, col_b, out or workspace, a workspace that is misaligned or too small, and a list entry outside [0, ld) (by
+ * list, position and value; nothing has read x through the lists by then, and out is untouched).  Synchronises the stream once, for that
+ * check; the distances are then enqueued. */
+size_t gss_profile_dist_pairs_workspace_bytes(int32_t n, int32_t T);
+int gss_profile_dist_pairs(int32_t n, const double *x, int64_t ld, int32_t T, const int32_t *col_a, const int32_t *col_b, int32_t metric,
+                           double *out, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- inner-product scores between listed embedding rows (predict_drug.py:52-66: sklearn.preprocessing.normalize, then np.matmul)
  * gss_embedding_scores: device fp32 emb [n][ld], ld >= d (a plan's embedding tensor with its zero padding); device int32 index lists rows
