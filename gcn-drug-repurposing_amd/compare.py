@@ -14,7 +14,7 @@ import sys
 import numpy as np
 
 from . import predict
-from .diffusion import METRICS
+from .diffusion import ALL_METRICS as METRICS
 from .msi import DRUG, INDICATION
 from .predict import PredictError, write_tsv
 

@@ -1,0 +1,228 @@
+// profile_rank.hip -- exact average-tie ranks of listed profile columns (scipy.stats.rankdata(x[:, c], method="average") per column), the
+// transform behind the "spearman" profile distance: Spearman's rho is the Pearson correlation of these ranks, so diffusion.py ranks the
+// referenced columns once and hands the rank matrix to gss_profile_dist with GSS_DIST_CORRELATION.
+//
+// include/gssgcn.h has the contract, DESIGN.md section 9.10 the cost model and the measurements.  A rank needs no sorted payload, only counts:
+//   rank(i) = (2 below(i) + tied(i) + 1) / 2,   below(i) = sum over chunks of lower_bound(chunk, key_i),
+//                                               tied(i)  = sum over chunks of upper_bound(chunk, key_i) - lower_bound(chunk, key_i)
+// so 2 below + tied = sum over chunks of (lower_bound + upper_bound), an integer <= 2 n.  Three launches per panel of kRkPanel listed columns:
+//   rk_keys_kernel   reads the panel's columns of x by rows (adjacent lanes = adjacent listed columns: coalesced when the list is) and writes
+//                    order-preserving uint64 keys [panel][n] into the workspace through a 64 x 64 LDS tile; -0.0 folds into +0.0, a NaN becomes
+//                    the all-ones key (above +inf's key, which no other value maps to)
+//   rk_rank_kernel   one workgroup per column: per chunk of kRkChunk keys, load the chunk into LDS (padded to a power of two with the all-ones
+//                    key), bitonic-sort it there, then every key of the column does its two binary searches in LDS and its owner thread adds
+//                    lower + upper to the key's int32 word of the workspace (the first chunk stores).  A column that holds a NaN is flagged
+//   rk_write_kernel  (acc + 1) / 2 into r through a 64 x 64 LDS tile, coalesced along r's rows; a flagged column is written as NaN
+// The counts are integers and every word (key, accumulator, flag, output) has one owner thread: no atomics, and a column's output depends
+// on nothing but its values.
+#include "common.h"
+
+namespace gss {
+namespace {
+
+constexpr int kRkTile = 64;            // the transposing kernels move 64 rows x 64 listed columns per workgroup
+constexpr int kRkTileThreads = 256;
+constexpr int kRkThreads = 1024;       // the rank kernel: 16 waves, four per SIMD, to keep the LDS busy (one workgroup per CU at 128 KiB)
+constexpr int kRkChunk = 16384;        // keys sorted in LDS at a time: 128 KiB
+constexpr int kRkPanel = 512;          // listed columns per pass through the workspace: two workgroups per CU on 256 CUs
+constexpr int kRkMaxRows = 1 << 24;
+constexpr int kRkStatusBytes = 256;    // the status word of the list check, in front of the workspace
+constexpr uint32_t kRkNoBad = 0xffffffffu;
+constexpr uint64_t kRkBehind = ~0ull;  // NaN and padding: above every other key
+
+__host__ __device__ inline int32_t rk_pow2_at_least(int32_t c) {
+  int32_t p = 64;
+  while (p < c) p <<= 1;
+  return p;
+}
+
+inline size_t rk_round8(size_t b) { return (b + 7) & ~(size_t)7; }
+
+// order-preserving key of a double under IEEE comparison; +0.0 and -0.0 are one value (auc.hip score_key), NaN -> kRkBehind
+__device__ __forceinline__ uint64_t rk_key(double x) {
+  if (x != x) return kRkBehind;
+  const uint64_t b = (uint64_t)__double_as_longlong(x == 0.0 ? 0.0 : x);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
+// status[0]: the first entry of cols outside [0, ld) (kRkNoBad = none); the host set the word to kRkNoBad
+__global__ __launch_bounds__(kRkTileThreads) void rk_check_cols_kernel(int32_t nc, const int32_t *__restrict__ cols, int64_t ld,
+                                                                        uint32_t *__restrict__ status) {
+  const int32_t t = blockIdx.x * kRkTileThreads + threadIdx.x;
+  if (t < nc) {
+    const int32_t c = cols[t];
+    if (c < 0 || c >= ld) atomicMin(&status[0], (uint32_t)t);
+  }
+}
+
+// panel columns [j0, j0 + 64) x rows [r0, r0 + 64): load phase lane = column, store phase lane = row.  `first` = the panel's first list position
+__global__ __launch_bounds__(kRkTileThreads) void rk_keys_kernel(int32_t n, const double *__restrict__ x, int64_t ld, int32_t pw, int32_t first,
+                                                                  const int32_t *__restrict__ cols, uint64_t *__restrict__ keys) {
+  __shared__ uint64_t tile[kRkTile][kRkTile + 1];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int32_t r0 = blockIdx.x * kRkTile, j0 = blockIdx.y * kRkTile;
+  if (j0 + tx < pw) {
+    const int32_t c = cols ? cols[first + j0 + tx] : first + j0 + tx;
+    const double *p = x + c;
+#pragma unroll 4
+    for (int m = 0; m < kRkTile / 4; ++m) {
+      const int32_t row = r0 + ty + 4 * m;
+      if (row < n) tile[ty + 4 * m][tx] = rk_key(p[(int64_t)row * ld]);
+    }
+  }
+  __syncthreads();
+  const int32_t row = r0 + tx;
+  if (row >= n) return;
+#pragma unroll 4
+  for (int m = 0; m < kRkTile / 4; ++m) {
+    const int32_t j = j0 + ty + 4 * m;
+    if (j < pw) keys[(size_t)j * n + row] = tile[tx][ty + 4 * m];
+  }
+}
+
+// first index in [0, len) whose key is >= k (strict = false) or > k (strict = true)
+__device__ __forceinline__ int32_t rk_search(const uint64_t *key, int32_t len, uint64_t k, bool strict) {
+  int32_t lo = 0, hi = len;
+  while (lo < hi) {
+    const int32_t mid = (lo + hi) >> 1;
+    const uint64_t m = key[mid];
+    if (strict ? m <= k : m < k) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// workgroup = panel column blockIdx.x; key i of the column belongs to thread i mod kRkThreads in every chunk round
+__global__ __launch_bounds__(kRkThreads) void rk_rank_kernel(int32_t n, const uint64_t *__restrict__ keys, int32_t *__restrict__ acc,
+                                                              int32_t *__restrict__ has_nan) {
+  extern __shared__ __align__(16) unsigned char rk_lds[];
+  uint64_t *srt = reinterpret_cast<uint64_t *>(rk_lds);   // [min(kRkChunk, pow2 >= n)]
+  const int tid = threadIdx.x;
+  const uint64_t *key = keys + (size_t)blockIdx.x * n;
+  int32_t *a = acc + (size_t)blockIdx.x * n;
+  int nan_here = 0;
+  for (int32_t c0 = 0; c0 < n; c0 += kRkChunk) {
+    const int32_t len = min(kRkChunk, n - c0), cpad = rk_pow2_at_least(len);
+    for (int32_t i = tid; i < cpad; i += kRkThreads) {
+      const uint64_t k = i < len ? key[c0 + i] : kRkBehind;
+      nan_here |= (i < len && k == kRkBehind) ? 1 : 0;
+      srt[i] = k;
+    }
+    __syncthreads();
+    // bitonic sort of the cpad keys, ascending
+    for (int32_t k = 2; k <= cpad; k <<= 1) {
+      for (int32_t j = k >> 1; j > 0; j >>= 1) {
+        for (int32_t i = tid; i < cpad / 2; i += kRkThreads) {
+          const int32_t lo = ((i & ~(j - 1)) << 1) | (i & (j - 1)), hi = lo + j;
+          const uint64_t u = srt[lo], v = srt[hi];
+          if ((u > v) == ((lo & k) == 0)) {
+            srt[lo] = v;
+            srt[hi] = u;
+          }
+        }
+        __syncthreads();
+      }
+    }
+    for (int32_t i = tid; i < n; i += kRkThreads) {
+      const uint64_t k = key[i];
+      const int32_t both = rk_search(srt, len, k, false) + rk_search(srt, len, k, true);
+      a[i] = c0 == 0 ? both : a[i] + both;
+    }
+    __syncthreads();   // the next chunk overwrites srt
+  }
+  const int any = __syncthreads_or(nan_here);
+  if (tid == 0) has_nan[blockIdx.x] = any;
+}
+
+// panel columns [j0, j0 + 64) x rows [r0, r0 + 64): load phase lane = row, store phase lane = column.  r points at the panel's first column
+__global__ __launch_bounds__(kRkTileThreads) void rk_write_kernel(int32_t n, int32_t pw, const int32_t *__restrict__ acc,
+                                                                   const int32_t *__restrict__ has_nan, double *__restrict__ r, int64_t ld_r) {
+  __shared__ int32_t tile[kRkTile][kRkTile + 1];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int32_t r0 = blockIdx.x * kRkTile, j0 = blockIdx.y * kRkTile;
+  if (r0 + tx < n) {
+#pragma unroll 4
+    for (int m = 0; m < kRkTile / 4; ++m) {
+      const int32_t j = j0 + ty + 4 * m;
+      if (j < pw) tile[ty + 4 * m][tx] = acc[(size_t)j * n + r0 + tx];
+    }
+  }
+  __syncthreads();
+  const int32_t j = j0 + tx;
+  if (j >= pw) return;
+  const bool nan_col = has_nan[j] != 0;
+#pragma unroll 4
+  for (int m = 0; m < kRkTile / 4; ++m) {
+    const int32_t row = r0 + ty + 4 * m;
+    if (row < n)   // acc = 2 below + tied <= 2 n: the sum and the halving are exact
+      r[(int64_t)row * ld_r + j] = nan_col ? __longlong_as_double(0x7ff8000000000000ll) : (double)(tile[tx][ty + 4 * m] + 1) * 0.5;
+  }
+}
+
+}  // namespace
+}  // namespace gss
+
+using namespace gss;
+
+extern "C" {
+
+// status words, then per panel column: n keys of 8 bytes, n accumulators of 4 bytes, one NaN flag
+size_t gss_profile_rank_workspace_bytes(int32_t n, int32_t nc) {
+  if (n < 1 || nc < 0) return 0;
+  const size_t p = (size_t)(nc < kRkPanel ? nc : kRkPanel);
+  return kRkStatusBytes + p * (size_t)n * 8 + rk_round8(p * (size_t)n * 4) + rk_round8(p * 4);
+}
+
+int gss_profile_rank(int32_t n, const double *x, int64_t ld, int32_t nc, const int32_t *cols, double *r, int64_t ld_r, void *workspace,
+                     size_t workspace_bytes, void *stream) {
+  GSS_REQUIRE(n >= 1, "profile_rank: n=%d rows must be >= 1", n);
+  GSS_REQUIRE(n <= kRkMaxRows, "profile_rank: n=%d rows is above the limit of %d (the counting scheme is quadratic in n / chunk: every key "
+              "searches every sorted chunk of %d keys)", n, kRkMaxRows, kRkChunk);
+  GSS_REQUIRE(nc >= 0, "profile_rank: nc=%d columns must be >= 0", nc);
+  GSS_REQUIRE(ld >= 1, "profile_rank: ld=%lld must be >= 1", (long long)ld);
+  GSS_REQUIRE(ld_r >= nc, "profile_rank: ld_r=%lld is below nc=%d", (long long)ld_r, nc);
+  if (nc == 0) return GSS_OK;
+  GSS_REQUIRE(x != nullptr, "profile_rank: x is null");
+  GSS_REQUIRE(r != nullptr, "profile_rank: r is null");
+  GSS_REQUIRE(workspace != nullptr, "profile_rank: workspace is null");
+  GSS_REQUIRE(cols || nc <= ld, "profile_rank: ld=%lld is below nc=%d (cols is null: columns 0 .. nc - 1)", (long long)ld, nc);
+  GSS_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "profile_rank: workspace is not 8-byte aligned");
+  const size_t want = gss_profile_rank_workspace_bytes(n, nc);
+  GSS_REQUIRE(workspace_bytes >= want, "profile_rank: workspace of %zu bytes is below the %zu that n=%d, nc=%d need", workspace_bytes, want, n,
+              nc);
+  hipStream_t st = as_stream(stream);
+  if (cols) {   // nothing reads x through the list before every entry of it is known to be a column of x
+    uint32_t *status = static_cast<uint32_t *>(workspace);
+    GSS_HIP(hipMemsetAsync(status, 0xff, 8, st));
+    hipLaunchKernelGGL(rk_check_cols_kernel, dim3(ceil_div(nc, kRkTileThreads)), dim3(kRkTileThreads), 0, st, nc, cols, ld, status);
+    GSS_LAUNCH_CHECK("rk_check_cols_kernel");
+    uint32_t h = kRkNoBad;
+    GSS_HIP(hipMemcpyAsync(&h, status, 4, hipMemcpyDeviceToHost, st));
+    GSS_HIP(hipStreamSynchronize(st));
+    if (h != kRkNoBad) {
+      int32_t c = 0;
+      GSS_HIP(hipMemcpy(&c, cols + h, 4, hipMemcpyDeviceToHost));
+      return fail(GSS_EINVAL, "profile_rank: cols[%u] = %d is outside [0, ld=%lld)", h, c, (long long)ld);
+    }
+  }
+  const size_t p = (size_t)(nc < kRkPanel ? nc : kRkPanel);
+  char *base = static_cast<char *>(workspace) + kRkStatusBytes;
+  uint64_t *keys = reinterpret_cast<uint64_t *>(base);
+  int32_t *acc = reinterpret_cast<int32_t *>(base + p * (size_t)n * 8);
+  int32_t *has_nan = reinterpret_cast<int32_t *>(base + p * (size_t)n * 8 + rk_round8(p * (size_t)n * 4));
+  const size_t lds = (size_t)(n < kRkChunk ? rk_pow2_at_least(n) : kRkChunk) * 8;
+  const size_t lds_arg = lds_request(rk_rank_kernel, lds);
+  for (int32_t first = 0; first < nc; first += kRkPanel) {   // the stream orders a panel's three launches and the panels after one another
+    const int32_t pw = nc - first < kRkPanel ? nc - first : kRkPanel;
+    const dim3 tiles(ceil_div(n, kRkTile), ceil_div(pw, kRkTile));
+    hipLaunchKernelGGL(rk_keys_kernel, tiles, dim3(kRkTileThreads), 0, st, n, x, ld, pw, first, cols, keys);
+    GSS_LAUNCH_CHECK("rk_keys_kernel");
+    hipLaunchKernelGGL(rk_rank_kernel, dim3(pw), dim3(kRkThreads), lds_arg, st, n, keys, acc, has_nan);
+    GSS_LAUNCH_CHECK("rk_rank_kernel");
+    hipLaunchKernelGGL(rk_write_kernel, tiles, dim3(kRkTileThreads), 0, st, n, pw, acc, has_nan, r + first, ld_r);
+    GSS_LAUNCH_CHECK("rk_write_kernel");
+  }
+  return GSS_OK;
+}
+
+}  // extern "C"

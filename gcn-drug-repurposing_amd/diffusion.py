@@ -12,7 +12,8 @@ per start node.
 
 compare_profiles: the comparison of two profiles the method rests on (multiscale/README.md, overview (c)), which the reference never makes: a
 pairwise distance between columns of the profile matrix (gss_profile_dist, csrc/profile_dist.hip), on the tensor PprEngine.run returned or on
-profiles loaded from a directory."""
+profiles loaded from a directory.  rank_profiles: the average-tie ranks of the nodes within each profile (gss_profile_rank,
+csrc/profile_rank.hip); the "spearman" distance is the correlation distance of those ranks."""
 from __future__ import annotations
 
 import ctypes as C
@@ -168,31 +169,107 @@ class PprEngine:
 METRICS = ("cityblock", "euclidean", "canberra", "cosine", "correlation")   # index = GSS_DIST_* of include/gssgcn.h
 
 
+RANK_METRICS = ("spearman",)   # the metric of the same position in RANK_BASE on the average-tie ranks of the profiles (gss_profile_rank); no C id
+RANK_BASE = ("correlation",)
+ALL_METRICS = METRICS + RANK_METRICS
+
+
 def check_metric(metric):
-    if metric not in METRICS:
-        raise ValueError(f"profile distance {metric!r} is unknown; choose one of {', '.join(METRICS)}")
-    return METRICS.index(metric)
+    """-> the GSS_DIST_* id the distance kernels take: the metric's own, or for a rank metric that of the metric applied to the ranks"""
+    if metric not in ALL_METRICS:
+        raise ValueError(f"profile distance {metric!r} is unknown; choose one of {', '.join(ALL_METRICS)}")
+    return METRICS.index(RANK_BASE[RANK_METRICS.index(metric)] if metric in RANK_METRICS else metric)
 
 
-def _column_list(what, sel, width, names=None):
+def _column_list(what, sel, width, names=None, who="compare_profiles"):
     """-> int32 column indices of a selection: integers (None = every column), or keys of `names` ({key: column})"""
     if sel is None:
         return np.arange(width, dtype=np.int32)
     if names is not None:
         missing = [k for k in sel if k not in names]
         if missing:
-            raise ValueError(f"compare_profiles: {what} {missing[0]!r} has no profile")
+            raise ValueError(f"{who}: {what} {missing[0]!r} has no profile")
         return np.asarray([names[k] for k in sel], dtype=np.int32)
     idx = np.asarray(sel, dtype=np.int64).reshape(-1)
     bad = np.flatnonzero((idx < 0) | (idx >= width))
     if len(bad):
-        raise ValueError(f"compare_profiles: {what} index {int(idx[bad[0]])} is outside [0, {width})")
+        raise ValueError(f"{who}: {what} index {int(idx[bad[0]])} is outside [0, {width})")
     return idx.astype(np.int32)
+
+
+def _row_stride(x):
+    return x.stride(0) if x.shape[0] > 1 else x.shape[1]   # one row: no row stride is ever applied (torch leaves it unspecified)
+
+
+def _rank_columns(x, cols):
+    """average-tie ranks of the listed columns (host int32 array) of the device fp64 matrix x [N][width] -> device fp64 [N][len(cols)]
+    (gss_profile_rank, csrc/profile_rank.hip; exact, a column with a NaN comes out NaN)"""
+    import torch
+    n, nc = x.shape[0], len(cols)
+    r = torch.empty(n, nc, dtype=torch.float64, device=x.device)
+    if nc == 0:
+        return r
+    lib = _lib.load()
+    with torch.cuda.device(x.device):
+        need = int(lib.gss_profile_rank_workspace_bytes(n, nc))
+        ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=x.device)
+        lst = None if np.array_equal(cols, np.arange(nc)) else torch.from_numpy(np.ascontiguousarray(cols, dtype=np.int32)).to(x.device)
+        _lib.check(lib.gss_profile_rank(n, x.data_ptr(), _row_stride(x), nc, _lib.ptr(lst), r.data_ptr(), nc, ws.data_ptr(), need,
+                                        _lib.current_stream()), "gss_profile_rank")
+    return r
+
+
+def _rank_referenced(x, lists):
+    """a rank metric's first step: the unique columns the lists name are ranked once -> (rank matrix [N][unique], the lists remapped into it)"""
+    uniq = np.unique(np.concatenate(lists)).astype(np.int32)
+    return _rank_columns(x, uniq), [np.searchsorted(uniq, c).astype(np.int32) for c in lists]
+
+
+def rank_profiles(profiles, cols=None, device="cuda"):
+    """average-tie ranks of the nodes within diffusion profiles -> device tensor fp64 [N][len(cols)], column j =
+    scipy.stats.rankdata(profile cols[j], method="average"), exactly (gss_profile_rank): the order of a profile's nodes, "the proteins and
+    functions a profile ranks highest", and the transform behind the "spearman" distance.  `profiles` is what compare_profiles accepts: the
+    device tensor x [N][kpad] (used in place; cols are column indices), a host array [K][N] (cols index its rows) or a {name: vector} dict
+    (cols are names).  cols may repeat and come in any order; None means every profile (not for a dict).  A profile that holds a NaN has
+    NaN for every rank.  No CPU fallback."""
+    import torch
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.GssError("profile ranks are computed on the GPU only (no CPU fallback)")
+    if isinstance(profiles, torch.Tensor):
+        x = profiles
+        if (x.dim() != 2 or x.dtype != torch.float64 or not x.is_cuda or x.shape[1] < 1 or (x.shape[1] > 1 and x.stride(1) != 1)
+                or (x.shape[0] > 1 and x.stride(0) < x.shape[1])):
+            raise ValueError("rank_profiles: a profile tensor must be a device fp64 matrix [N][columns] with unit column stride and "
+                             "a row stride of at least its width")
+        c = _column_list("column", cols, x.shape[1], who="rank_profiles")
+    elif isinstance(profiles, dict):
+        if cols is None:
+            raise ValueError("rank_profiles: cols must name the profiles of a dict")
+        keys = list(dict.fromkeys(cols))
+        c = _column_list("column", cols, len(keys), {k: i for i, k in enumerate(keys) if k in profiles}, who="rank_profiles")
+        host = [np.asarray(profiles[k], dtype=np.float64).reshape(-1) for k in keys]
+        if len({len(v) for v in host}) > 1:
+            raise ValueError("rank_profiles: the profiles differ in length")
+        if not host:
+            raise ValueError("rank_profiles: no profile is named")
+        x = torch.from_numpy(np.stack(host)).to(dev).t().contiguous()
+    else:
+        host = np.ascontiguousarray(profiles, dtype=np.float64)
+        if host.ndim != 2:
+            raise ValueError(f"rank_profiles: a host profile array must be [K][N], not {host.shape}")
+        c = _column_list("column", cols, host.shape[0], who="rank_profiles")
+        x = torch.from_numpy(host).to(dev).t().contiguous()
+    if x.shape[0] < 1:
+        raise ValueError("rank_profiles: the profiles are empty")
+    return _rank_columns(x, c)
 
 
 def compare_profiles(profiles, rows, cols, metric, device="cuda"):
     """distance between diffusion profiles -> device tensor fp64 [len(rows)][len(cols)], scipy.spatial.distance.cdist's value of `metric`
-    (one of METRICS) for every (row profile, column profile) pair.  `profiles` is
+    (one of ALL_METRICS) for every (row profile, column profile) pair; "spearman" = 1 - Spearman's rho = the correlation distance of the
+    profiles' average-tie ranks (the unique profiles rows and cols name are ranked once by gss_profile_rank, then compared as correlation
+    compares: a constant profile or one with a NaN gives NaN).  `profiles` is
       * the device tensor PprEngine.run returned, x [N][kpad] with profile c in column c: used in place; rows / cols are column indices;
       * a host array [K][N] (one profile per row): uploaded once, transposed into the kernel's layout; rows / cols index its rows;
       * the {name: vector} dict DiffusionProfiles.load_diffusion_profiles fills: the named profiles are uploaded once; rows / cols are names.
@@ -231,10 +308,12 @@ def compare_profiles(profiles, rows, cols, metric, device="cuda"):
         return out
     if x.shape[0] < 1:
         raise ValueError("compare_profiles: the profiles are empty")
+    if metric in RANK_METRICS:   # the referenced profiles are ranked once; metric_id is the base metric's, applied to the ranks
+        x, (ca, cb) = _rank_referenced(x, [ca, cb])
     lists = []
     for c in (ca, cb):   # "the first n columns" needs no list (and no check of one)
         lists.append(None if np.array_equal(c, np.arange(len(c))) else torch.from_numpy(c).to(x.device))
-    ld = x.stride(0) if x.shape[0] > 1 else x.shape[1]   # one row: no row stride is ever applied (torch leaves it unspecified)
+    ld = _row_stride(x)
     with torch.cuda.device(x.device):
         _lib.check(_lib.load().gss_profile_dist(x.shape[0], x.data_ptr(), ld, len(ca), _lib.ptr(lists[0]), len(cb), _lib.ptr(lists[1]),
                                                 metric_id, out.data_ptr(), len(cb), _lib.current_stream()),
@@ -244,7 +323,7 @@ def compare_profiles(profiles, rows, cols, metric, device="cuda"):
 
 def compare_profile_pairs(profiles, col_a, col_b, metric, device="cuda"):
     """distance between listed pairs of diffusion profiles -> device tensor fp64 [T], entry t = scipy.spatial.distance's value of `metric`
-    (one of METRICS) for profiles col_a[t] and col_b[t] (gss_profile_dist_pairs: T distances for the price of T, where compare_profiles
+    (one of ALL_METRICS; "spearman" as in compare_profiles) for profiles col_a[t] and col_b[t] (gss_profile_dist_pairs: T distances for the price of T, where compare_profiles
     would compute T x T and keep the diagonal).  `profiles` is the device tensor PprEngine.run returned (x [N][kpad], profile c in column c,
     used in place) or a host array [K][N] (uploaded once; the lists index its rows).  Pairs may repeat and come in any order; an entry's bits
     do not depend on the rest of the list.  No CPU fallback."""
@@ -275,7 +354,9 @@ def compare_profile_pairs(profiles, col_a, col_b, metric, device="cuda"):
         return out
     if x.shape[0] < 1:
         raise ValueError("compare_profile_pairs: the profiles are empty")
-    ld = x.stride(0) if x.shape[0] > 1 else x.shape[1]
+    if metric in RANK_METRICS:
+        x, (ca, cb) = _rank_referenced(x, [ca, cb])
+    ld = _row_stride(x)
     lib = _lib.load()
     with torch.cuda.device(x.device):
         need = int(lib.gss_profile_dist_pairs_workspace_bytes(x.shape[0], len(ca)))

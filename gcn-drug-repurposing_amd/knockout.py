@@ -433,7 +433,7 @@ def usable_triples(msi_graph, triples, err):
 
 def parse_args(argv=None):
     import argparse
-    from .diffusion import METRICS
+    from .diffusion import ALL_METRICS as METRICS
     p = argparse.ArgumentParser(description="Drug Repurposing: knock genes out of the diffusion profiles of a drug and an indication (knockout.py)")
     p.add_argument("-c", "--config", default="config.json", type=str, help="config file path (default: config.json), as evaluate_auc.py reads it")
     p.add_argument("--triples", default=None, type=str, help="a TSV with the columns drug, indication, gene (data/pharmgkb_df.tsv): one row out per triple")

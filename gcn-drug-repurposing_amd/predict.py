@@ -64,8 +64,8 @@ def _get(cfg, *keys, default=KeyError):
 
 def compare_setting(cfg, method):
     """diffusion.compare: 'visit' (the default: the query's visit probability at the drug's node, the reference's score) or one of
-    diffusion.METRICS (the score is minus that distance between the query's profile and the drug's own)"""
-    from .diffusion import METRICS
+    diffusion.ALL_METRICS (the score is minus that distance between the query's profile and the drug's own)"""
+    from .diffusion import ALL_METRICS as METRICS
     compare = _get(cfg, "diffusion", "compare", default="visit")
     if compare == "visit":
         return compare

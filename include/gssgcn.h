@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define GSS_ABI_VERSION 17  /* 17: gene knock-outs per column of the diffusion profiles -- gss_ppr_set_knockout; distances of listed column pairs of the profile matrix -- gss_profile_dist_pairs, gss_profile_dist_pairs_workspace_bytes; 16: ROC-AUC, average precision and hits@k per row in one launch -- gss_rank_metrics_rows, gss_rank_metrics_workspace_bytes; 15: entry points for tests of the row-sparse SpMM modes -- gss_spmm_bwd1_sparse_ex, gss_spmm_bwd2_sparse_res, gss_spmm_filtered, gss_mark_rows_and_neighbours, gss_batch_bits, gss_bits_fill; 14:indication x drug scores from the embedding tensor -- gss_embedding_scores; 13: pairwise distances between diffusion profiles -- gss_profile_dist; 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
+#define GSS_ABI_VERSION 18  /* 18: exact average-tie ranks of listed profile columns, the transform behind the spearman distance -- gss_profile_rank, gss_profile_rank_workspace_bytes; 17: gene knock-outs per column of the diffusion profiles -- gss_ppr_set_knockout; distances of listed column pairs of the profile matrix -- gss_profile_dist_pairs, gss_profile_dist_pairs_workspace_bytes; 16: ROC-AUC, average precision and hits@k per row in one launch -- gss_rank_metrics_rows, gss_rank_metrics_workspace_bytes; 15: entry points for tests of the row-sparse SpMM modes -- gss_spmm_bwd1_sparse_ex, gss_spmm_bwd2_sparse_res, gss_spmm_filtered, gss_mark_rows_and_neighbours, gss_batch_bits, gss_bits_fill; 14:indication x drug scores from the embedding tensor -- gss_embedding_scores; 13: pairwise distances between diffusion profiles -- gss_profile_dist; 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
 
 #define GSS_OK 0
 #define GSS_EINVAL (-22)   /* bad argument (shape, null pointer, unsupported d) */
@@ -535,6 +535,29 @@ int gss_profile_dist(int32_t n, const double *x, int64_t ld, int32_t na, const i
 size_t gss_profile_dist_pairs_workspace_bytes(int32_t n, int32_t T);
 int gss_profile_dist_pairs(int32_t n, const double *x, int64_t ld, int32_t T, const int32_t *col_a, const int32_t *col_b, int32_t metric,
                            double *out, void *workspace, size_t workspace_bytes, void *stream);
+
+/* gss_profile_rank: exact average-tie ranks of listed columns of the profile matrix -- the transform behind the "spearman" profile distance
+ * (Spearman's rho is the Pearson correlation of the ranks: rank the columns here, then gss_profile_dist with GSS_DIST_CORRELATION on r; there
+ * is no metric id for it).  x: device fp64 [n][ld], profile c = column c (what gss_ppr_run writes and gss_profile_dist reads); cols: device
+ * int32 [nc], honoured as given (any order, repeats allowed; null = columns 0 .. nc - 1) -> r: device fp64 [n][ld_r], for j < nc
+ *   r[:, j] = scipy.stats.rankdata(x[:, cols[j]], method="average")
+ * EXACTLY: a rank is (2 below + tied + 1) / 2 with integer counts, so every output is an integer or a half-integer.  Columns j >= nc of r are
+ * not touched.  r and x must not overlap (not checked).  Order is that of IEEE comparison, as numpy sorts: -0.0 and +0.0 are one value,
+ * +-inf are ordinary extremes, subnormals are distinct values.  A listed column that holds a NaN comes out NaN in all n entries (scipy's
+ * nan_policy="propagate"): a value, not an error.  The counts are integers and every output word has one owner thread: a column's bits do
+ * not depend on nc, on its place in the list, on the grid or on an earlier call; nothing goes through an atomic.
+ * Kernel: per panel of 512 listed columns, a transposing pass writes order-preserving uint64 keys [panel][n]; one workgroup per column sorts
+ * the column in LDS in chunks of 16,384 keys and lets every key count, by two binary searches per chunk, the keys below it and tied with it
+ * into an int32 word; a second transposing pass writes (count + 1) / 2.  The work is quadratic in n / 16,384, hence the limit on n.
+ * workspace: the caller's, device, 8-byte aligned, at least gss_profile_rank_workspace_bytes(n, nc) bytes, which depends on (n, nc) only:
+ *   256 + p n 8 + round8(p n 4) + round8(p 4)   with p = min(nc, 512), round8 = up to a multiple of 8   (0 for n < 1 or nc < 0)
+ * Nothing is allocated inside.  nc = 0 is a no-op.  Refuses (GSS_EINVAL, by name in gss_last_error, before anything reads x through the list
+ * and with r untouched): n < 1, n above 2^24, nc < 0, ld < 1, ld_r < nc, and with nc > 0 a null x, r or workspace, ld below nc where cols is
+ * null, a misaligned or too small workspace (naming the needed size), and a list entry outside [0, ld) (by position and value: a check
+ * launch of its own and one synchronisation of the stream; a null list needs neither and the call then only enqueues). */
+size_t gss_profile_rank_workspace_bytes(int32_t n, int32_t nc);
+int gss_profile_rank(int32_t n, const double *x, int64_t ld, int32_t nc, const int32_t *cols, double *r, int64_t ld_r, void *workspace,
+                     size_t workspace_bytes, void *stream);
 
 /* ---- inner-product scores between listed embedding rows (predict_drug.py:52-66: sklearn.preprocessing.normalize, then np.matmul)
  * gss_embedding_scores: device fp32 emb [n][ld], ld >= d (a plan's embedding tensor with its zero padding); device int32 index lists rows
