@@ -14,8 +14,9 @@
 //                    lower + upper to the key's int32 word of the workspace (the first chunk stores).  A column that holds a NaN is flagged
 //   rk_write_kernel  (acc + 1) / 2 into r through a 64 x 64 LDS tile, coalesced along r's rows; a flagged column is written as NaN
 // The counts are integers and every word (key, accumulator, flag, output) has one owner thread: no atomics, and a column's output depends
-// on nothing but its values.
-#include "common.h"
+// on nothing but its values.  The key, the sort and the search are rank_keys.h's, the ones gss_auc_rows and gss_rank_metrics_rows count
+// ties with: a rank here and a U statistic there order the same doubles the same way.
+#include "rank_keys.h"
 
 namespace gss {
 namespace {
@@ -28,22 +29,8 @@ constexpr int kRkPanel = 512;          // listed columns per pass through the wo
 constexpr int kRkMaxRows = 1 << 24;
 constexpr int kRkStatusBytes = 256;    // the status word of the list check, in front of the workspace
 constexpr uint32_t kRkNoBad = 0xffffffffu;
-constexpr uint64_t kRkBehind = ~0ull;  // NaN and padding: above every other key
-
-__host__ __device__ inline int32_t rk_pow2_at_least(int32_t c) {
-  int32_t p = 64;
-  while (p < c) p <<= 1;
-  return p;
-}
 
 inline size_t rk_round8(size_t b) { return (b + 7) & ~(size_t)7; }
-
-// order-preserving key of a double under IEEE comparison; +0.0 and -0.0 are one value (auc.hip score_key), NaN -> kRkBehind
-__device__ __forceinline__ uint64_t rk_key(double x) {
-  if (x != x) return kRkBehind;
-  const uint64_t b = (uint64_t)__double_as_longlong(x == 0.0 ? 0.0 : x);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
 
 // status[0]: the first entry of cols outside [0, ld) (kRkNoBad = none); the host set the word to kRkNoBad
 __global__ __launch_bounds__(kRkTileThreads) void rk_check_cols_kernel(int32_t nc, const int32_t *__restrict__ cols, int64_t ld,
@@ -67,7 +54,7 @@ __global__ __launch_bounds__(kRkTileThreads) void rk_keys_kernel(int32_t n, cons
 #pragma unroll 4
     for (int m = 0; m < kRkTile / 4; ++m) {
       const int32_t row = r0 + ty + 4 * m;
-      if (row < n) tile[ty + 4 * m][tx] = rk_key(p[(int64_t)row * ld]);
+      if (row < n) tile[ty + 4 * m][tx] = order_key_nan_behind(p[(int64_t)row * ld]);
     }
   }
   __syncthreads();
@@ -80,18 +67,6 @@ __global__ __launch_bounds__(kRkTileThreads) void rk_keys_kernel(int32_t n, cons
   }
 }
 
-// first index in [0, len) whose key is >= k (strict = false) or > k (strict = true)
-__device__ __forceinline__ int32_t rk_search(const uint64_t *key, int32_t len, uint64_t k, bool strict) {
-  int32_t lo = 0, hi = len;
-  while (lo < hi) {
-    const int32_t mid = (lo + hi) >> 1;
-    const uint64_t m = key[mid];
-    if (strict ? m <= k : m < k) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
 // workgroup = panel column blockIdx.x; key i of the column belongs to thread i mod kRkThreads in every chunk round
 __global__ __launch_bounds__(kRkThreads) void rk_rank_kernel(int32_t n, const uint64_t *__restrict__ keys, int32_t *__restrict__ acc,
                                                               int32_t *__restrict__ has_nan) {
@@ -102,30 +77,17 @@ __global__ __launch_bounds__(kRkThreads) void rk_rank_kernel(int32_t n, const ui
   int32_t *a = acc + (size_t)blockIdx.x * n;
   int nan_here = 0;
   for (int32_t c0 = 0; c0 < n; c0 += kRkChunk) {
-    const int32_t len = min(kRkChunk, n - c0), cpad = rk_pow2_at_least(len);
+    const int32_t len = min(kRkChunk, n - c0), cpad = pow2_at_least(len);
     for (int32_t i = tid; i < cpad; i += kRkThreads) {
-      const uint64_t k = i < len ? key[c0 + i] : kRkBehind;
-      nan_here |= (i < len && k == kRkBehind) ? 1 : 0;
+      const uint64_t k = i < len ? key[c0 + i] : kBehind;
+      nan_here |= (i < len && k == kBehind) ? 1 : 0;
       srt[i] = k;
     }
     __syncthreads();
-    // bitonic sort of the cpad keys, ascending
-    for (int32_t k = 2; k <= cpad; k <<= 1) {
-      for (int32_t j = k >> 1; j > 0; j >>= 1) {
-        for (int32_t i = tid; i < cpad / 2; i += kRkThreads) {
-          const int32_t lo = ((i & ~(j - 1)) << 1) | (i & (j - 1)), hi = lo + j;
-          const uint64_t u = srt[lo], v = srt[hi];
-          if ((u > v) == ((lo & k) == 0)) {
-            srt[lo] = v;
-            srt[hi] = u;
-          }
-        }
-        __syncthreads();
-      }
-    }
+    sort_keys<kRkThreads>(srt, cpad, tid);
     for (int32_t i = tid; i < n; i += kRkThreads) {
       const uint64_t k = key[i];
-      const int32_t both = rk_search(srt, len, k, false) + rk_search(srt, len, k, true);
+      const int32_t both = search(srt, 0, len, k, false) + search(srt, 0, len, k, true);
       a[i] = c0 == 0 ? both : a[i] + both;
     }
     __syncthreads();   // the next chunk overwrites srt
@@ -210,7 +172,7 @@ int gss_profile_rank(int32_t n, const double *x, int64_t ld, int32_t nc, const i
   uint64_t *keys = reinterpret_cast<uint64_t *>(base);
   int32_t *acc = reinterpret_cast<int32_t *>(base + p * (size_t)n * 8);
   int32_t *has_nan = reinterpret_cast<int32_t *>(base + p * (size_t)n * 8 + rk_round8(p * (size_t)n * 4));
-  const size_t lds = (size_t)(n < kRkChunk ? rk_pow2_at_least(n) : kRkChunk) * 8;
+  const size_t lds = (size_t)(n < kRkChunk ? pow2_at_least(n) : kRkChunk) * 8;
   const size_t lds_arg = lds_request(rk_rank_kernel, lds);
   for (int32_t first = 0; first < nc; first += kRkPanel) {   // the stream orders a panel's three launches and the panels after one another
     const int32_t pw = nc - first < kRkPanel ? nc - first : kRkPanel;

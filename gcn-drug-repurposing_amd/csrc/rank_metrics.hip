@@ -2,8 +2,8 @@
 // multiscale-interactome work reports for drug-indication prediction; include/gssgcn.h has the contract, DESIGN.md section 9.8 the
 // definitions, the cost model and the measurement).
 //
-// One workgroup per row, as auc.hip (whose key, search and sort this file restates: auc.hip stays as it is).  160 KiB of LDS hold the
-// 16,384 keys of one sorted array, not two, so the row is sorted twice in the same LDS buffer:
+// One workgroup per row, as auc.hip; the key, the sort, the search and the check of the row's positives are rank_keys.h's, which both
+// files use.  160 KiB of LDS hold the 16,384 keys of one sorted array, not two, so the row is sorted twice in the same LDS buffer:
 //   1. the positives' keys (negatives and padding get the all-ones key and sort behind them); the P sorted keys are parked in the row's
 //      slice of the caller's workspace, ws[r * C .. r * C + P);
 //   2. the negatives' keys, as auc.hip does; they stay in LDS.
@@ -20,9 +20,7 @@
 //         positive's group holds the item its group has no positive and hits = above.
 // Every output word is written by one thread and no result goes through an atomic: bitwise reproducible, and a function of the row's
 // multiset of (score, label) pairs alone.
-#include <new>
-
-#include "common.h"
+#include "rank_keys.h"
 
 namespace gss {
 namespace {
@@ -31,57 +29,11 @@ constexpr int kRmThreads = 256;
 constexpr int kRmWaves = kRmThreads / kWave;
 constexpr int kRmMaxCols = 16384;               // the sort buffer: pow2ceil(C) keys of 8 bytes in LDS (128 KiB at the limit)
 constexpr int kRmMaxCuts = 8;
-constexpr uint64_t kBehind = ~0ull;             // the key of the other class and of padding: above every finite score's key
-
-// per-row refusal, written to n_pos[r] as -code with the offending column in n_neg[r] (auc.hip's codes)
-enum RmRefusal { kBadPtr = 1, kColRange = 2, kColRepeat = 3, kNonFinite = 4 };
 
 struct Cuts {
   int32_t nk;
   int32_t m[kRmMaxCuts];   // ascending index of the item of rank min(k, C): C - min(k, C)
 };
-
-inline int64_t pow2_at_least(int64_t c) {
-  int64_t p = 64;
-  while (p < c) p <<= 1;
-  return p;
-}
-
-__device__ __forceinline__ bool finite_bits(uint64_t b) { return (b & 0x7ff0000000000000ull) != 0x7ff0000000000000ull; }
-
-// order-preserving key of a finite double; +0.0 and -0.0 are one value
-__device__ __forceinline__ uint64_t score_key(double x) {
-  const uint64_t b = (uint64_t)__double_as_longlong(x == 0.0 ? 0.0 : x);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-
-// first index in [lo, hi) whose key is >= k (strict = false) or > k (strict = true); hi if there is none
-__device__ __forceinline__ int32_t search(const uint64_t *key, int32_t lo, int32_t hi, uint64_t k, bool strict) {
-  while (lo < hi) {
-    const int32_t mid = (lo + hi) >> 1;
-    const uint64_t m = key[mid];
-    if (strict ? m <= k : m < k) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-// bitonic sort of the cpad keys, ascending (cpad a power of two); ends behind a barrier
-__device__ __forceinline__ void sort_keys(uint64_t *key, int32_t cpad, int32_t tid) {
-  for (int32_t k = 2; k <= cpad; k <<= 1) {
-    for (int32_t j = k >> 1; j > 0; j >>= 1) {
-      for (int32_t i = tid; i < cpad / 2; i += kRmThreads) {
-        const int32_t lo = ((i & ~(j - 1)) << 1) | (i & (j - 1)), hi = lo + j;
-        const uint64_t x = key[lo], y = key[hi];
-        if ((x > y) == ((lo & k) == 0)) {
-          key[lo] = y;
-          key[hi] = x;
-        }
-      }
-      __syncthreads();
-    }
-  }
-}
 
 __global__ __launch_bounds__(kRmThreads) void rank_metrics_kernel(int32_t C, int32_t cpad, const double *__restrict__ scores, int64_t ld,
                                                                   const int32_t *__restrict__ pos_ptr, const int32_t *__restrict__ pos_col,
@@ -91,7 +43,6 @@ __global__ __launch_bounds__(kRmThreads) void rank_metrics_kernel(int32_t C, int
   extern __shared__ __align__(16) unsigned char lds[];
   uint64_t *key = reinterpret_cast<uint64_t *>(lds);                        // [cpad]
   uint32_t *is_pos = reinterpret_cast<uint32_t *>(lds + (size_t)cpad * 8);  // [cpad / 32] bitmap
-  __shared__ int32_t bad_range, bad_repeat, bad_finite;
   __shared__ unsigned long long part_u[kRmWaves];
   __shared__ double part_ap[kRmWaves];
   __shared__ int32_t part_above[kRmWaves][kRmMaxCuts];
@@ -100,79 +51,30 @@ __global__ __launch_bounds__(kRmThreads) void rank_metrics_kernel(int32_t C, int
   const double qnan = __longlong_as_double(0x7ff8000000000000ll);
   const double *row = scores + (int64_t)r * ld;
   uint64_t *park = ws + (int64_t)r * C;                                     // [P] of the row's C words
-  const int32_t b = pos_ptr[r], e = pos_ptr[r + 1];
-  const int32_t P = e - b;
-  if (b < 0 || P < 0 || P > C || (r == 0 && b != 0)) {   // uniform: every thread read the same two words
-    if (tid == 0) {
-      auc[r] = qnan;
-      ap[r] = qnan;
-      n_pos[r] = -kBadPtr;
-      n_neg[r] = P;
-    }
-    return;
-  }
-  if (tid == 0) {
-    bad_range = INT32_MAX;
-    bad_repeat = INT32_MAX;
-    bad_finite = INT32_MAX;
-  }
   if (tid < kRmMaxCuts) grp[tid][0] = -1;
-  for (int32_t w = tid; w < cpad / 32; w += kRmThreads) is_pos[w] = 0u;
-  __syncthreads();
-  for (int32_t k = tid; k < P; k += kRmThreads) {
-    const int32_t c = pos_col[b + k];
-    if (c < 0 || c >= C) {
-      atomicMin(&bad_range, k);     // the first offending entry in list order
-      continue;
-    }
-    const uint32_t bit = 1u << (c & 31);
-    if (atomicOr(&is_pos[c >> 5], bit) & bit) atomicMin(&bad_repeat, c);
-  }
-  __syncthreads();
+  int32_t b, P;
   // first sort: the positives' keys
-  for (int32_t c = tid; c < cpad; c += kRmThreads) {
-    uint64_t k = kBehind;
-    if (c < C) {
-      const double x = row[c];
-      if (!finite_bits((uint64_t)__double_as_longlong(x))) atomicMin(&bad_finite, c);
-      else if ((is_pos[c >> 5] >> (c & 31)) & 1u) k = score_key(x);
-    }
-    key[c] = k;
-  }
-  __syncthreads();
-  const int32_t N = C - P;
-  if (bad_range != INT32_MAX || bad_repeat != INT32_MAX || bad_finite != INT32_MAX || P == 0 || N == 0) {
-    if (tid == 0) {
+  const bool has_list = row_positives(pos_ptr, r, C, tid, n_pos, n_neg, b, P);
+  if (!has_list || !mark_and_fill<kRmThreads, true>(C, cpad, row, pos_col + b, P, tid, key, is_pos, &n_pos[r], &n_neg[r])) {
+    if (tid == 0) {                 // refused, or one class
       auc[r] = qnan;
       ap[r] = qnan;
-      if (bad_range != INT32_MAX) {
-        n_pos[r] = -kColRange;
-        n_neg[r] = pos_col[b + bad_range];
-      } else if (bad_repeat != INT32_MAX) {
-        n_pos[r] = -kColRepeat;
-        n_neg[r] = bad_repeat;
-      } else if (bad_finite != INT32_MAX) {
-        n_pos[r] = -kNonFinite;
-        n_neg[r] = bad_finite;
-      } else {
-        n_pos[r] = P;
-        n_neg[r] = N;
-      }
     }
-    if (tid < cuts.nk) hits[(int64_t)r * cuts.nk + tid] = qnan;
-    return;
+    if (has_list && tid < cuts.nk) hits[(int64_t)r * cuts.nk + tid] = qnan;
+    return;                         // uniform: both answers are the workgroup's
   }
-  sort_keys(key, cpad, tid);
+  const int32_t N = C - P;
+  sort_keys<kRmThreads>(key, cpad, tid);
   for (int32_t i = tid; i < P; i += kRmThreads) park[i] = key[i];
   __syncthreads();                  // the keys are read out of LDS before the second fill overwrites them
   // second sort: the negatives' keys, which stay in LDS
   for (int32_t c = tid; c < cpad; c += kRmThreads) {
     uint64_t k = kBehind;
-    if (c < C && !((is_pos[c >> 5] >> (c & 31)) & 1u)) k = score_key(row[c]);
+    if (c < C && !((is_pos[c >> 5] >> (c & 31)) & 1u)) k = order_key(row[c]);
     key[c] = k;
   }
   __syncthreads();
-  sort_keys(key, cpad, tid);        // its barriers also make the parked keys visible to the whole workgroup
+  sort_keys<kRmThreads>(key, cpad, tid);        // its barriers also make the parked keys visible to the whole workgroup
 
   unsigned long long twice_u = 0;
   double ap_sum = 0.0;
@@ -287,33 +189,12 @@ int gss_rank_metrics_rows(int32_t R, int32_t C, const double *scores, int64_t ld
               gss_rank_metrics_workspace_bytes(R, C));
   GSS_REQUIRE(((uintptr_t)workspace & 7) == 0, "rank_metrics_rows: the workspace must be 8-byte aligned");
   hipStream_t st = as_stream(stream);
-  const int32_t cpad = (int32_t)pow2_at_least(C);
+  const int32_t cpad = pow2_at_least(C);
   const size_t lds = (size_t)cpad * 8 + (size_t)cpad / 8;
   hipLaunchKernelGGL(rank_metrics_kernel, dim3(R), dim3(kRmThreads), lds_request(rank_metrics_kernel, lds), st, C, cpad, scores, ld, pos_ptr,
                      pos_col, cuts, auc, ap, hits, n_pos, n_neg, reinterpret_cast<uint64_t *>(workspace));
   GSS_LAUNCH_CHECK("rank_metrics_kernel");
-  // the refusals come back in the count words: -code in n_pos, the column in n_neg
-  int32_t *h = new (std::nothrow) int32_t[(size_t)2 * R];
-  if (!h) return fail(GSS_ENOMEM, "rank_metrics_rows: host status buffer of %d rows", R);
-  hipError_t e1 = hipMemcpyAsync(h, n_pos, (size_t)R * 4, hipMemcpyDeviceToHost, st);
-  hipError_t e2 = e1 == hipSuccess ? hipMemcpyAsync(h + R, n_neg, (size_t)R * 4, hipMemcpyDeviceToHost, st) : e1;
-  hipError_t e3 = e2 == hipSuccess ? hipStreamSynchronize(st) : e2;
-  int rc = GSS_OK;
-  if (e3 != hipSuccess) rc = fail(GSS_EHIP, "rank_metrics_rows: reading the row status failed: %s", hipGetErrorString(e3));
-  for (int32_t r = 0; rc == GSS_OK && r < R; ++r) {
-    const int32_t code = -h[r], col = h[R + r];
-    if (code == kBadPtr)
-      rc = fail(GSS_EINVAL, "rank_metrics_rows: row %d: pos_ptr is not a CSR row pointer (0 first, non-decreasing, at most C=%d per row; %d here)",
-                r, C, col);
-    else if (code == kColRange)
-      rc = fail(GSS_EINVAL, "rank_metrics_rows: row %d: pos_col %d is outside [0, %d)", r, col, C);
-    else if (code == kColRepeat)
-      rc = fail(GSS_EINVAL, "rank_metrics_rows: row %d: pos_col %d is repeated", r, col);
-    else if (code == kNonFinite)
-      rc = fail(GSS_EINVAL, "rank_metrics_rows: row %d, column %d: the score is NaN or infinite (roc_auc_score refuses it)", r, col);
-  }
-  delete[] h;
-  return rc;
+  return read_refusals("rank_metrics_rows", R, C, n_pos, n_neg, st);
 }
 
 }  // extern "C"

@@ -22,6 +22,7 @@ import os
 import re
 import sys
 import time
+import types
 import warnings
 
 import numpy as np
@@ -164,10 +165,9 @@ def format_metric_line(name, values):
 
 
 def _device_inputs(who, scores, pos_ptr, pos_col):
-    """the shape checks device_aucs and device_metrics share, on the host -> (scores, ptr, col, on_device)"""
+    """the shape checks device_aucs and device_metrics share, on the host -> (scores, ptr, col)"""
     import torch
-    on_device = isinstance(scores, torch.Tensor)
-    if on_device:
+    if isinstance(scores, torch.Tensor):
         if scores.dim() != 2 or scores.dtype != torch.float64 or not scores.is_cuda:
             raise PredictError(f"{who}: device scores must be an fp64 matrix [R, C] on the GPU")
         s = scores.contiguous()
@@ -179,7 +179,7 @@ def _device_inputs(who, scores, pos_ptr, pos_col):
         raise PredictError(f"{who}: scores {s.shape} and the positives' row pointer ({len(ptr)} entries over {len(col)}) disagree")
     if s.shape[1] > MAX_COLS:
         raise PredictError(f"{s.shape[1]} drugs per indication is above the limit of {MAX_COLS} (one workgroup sorts a row in LDS)")
-    return s, ptr, col, on_device
+    return s, ptr, col
 
 
 def check_cuts(who, ks):
@@ -192,70 +192,79 @@ def check_cuts(who, ks):
     return np.asarray(ks, dtype=np.int32)
 
 
+def _row_buffers(dev, scores, ptr, col, nk=None):
+    """what one launch of _launch_rows reads and writes, on device dev, under DeviceEvaluator's attribute names: the scores (a device
+    tensor stays where it is), the positives' CSR and gss_auc_rows' outputs; with nk, room for nk cut-offs, also those of
+    gss_rank_metrics_rows and its workspace, the sorted positives' parking space of csrc/rank_metrics.hip"""
+    import torch
+    R, C = scores.shape
+    b = types.SimpleNamespace()
+    b.d_scores = scores if isinstance(scores, torch.Tensor) else torch.from_numpy(scores).to(dev)
+    b.d_ptr = torch.from_numpy(ptr).to(dev)
+    b.d_col = torch.from_numpy(col if len(col) else np.zeros(1, np.int32)).to(dev)   # no positive anywhere: a word nothing reads, not a null pointer
+    b.d_auc = torch.empty(R, dtype=torch.float64, device=dev)
+    b.d_pos = torch.empty(R, dtype=torch.int32, device=dev)
+    b.d_neg = torch.empty(R, dtype=torch.int32, device=dev)
+    if nk is not None:
+        b.d_ap = torch.empty(R, dtype=torch.float64, device=dev)
+        b.d_hits = torch.empty(R * max(nk, 1), dtype=torch.float64, device=dev)
+        b.d_work = torch.empty(R * C, dtype=torch.int64, device=dev)
+    return b
+
+
+def _launch_rows(b, h_ks=None):
+    """gss_auc_rows on the buffers b (_row_buffers, or a DeviceEvaluator), or with the cut-offs h_ks (check_cuts) gss_rank_metrics_rows.
+    Both synchronise the stream; no CPU fallback"""
+    from . import _lib
+    lib = _lib.load()
+    R, C = b.d_scores.shape
+    rows = (R, C, _lib.ptr(b.d_scores), C, _lib.ptr(b.d_ptr), _lib.ptr(b.d_col))
+    counts = (_lib.ptr(b.d_pos), _lib.ptr(b.d_neg))
+    if h_ks is None:
+        _lib.check(lib.gss_auc_rows(*rows, _lib.ptr(b.d_auc), *counts, _lib.current_stream()), "gss_auc_rows")
+    else:
+        _lib.check(lib.gss_rank_metrics_rows(*rows, len(h_ks), h_ks.ctypes.data if len(h_ks) else None, _lib.ptr(b.d_auc), _lib.ptr(b.d_ap),
+                                             _lib.ptr(b.d_hits), *counts, _lib.ptr(b.d_work), b.d_work.numel() * 8, _lib.current_stream()),
+                   "gss_rank_metrics_rows")
+
+
+def _device_rows(who, scores, pos_ptr, pos_col, ks, timings):
+    """device_metrics, and with ks = None device_aucs: the checks on the host, the upload, the one launch -> host (auc, ap, hits, n_pos,
+    n_neg), ap and hits None without ks"""
+    import torch
+
+    from . import _lib
+    s, ptr, col = _device_inputs(who, scores, pos_ptr, pos_col)
+    h_ks = None if ks is None else check_cuts(who, ks)
+    R, nk = s.shape[0], 0 if ks is None else len(h_ks)
+    if R == 0:
+        return np.zeros(0), np.zeros(0), np.zeros((0, nk)), np.zeros(0, np.int32), np.zeros(0, np.int32)
+    t = {} if timings is None else timings
+    _lib.load()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    b = _row_buffers(torch.device("cuda"), s, ptr, col, None if ks is None else nk)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    _launch_rows(b, h_ks)
+    t["upload_s"], t["kernel_s"] = t1 - t0, time.perf_counter() - t1
+    ap, hits = (None, None) if ks is None else (b.d_ap.cpu().numpy(), b.d_hits[:R * nk].cpu().numpy().reshape(R, nk))
+    return b.d_auc.cpu().numpy(), ap, hits, b.d_pos.cpu().numpy(), b.d_neg.cpu().numpy()
+
+
 def device_metrics(scores, pos_ptr, pos_col, ks, timings=None):
     """device_aucs with average precision and the hits at every cut-off of ks beside the AUC, all in one launch (csrc/rank_metrics.hip):
     -> host (auc [R], ap [R], hits [R, len(ks)], n_pos [R], n_neg [R]); NaN in auc, ap and hits where a row has one class.  The AUCs are
     the bits device_aucs returns.  No CPU fallback; scores on the host or an fp64 device tensor; timings as device_aucs."""
-    import torch
-
-    from . import _lib
-    s, ptr, col, on_device = _device_inputs("device_metrics", scores, pos_ptr, pos_col)
-    h_ks = check_cuts("device_metrics", ks)
-    R, nk = s.shape[0], len(h_ks)
-    if R == 0:
-        return np.zeros(0), np.zeros(0), np.zeros((0, nk)), np.zeros(0, np.int32), np.zeros(0, np.int32)
-    t = {} if timings is None else timings
-    lib = _lib.load()
-    dev = torch.device("cuda")
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    d_s = s if on_device else torch.from_numpy(s).to(dev)
-    d_ptr = torch.from_numpy(ptr).to(dev)
-    d_col = torch.from_numpy(col if len(col) else np.zeros(1, np.int32)).to(dev)
-    auc = torch.empty(R, dtype=torch.float64, device=dev)
-    ap = torch.empty(R, dtype=torch.float64, device=dev)
-    hits = torch.empty(R, max(nk, 1), dtype=torch.float64, device=dev)
-    n_pos = torch.empty(R, dtype=torch.int32, device=dev)
-    n_neg = torch.empty(R, dtype=torch.int32, device=dev)
-    ws_bytes = lib.gss_rank_metrics_workspace_bytes(R, s.shape[1])
-    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    _lib.check(lib.gss_rank_metrics_rows(R, s.shape[1], _lib.ptr(d_s), s.shape[1], _lib.ptr(d_ptr), _lib.ptr(d_col), nk,
-                                         h_ks.ctypes.data if nk else None, _lib.ptr(auc), _lib.ptr(ap), _lib.ptr(hits), _lib.ptr(n_pos),
-                                         _lib.ptr(n_neg), _lib.ptr(ws), ws_bytes, _lib.current_stream()), "gss_rank_metrics_rows")   # synchronises
-    t["upload_s"], t["kernel_s"] = t1 - t0, time.perf_counter() - t1
-    return auc.cpu().numpy(), ap.cpu().numpy(), hits.cpu().numpy()[:, :nk], n_pos.cpu().numpy(), n_neg.cpu().numpy()
+    return _device_rows("device_metrics", scores, pos_ptr, pos_col, ks, timings)
 
 
 def device_aucs(scores, pos_ptr, pos_col, timings=None):
     """one device launch: host scores fp64 [R, C] and the positives as a CSR -> host (auc [R], n_pos [R], n_neg [R]); NaN AUC where a
     row has one class.  No CPU fallback.  timings: upload_s / kernel_s (host clock around synchronised work).  Scores that are already a
     device tensor (fp64 [R, C], the negated output of gss_profile_dist) go into the kernel where they are."""
-    import torch
-
-    from . import _lib
-    s, ptr, col, on_device = _device_inputs("device_aucs", scores, pos_ptr, pos_col)
-    R = s.shape[0]
-    if R == 0:
-        return np.zeros(0), np.zeros(0, np.int32), np.zeros(0, np.int32)
-    t = {} if timings is None else timings
-    lib = _lib.load()
-    dev = torch.device("cuda")
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    d_s = s if on_device else torch.from_numpy(s).to(dev)
-    d_ptr = torch.from_numpy(ptr).to(dev)
-    d_col = torch.from_numpy(col if len(col) else np.zeros(1, np.int32)).to(dev)
-    auc = torch.empty(R, dtype=torch.float64, device=dev)
-    n_pos = torch.empty(R, dtype=torch.int32, device=dev)
-    n_neg = torch.empty(R, dtype=torch.int32, device=dev)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    _lib.check(lib.gss_auc_rows(R, s.shape[1], _lib.ptr(d_s), s.shape[1], _lib.ptr(d_ptr), _lib.ptr(d_col), _lib.ptr(auc),
-                                _lib.ptr(n_pos), _lib.ptr(n_neg), _lib.current_stream()), "gss_auc_rows")   # synchronises the stream
-    t["upload_s"], t["kernel_s"] = t1 - t0, time.perf_counter() - t1
-    return auc.cpu().numpy(), n_pos.cpu().numpy(), n_neg.cpu().numpy()
+    auc, _, _, n_pos, n_neg = _device_rows("device_aucs", scores, pos_ptr, pos_col, None, timings)
+    return auc, n_pos, n_neg
 
 
 # ---- scores and labels ---------------------------------------------------------------------------------------------------------------
@@ -323,6 +332,18 @@ class Result:
         self.metric_lines = [format_metric_line(name, v[self.kept]) for name, v in self.metrics.items()]   # over the AUC line's indications
 
 
+def skipped_by_reason(inds, listed, n_pos, n_neg):
+    """the indications without an AUC, by reason: no positive (no row in the label table, or none of its listed drugs is a drug node) or
+    no negative"""
+    skipped = {"no_row": [], "no_known_drug": [], "all_positive": []}
+    for k, i in enumerate(inds):
+        if n_pos[k] == 0:
+            skipped["no_known_drug" if listed[i] else "no_row"].append(i)
+        elif n_neg[k] == 0:
+            skipped["all_positive"].append(i)
+    return skipped
+
+
 def skip_report(res, labels):
     sk = res.skipped
     total = sum(len(v) for v in sk.values())
@@ -380,13 +401,8 @@ def run(s, seed=0, per_indication=None, auc_source=device_aucs, timings=None, er
     else:
         auc, n_pos, n_neg = auc_source(scores, pos_ptr, pos_col)
     t["auc_s"] = time.perf_counter() - t2
-    skipped = {"no_row": [], "no_known_drug": [], "all_positive": []}
-    for k, i in enumerate(inds):
-        if n_pos[k] == 0:
-            skipped["no_known_drug" if listed[i] else "no_row"].append(i)
-        elif n_neg[k] == 0:
-            skipped["all_positive"].append(i)
-    res = Result(inds, np.asarray(auc, np.float64), np.asarray(n_pos), np.asarray(n_neg), skipped, unknown, drugs, scores, ap, values)
+    res = Result(inds, np.asarray(auc, np.float64), np.asarray(n_pos), np.asarray(n_neg), skipped_by_reason(inds, listed, n_pos, n_neg), unknown,
+                 drugs, scores, ap, values)
     for line in skip_report(res, s.labels):
         print(line, file=err)
     if not res.kept:
@@ -444,16 +460,8 @@ class DeviceEvaluator:
         dev = torch.device("cuda") if device is None else torch.device(device)
         R, C = len(self.rows), len(self.cols)
         self.d_rows, self.d_cols = torch.from_numpy(self.rows).to(dev), torch.from_numpy(self.cols).to(dev)
-        self.d_ptr = torch.from_numpy(self.pos_ptr).to(dev)
-        self.d_col = torch.from_numpy(self.pos_col if len(self.pos_col) else np.zeros(1, np.int32)).to(dev)
-        self.d_scores = torch.empty(R, C, dtype=torch.float64, device=dev)
-        self.d_auc = torch.empty(R, dtype=torch.float64, device=dev)
-        self.d_pos = torch.empty(R, dtype=torch.int32, device=dev)
-        self.d_neg = torch.empty(R, dtype=torch.int32, device=dev)
-        # score(metrics=...): average precision, hits at up to MAX_CUTS cut-offs and the sorted positives' parking space of csrc/rank_metrics.hip
-        self.d_ap = torch.empty(R, dtype=torch.float64, device=dev)
-        self.d_hits = torch.empty(R * MAX_CUTS, dtype=torch.float64, device=dev)
-        self.d_work = torch.empty(R * C, dtype=torch.int64, device=dev)
+        # the buffers of _launch_rows as attributes of the evaluator: score() launches on itself.  Room for score(metrics=...) at MAX_CUTS cut-offs
+        vars(self).update(vars(_row_buffers(dev, torch.empty(R, C, dtype=torch.float64, device=dev), self.pos_ptr, self.pos_col, MAX_CUTS)))
         self.device = self.d_rows.device      # with its index, as a tensor's device has it
 
     def check_tensor(self, emb, d=None):
@@ -498,14 +506,7 @@ class DeviceEvaluator:
             _lib.check(lib.gss_embedding_scores(self.n, d, _lib.ptr(emb), emb.stride(0), R, _lib.ptr(self.d_rows), C, _lib.ptr(self.d_cols),
                                                 int(self.normalize), _lib.ptr(self.d_scores), C, _lib.current_stream()), "gss_embedding_scores")
             t1 = time.perf_counter()
-            if metrics:
-                _lib.check(lib.gss_rank_metrics_rows(R, C, _lib.ptr(self.d_scores), C, _lib.ptr(self.d_ptr), _lib.ptr(self.d_col), len(ks),
-                                                     h_ks.ctypes.data if len(ks) else None, _lib.ptr(self.d_auc), _lib.ptr(self.d_ap),
-                                                     _lib.ptr(self.d_hits), _lib.ptr(self.d_pos), _lib.ptr(self.d_neg), _lib.ptr(self.d_work),
-                                                     self.d_work.numel() * 8, _lib.current_stream()), "gss_rank_metrics_rows")
-            else:
-                _lib.check(lib.gss_auc_rows(R, C, _lib.ptr(self.d_scores), C, _lib.ptr(self.d_ptr), _lib.ptr(self.d_col), _lib.ptr(self.d_auc),
-                                            _lib.ptr(self.d_pos), _lib.ptr(self.d_neg), _lib.current_stream()), "gss_auc_rows")   # both synchronise
+            _launch_rows(self, h_ks if metrics else None)
         t2 = time.perf_counter()
         auc, n_pos, n_neg = self.d_auc.cpu().numpy(), self.d_pos.cpu().numpy(), self.d_neg.cpu().numpy()
         ap = values = None
@@ -513,13 +514,8 @@ class DeviceEvaluator:
             ap = self.d_ap.cpu().numpy()
             hits = self.d_hits[:R * len(ks)].cpu().numpy().reshape(R, len(ks))
             values = metric_arrays(metrics, ks, auc, ap, hits, n_pos)
-        skipped = {"no_row": [], "no_known_drug": [], "all_positive": []}
-        for k, i in enumerate(self.indications):
-            if n_pos[k] == 0:
-                skipped["no_known_drug" if self.listed[i] else "no_row"].append(i)
-            elif n_neg[k] == 0:
-                skipped["all_positive"].append(i)
-        res = Result(self.indications, auc, n_pos, n_neg, skipped, self.unknown_pairs, self.drugs, self.d_scores, ap, values)
+        res = Result(self.indications, auc, n_pos, n_neg, skipped_by_reason(self.indications, self.listed, n_pos, n_neg), self.unknown_pairs,
+                     self.drugs, self.d_scores, ap, values)
         t["scores_s"], t["auc_s"], t["host_s"] = t1 - t0, t2 - t1, time.perf_counter() - t2
         return res
 

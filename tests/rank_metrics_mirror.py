@@ -86,3 +86,28 @@ def csr(rows):
     ptr[1:] = np.cumsum([len(r) for r in rows])
     col = np.concatenate([np.asarray(r, np.int32) for r in rows] + [np.zeros(0, np.int32)])
     return ptr, col.astype(np.int32)
+
+
+# ---- one ordering behind the three entry points: the AUC out of average-tie ranks ------------------------------------------------------
+
+RANK_IDENTITY_WIDTHS = (2, 63, 64, 65, 200)
+
+
+def tied_rows(C, R=5):
+    """seeded scores [R, C] on a handful of levels with both signed zeros, and per row 1 .. C - 1 positive columns"""
+    rng = np.random.RandomState(100 + C)
+    s = np.round(rng.randn(R, C), 0) * 0.5
+    s[s == 0] = np.where(rng.rand(int((s == 0).sum())) < 0.5, -0.0, 0.0)
+    s[0, 0], s[R - 1, C - 1] = 0.0, -0.0
+    assert np.any(np.signbit(s) & (s == 0)) and np.any(~np.signbit(s) & (s == 0))
+    return s, [np.sort(rng.choice(C, rng.randint(1, C), replace=False)) for _ in range(R)]
+
+
+def auc_from_ranks(ranks, cols):
+    """ranks [C]: the average-tie ranks (1 = lowest) of one row's C scores, cols: its P positives.  2 r - 1 = 2 below + tied counts the
+    whole row; the positives among themselves make P^2 of it, so 2 U = sum over positives of (2 r_i - 1) - P^2, exact in int64, and
+    AUC = 2 U / (2 P N): the kernels' one division"""
+    twice = np.asarray(ranks, np.float64)[cols] * 2 - 1
+    assert np.all(twice == np.round(twice))
+    P, N = len(cols), len(ranks) - len(cols)
+    return float(int(twice.astype(np.int64).sum()) - P * P) / (2.0 * float(P) * float(N))

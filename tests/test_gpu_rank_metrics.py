@@ -143,6 +143,27 @@ def test_heavy_ties_and_signed_zeros_with_cuts_inside_and_at_the_end_of_groups()
     print(f"cuts inside a group: {inside}, on a group's last member: {last + 1}")
 
 
+@pytest.mark.parametrize("C", M.RANK_IDENTITY_WIDTHS)
+def test_the_three_entry_points_share_one_ordering(C):
+    """gss_profile_rank on the transposed scores, the identity of M.auc_from_ranks on its ranks: the bits of auc from gss_auc_rows and from
+    gss_rank_metrics_rows.  Each kernel is otherwise compared with its own mirror only"""
+    s, rows = M.tied_rows(C)
+    R = len(rows)
+    lib = _lib.load()
+    x = torch.from_numpy(s).cuda().t().contiguous()                            # [C, R]: row r of the scores is profile column r
+    ranks = torch.empty(C, R, dtype=torch.float64, device="cuda")
+    need = int(lib.gss_profile_rank_workspace_bytes(C, R))
+    ws = torch.empty((need + 7) // 8, dtype=torch.int64, device="cuda")
+    rc = lib.gss_profile_rank(C, _lib.ptr(x), R, R, None, _lib.ptr(ranks), R, _lib.ptr(ws), need, _lib.current_stream())
+    assert rc == 0, lib.gss_last_error()
+    torch.cuda.synchronize()
+    ranks = ranks.cpu().numpy()
+    got = np.array([M.auc_from_ranks(ranks[:, r], rows[r]) for r in range(R)])
+    rc, auc, *_, msg = device_metrics(s, rows, ())
+    assert rc == 0, msg
+    assert np.array_equal(_bits(got), _bits(device_aucs(s, rows))) and np.array_equal(_bits(got), _bits(auc)), (got, auc)
+
+
 def test_single_positive_and_single_negative():
     rng = np.random.RandomState(2)
     s = rng.randn(8, 1661)

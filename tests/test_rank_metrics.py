@@ -101,6 +101,18 @@ def test_mirror_one_class_rows_and_auc_column():
     assert ap[0] == 0.75 and list(hits[0]) == [1.0, 1.5, 2.0]
 
 
+@pytest.mark.parametrize("C", M.RANK_IDENTITY_WIDTHS)
+def test_auc_is_the_positives_average_tie_ranks(C):
+    """the rank mirror (profile_rank_mirror.mirror_rank) and the AUC mirror state one ordering: the identity of M.auc_from_ranks, bit for bit"""
+    import profile_rank_mirror as PR
+    s, rows = M.tied_rows(C)
+    ptr, col = M.csr(rows)
+    want, n_pos, n_neg = F.mirror_aucs(s, ptr, col)
+    assert np.all(n_pos >= 1) and np.all(n_neg >= 1)
+    got = np.array([M.auc_from_ranks(PR.mirror_rank(s[r]), rows[r]) for r in range(len(rows))])
+    assert np.array_equal(got.view(np.uint64), want.view(np.uint64)), (got, want)
+
+
 def test_metric_name_parser():
     from gcn_drug_repurposing_amd import evaluate
     from gcn_drug_repurposing_amd.predict import PredictError

@@ -24,7 +24,7 @@ def main():
     import torch
     from gcn_drug_repurposing_amd import _lib, consumer, evaluate, synth
     out = {"graph": "synth.standin_tables(seed=1) + synth.standin_drug_indications()", "method": "node2vec, seeded N(0,1) d=128",
-           "source_hash": _lib.source_hashes()["auc.hip"], "reps": a.reps}
+           "source_hash": {k: _lib.source_hashes()[k] for k in ("auc.hip", "rank_keys.h")}, "reps": a.reps}
     with tempfile.TemporaryDirectory() as tmp:
         d = os.path.join(tmp, "data")
         os.makedirs(d)

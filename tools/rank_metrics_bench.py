@@ -27,7 +27,7 @@ def main():
     from gcn_drug_repurposing_amd.msi import COMPONENTS, MsiGraph
     hashes = _lib.source_hashes()
     out = {"graph": "synth.standin_tables(seed=1) + synth.standin_drug_indications()", "scores": "seeded N(0,1) d=128 inner products",
-           "ks": list(KS), "source_hash": {k: hashes[k] for k in ("rank_metrics.hip", "auc.hip")}, "reps": a.reps}
+           "ks": list(KS), "source_hash": {k: hashes[k] for k in ("rank_metrics.hip", "auc.hip", "rank_keys.h")}, "reps": a.reps}
     with tempfile.TemporaryDirectory() as tmp:
         for name, rows in synth.standin_tables(seed=1).items():
             with open(os.path.join(tmp, name + ".tsv"), "w") as f:
