@@ -13,7 +13,9 @@ per start node.
 compare_profiles: the comparison of two profiles the method rests on (multiscale/README.md, overview (c)), which the reference never makes: a
 pairwise distance between columns of the profile matrix (gss_profile_dist, csrc/profile_dist.hip), on the tensor PprEngine.run returned or on
 profiles loaded from a directory.  rank_profiles: the average-tie ranks of the nodes within each profile (gss_profile_rank,
-csrc/profile_rank.hip); the "spearman" distance is the correlation distance of those ranks."""
+csrc/profile_rank.hip); the "spearman" distance is the correlation distance of those ranks.  top_nodes: the k highest nodes of each
+profile per node group -- the proteins and the biological functions a treatment runs through -- and top_overlap: how many of them two
+profiles share (gss_profile_topk, gss_topk_overlap, csrc/profile_topk.hip)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -263,6 +265,138 @@ def rank_profiles(profiles, cols=None, device="cuda"):
     if x.shape[0] < 1:
         raise ValueError("rank_profiles: the profiles are empty")
     return _rank_columns(x, c)
+
+
+MAX_TOP, MAX_GROUPS = 1024, 8   # gss_profile_topk's limits on k and G
+
+
+def _profile_source(profiles, cols, who):
+    """the three kinds of `profiles` rank_profiles accepts, resolved on the host -> (N, column list int32, upload), where upload(dev) gives
+    the device fp64 matrix [N][width] with unit column stride (a device tensor is used in place).  Nothing here touches the GPU"""
+    import torch
+    if isinstance(profiles, torch.Tensor):
+        x = profiles
+        if (x.dim() != 2 or x.dtype != torch.float64 or not x.is_cuda or x.shape[1] < 1 or (x.shape[1] > 1 and x.stride(1) != 1)
+                or (x.shape[0] > 1 and x.stride(0) < x.shape[1])):
+            raise ValueError(f"{who}: a profile tensor must be a device fp64 matrix [N][columns] with unit column stride and "
+                             "a row stride of at least its width")
+        return x.shape[0], _column_list("column", cols, x.shape[1], who=who), lambda dev: x
+    if isinstance(profiles, dict):
+        if cols is None:
+            raise ValueError(f"{who}: cols must name the profiles of a dict")
+        keys = list(dict.fromkeys(cols))
+        c = _column_list("column", cols, len(keys), {k: i for i, k in enumerate(keys) if k in profiles}, who=who)
+        host = [np.asarray(profiles[k], dtype=np.float64).reshape(-1) for k in keys]
+        if len({len(v) for v in host}) > 1:
+            raise ValueError(f"{who}: the profiles differ in length")
+        if not host:
+            raise ValueError(f"{who}: no profile is named")
+        return len(host[0]), c, lambda dev: torch.from_numpy(np.stack(host)).to(dev).t().contiguous()
+    host = np.ascontiguousarray(profiles, dtype=np.float64)
+    if host.ndim != 2:
+        raise ValueError(f"{who}: a host profile array must be [K][N], not {host.shape}")
+    return host.shape[1], _column_list("column", cols, host.shape[0], who=who), lambda dev: torch.from_numpy(host).to(dev).t().contiguous()
+
+
+def top_nodes(profiles, cols=None, k=20, groups=None, n_groups=None, device="cuda"):
+    """the k highest nodes of diffusion profiles, per node group -> device tensors (idx int32 [len(cols)][G][k], val fp64 [len(cols)][G][k],
+    cnt int32 [len(cols)][G]): for profile cols[j] and group g, idx[j][g][:cnt[j][g]] are the group's nodes in the order of
+    np.argsort(-profile[members], kind="stable")[:k] -- descending value, ties by the smaller node index, exactly -- and val their values;
+    the slots from cnt on hold -1 and NaN, and a profile with a NaN among the group's nodes has cnt = -1 and nothing listed
+    (gss_profile_topk).  `profiles` is what rank_profiles accepts: the device tensor x [N][kpad] (used in place; cols are column indices), a
+    host array [K][N] (cols index its rows) or a {name: vector} dict (cols are names); cols may repeat and come in any order, None means
+    every profile (not for a dict).  `groups`: a host or device integer array [N] with each node's group in [-1, G), -1 = never listed
+    (msi.py's node types, for "the proteins and the biological functions"); None = one group of all nodes.  G = n_groups, or the highest
+    group + 1.  k <= 1024, G <= 8.  No CPU fallback."""
+    import torch
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.GssError("the top nodes of a profile are selected on the GPU only (no CPU fallback)")
+    if not isinstance(k, (int, np.integer)) or not 1 <= k <= MAX_TOP:
+        raise ValueError(f"top_nodes: k={k!r} is outside [1, {MAX_TOP}]")
+    n, c, upload = _profile_source(profiles, cols, "top_nodes")
+    if n < 1:
+        raise ValueError("top_nodes: the profiles are empty")
+    grp = None
+    if groups is None:
+        G = 1 if n_groups is None else int(n_groups)
+        if G != 1:
+            raise ValueError(f"top_nodes: n_groups={n_groups!r} needs a groups array (without one every node is in group 0)")
+    else:
+        on_device = isinstance(groups, torch.Tensor) and groups.is_cuda
+        grp = groups if isinstance(groups, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(groups))
+        if grp.dim() != 1 or grp.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+            raise ValueError(f"top_nodes: groups must be an integer array [N], not {tuple(grp.shape)} of {grp.dtype}")
+        if grp.shape[0] != n:
+            raise ValueError(f"top_nodes: groups has {grp.shape[0]} entries, the profiles {n} nodes")
+        if n_groups is not None:
+            G = int(n_groups)
+        elif on_device:
+            G = max(1, int(grp.max()) + 1)
+        else:
+            G = max(1, int(grp.numpy().max()) + 1)
+        if not 1 <= G <= MAX_GROUPS:
+            raise ValueError(f"top_nodes: G={G} groups is outside [1, {MAX_GROUPS}]")
+        bad = torch.nonzero((grp < -1) | (grp >= G))
+        if bad.numel():
+            at = int(bad[0])
+            raise ValueError(f"top_nodes: groups[{at}] = {int(grp[at])} is outside [-1, G={G})")
+    nc = len(c)
+    x = upload(dev)
+    idx = torch.empty(nc, G, k, dtype=torch.int32, device=x.device)
+    val = torch.empty(nc, G, k, dtype=torch.float64, device=x.device)
+    cnt = torch.empty(nc, G, dtype=torch.int32, device=x.device)
+    if nc == 0:
+        return idx, val, cnt
+    lib = _lib.load()
+    with torch.cuda.device(x.device):
+        need = int(lib.gss_profile_topk_workspace_bytes(n, nc, G, int(k)))
+        ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=x.device)
+        lst = None if np.array_equal(c, np.arange(nc)) else torch.from_numpy(np.ascontiguousarray(c, dtype=np.int32)).to(x.device)
+        d_grp = None if grp is None else grp.to(device=x.device, dtype=torch.int32).contiguous()
+        _lib.check(lib.gss_profile_topk(n, x.data_ptr(), _row_stride(x), nc, _lib.ptr(lst), G, _lib.ptr(d_grp), int(k), idx.data_ptr(),
+                                        val.data_ptr(), cnt.data_ptr(), ws.data_ptr(), need, _lib.current_stream()), "gss_profile_topk")
+    return idx, val, cnt
+
+
+def top_overlap(idx, cnt, a, b):
+    """how many nodes two selections of top_nodes share, per group -> device tensor int32 [T][G]: entry (t, g) = the number of node indices
+    in both idx[a[t]][g][:cnt] and idx[b[t]][g][:cnt] (len(np.intersect1d(...))); -1 where either side has cnt = -1.  idx, cnt: top_nodes'
+    device tensors [S][G][k] and [S][G]; a, b: integer lists of T selection numbers in [0, S), on the host or the device; pairs may repeat
+    (gss_topk_overlap).  No CPU fallback."""
+    import torch
+    if (not isinstance(idx, torch.Tensor) or not isinstance(cnt, torch.Tensor) or idx.dim() != 3 or cnt.dim() != 2 or idx.dtype != torch.int32
+            or cnt.dtype != torch.int32 or tuple(cnt.shape) != tuple(idx.shape[:2])):
+        raise ValueError("top_overlap: idx and cnt must be top_nodes' int32 tensors [S][G][k] and [S][G]")
+    S, G, k = idx.shape
+    if not 1 <= k <= MAX_TOP:
+        raise ValueError(f"top_overlap: k={k} is outside [1, {MAX_TOP}]")
+    if not 1 <= G <= MAX_GROUPS:
+        raise ValueError(f"top_overlap: G={G} groups is outside [1, {MAX_GROUPS}]")
+    lists = []
+    for name, v in (("a", a), ("b", b)):
+        if not (isinstance(v, torch.Tensor) and v.is_cuda):
+            h = np.asarray(v, dtype=np.int64).reshape(-1)
+            bad = np.flatnonzero((h < 0) | (h >= S))
+            if len(bad):
+                raise ValueError(f"top_overlap: {name}[{int(bad[0])}] = {int(h[bad[0]])} is outside [0, S={S})")
+            v = torch.from_numpy(h.astype(np.int32))
+        lists.append(v)
+    if lists[0].numel() != lists[1].numel():
+        raise ValueError(f"top_overlap: a lists {lists[0].numel()} selections and b {lists[1].numel()}")
+    if not idx.is_cuda or not cnt.is_cuda:
+        raise _lib.GssError("top_overlap: the selections are compared on the GPU only (no CPU fallback)")
+    T = lists[0].numel()
+    shared = torch.empty(T, G, dtype=torch.int32, device=idx.device)
+    if T == 0:
+        return shared
+    lib = _lib.load()
+    with torch.cuda.device(idx.device):
+        da, db = (v.to(device=idx.device, dtype=torch.int32).contiguous().view(-1) for v in lists)
+        idx, cnt = idx.contiguous(), cnt.contiguous()
+        _lib.check(lib.gss_topk_overlap(S, G, k, idx.data_ptr(), cnt.data_ptr(), T, da.data_ptr(), db.data_ptr(), shared.data_ptr(),
+                                        _lib.current_stream()), "gss_topk_overlap")
+    return shared
 
 
 def compare_profiles(profiles, rows, cols, metric, device="cuda"):

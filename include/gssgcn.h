@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define GSS_ABI_VERSION 18  /* 18: exact average-tie ranks of listed profile columns, the transform behind the spearman distance -- gss_profile_rank, gss_profile_rank_workspace_bytes; 17: gene knock-outs per column of the diffusion profiles -- gss_ppr_set_knockout; distances of listed column pairs of the profile matrix -- gss_profile_dist_pairs, gss_profile_dist_pairs_workspace_bytes; 16: ROC-AUC, average precision and hits@k per row in one launch -- gss_rank_metrics_rows, gss_rank_metrics_workspace_bytes; 15: entry points for tests of the row-sparse SpMM modes -- gss_spmm_bwd1_sparse_ex, gss_spmm_bwd2_sparse_res, gss_spmm_filtered, gss_mark_rows_and_neighbours, gss_batch_bits, gss_bits_fill; 14:indication x drug scores from the embedding tensor -- gss_embedding_scores; 13: pairwise distances between diffusion profiles -- gss_profile_dist; 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
+#define GSS_ABI_VERSION 19  /* 19: exact typed top-k selection of listed profile columns and set overlap between selections -- gss_profile_topk, gss_profile_topk_workspace_bytes, gss_topk_overlap; 18: exact average-tie ranks of listed profile columns, the transform behind the spearman distance -- gss_profile_rank, gss_profile_rank_workspace_bytes; 17: gene knock-outs per column of the diffusion profiles -- gss_ppr_set_knockout; distances of listed column pairs of the profile matrix -- gss_profile_dist_pairs, gss_profile_dist_pairs_workspace_bytes; 16: ROC-AUC, average precision and hits@k per row in one launch -- gss_rank_metrics_rows, gss_rank_metrics_workspace_bytes; 15: entry points for tests of the row-sparse SpMM modes -- gss_spmm_bwd1_sparse_ex, gss_spmm_bwd2_sparse_res, gss_spmm_filtered, gss_mark_rows_and_neighbours, gss_batch_bits, gss_bits_fill; 14:indication x drug scores from the embedding tensor -- gss_embedding_scores; 13: pairwise distances between diffusion profiles -- gss_profile_dist; 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
 
 #define GSS_OK 0
 #define GSS_EINVAL (-22)   /* bad argument (shape, null pointer, unsupported d) */
@@ -558,6 +558,41 @@ int gss_profile_dist_pairs(int32_t n, const double *x, int64_t ld, int32_t T, co
 size_t gss_profile_rank_workspace_bytes(int32_t n, int32_t nc);
 int gss_profile_rank(int32_t n, const double *x, int64_t ld, int32_t nc, const int32_t *cols, double *r, int64_t ld_r, void *workspace,
                      size_t workspace_bytes, void *stream);
+
+/* gss_profile_topk: the k highest nodes of listed columns of the profile matrix, per node group -- "the proteins and biological functions" a
+ * treatment's profile runs through (multiscale/README.md).  x: device fp64 [n][ld], profile c = column c; cols: device int32 [nc], honoured as
+ * given (any order, repeats allowed; null = columns 0 .. nc - 1); group: device int32 [n], node i belongs to group[i] in [-1, G), -1 = never
+ * selected (null = every node in group 0, and G must be 1) -> idx: device int32 [nc][G][k], val: device fp64 [nc][G][k], cnt: device int32
+ * [nc][G].  For list position j (column c = cols[j]) and group g, with members = the nodes of g in ascending index:
+ *   idx[j][g][:cnt] = members[np.argsort(-x[members, c], kind="stable")[:k]],  cnt[j][g] = min(k, len(members)),  val = x[idx, c] bit for bit
+ * EXACTLY: descending value, ties by the smaller node index; -0.0 and +0.0 tie, +-inf are ordinary extremes, subnormals distinct values.
+ * Slots from cnt on hold idx = -1 and val = NaN.  A NaN among the group's own nodes in that column flags (j, g): cnt = -1, every idx = -1,
+ * every val = NaN; a NaN at a node of another group or of group -1 changes nothing.  The output of a (column, group) depends on that column's
+ * values and on group alone -- not on the list, the position in it, nc, ld or the other columns, bit for bit; every output word has one owner,
+ * the only atomics are integer counters in LDS.
+ * Kernel: per panel of 512 listed columns a transposing pass writes order-preserving uint64 keys [panel][n] (rank_keys.h); one workgroup
+ * per column then runs, for all G groups at once, an exact radix select (8-bit digits from the top, LDS histograms; a group stops as soon
+ * as its bucket is taken whole; ties at the k-th key are resolved by up to three more digit passes over the node index), collects the
+ * selected (key, index) pairs, bitonic-sorts them in LDS and reads the values back from x.
+ * workspace: the caller's, device, 8-byte aligned, at least gss_profile_topk_workspace_bytes(n, nc, G, k) = 256 + min(nc, 512) n 8 bytes
+ * (0 for arguments outside the limits).  Nothing is allocated inside.  nc = 0 is a no-op.  Refuses (GSS_EINVAL, by name in gss_last_error,
+ * outputs untouched): n outside [1, 2^24], k outside [1, 1024], G outside [1, 8], nc < 0, ld < 1, and with nc > 0 a null x, idx, val, cnt or
+ * workspace, a null group with G != 1, ld below nc where cols is null, a misaligned or too small workspace (naming the needed size), a cols
+ * entry outside [0, ld) and a group entry outside [-1, G) (by position and value: one check launch and one synchronisation of the stream,
+ * only where cols or group is given). */
+size_t gss_profile_topk_workspace_bytes(int32_t n, int32_t nc, int32_t G, int32_t k);
+int gss_profile_topk(int32_t n, const double *x, int64_t ld, int32_t nc, const int32_t *cols, int32_t G, const int32_t *group, int32_t k,
+                     int32_t *idx, double *val, int32_t *cnt, void *workspace, size_t workspace_bytes, void *stream);
+
+/* gss_topk_overlap: how many nodes two selections share, per group.  idx [S][G][k], cnt [S][G]: gss_profile_topk's outputs for S
+ * selections; a, b: device int32 [T], selection numbers in [0, S) -> shared: device int32 [T][G], shared[t][g] = the number of node indices
+ * in both idx[a[t]][g][:cnt] and idx[b[t]][g][:cnt] (len(np.intersect1d(...))), or -1 where either side has cnt = -1.  Pairs may repeat; an
+ * entry depends on its own pair only.  One workgroup per (t, g): side a sorted in LDS, side b searched in it.  T = 0 is a no-op.  Refuses
+ * (GSS_EINVAL, by name): S < 1, T < 0, k outside [1, 1024], G outside [1, 8], a null idx, cnt, a, b or shared, and an a or b entry outside
+ * [0, S) (by list, position and value; a status word is allocated and freed inside, and the stream is synchronised once); shared is then
+ * untouched. */
+int gss_topk_overlap(int32_t S, int32_t G, int32_t k, const int32_t *idx, const int32_t *cnt, int32_t T, const int32_t *a, const int32_t *b,
+                     int32_t *shared, void *stream);
 
 /* ---- inner-product scores between listed embedding rows (predict_drug.py:52-66: sklearn.preprocessing.normalize, then np.matmul)
  * gss_embedding_scores: device fp32 emb [n][ld], ld >= d (a plan's embedding tensor with its zero padding); device int32 index lists rows

@@ -1,0 +1,145 @@
+#!/usr/bin/env python3
+"""Three routes to "the 20 proteins and the 20 biological functions every profile ranks highest" on the diffusion profiles of the
+29,960-node whole-graph stand-in (1,661 drugs, 841 indications incl. NodeCovid: 2,502 columns, left on the device by PprEngine.run), G = 2
+groups (protein, functional pathway), k = 20:
+  1. gss_profile_topk on all columns (null list, the caller's workspace and outputs): device events around the entry point;
+  2. gss_profile_rank on the same columns -- the only device route to a profile's highest nodes before gss_profile_topk -- plus the download
+     of its [N][2,502] fp64 rank matrix (what the host then has to select from): device events around the kernel, wall clock around the copy;
+  3. host np.argpartition over the downloaded profiles, per column and group (one core), with the download of the profile matrix.
+Median of --reps timed calls after two warm-up calls.  Route 1's selection is checked against route 3's on every column (as sets: argpartition
+does not order).  Also times gss_topk_overlap on the 1,661 x 841 drug-indication pairs.
+Writes profiles/profile_topk_bench.json (or --out).   python tools/profile_topk_bench.py [--reps 10] [--k 20]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def timed(fn, reps):
+    import torch
+    ms = []
+    for r in range(reps + 2):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        if r >= 2:
+            ms.append(e0.elapsed_time(e1))
+    return {"ms_median": float(np.median(ms)), "ms_min": float(min(ms)), "ms_max": float(max(ms))}
+
+
+def walled(fn, reps):
+    import torch
+    ms = []
+    for r in range(reps + 2):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = fn()
+        torch.cuda.synchronize()
+        if r >= 2:
+            ms.append((time.perf_counter() - t0) * 1e3)
+    return {"ms_median": float(np.median(ms)), "ms_min": float(min(ms)), "ms_max": float(max(ms))}, res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--k", type=int, default=20)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "profile_topk_bench.json"))
+    a = ap.parse_args()
+    import scipy.sparse as sp
+    import torch
+    from gcn_drug_repurposing_amd import _lib, synth
+    from gcn_drug_repurposing_amd.diffusion import PprEngine, PprProblem
+    hashes = _lib.source_hashes()
+    lib = _lib.load()
+    assert lib.gss_source_hash(b"profile_topk.hip").decode() == hashes["profile_topk.hip"], "the library was not built from this tree"
+    out = {"graph": "synth.whole_graph_standin(seed=1)", "source_hash": {k: hashes[k] for k in ("profile_topk.hip", "profile_rank.hip", "rank_keys.h", "*")},
+           "reps": a.reps, "k": a.k, "groups": ["protein", "functional_pathway"]}
+    adj, ntype, _ = synth.whole_graph_standin(seed=1)
+    m0 = sp.csr_matrix(adj, dtype=np.float64)
+    starts = np.flatnonzero(ntype <= 1)
+    prot = {int(s): m0.indices[m0.indptr[s]:m0.indptr[s + 1]].tolist() for s in starts}
+    eng = PprEngine(PprProblem(m0, starts, prot))
+    x, _ = eng.run(0.8595436247434408, 1e-6, 1000)
+    torch.cuda.synchronize()
+    n, nc, ld, G, k = x.shape[0], len(starts), int(x.stride(0)), 2, a.k
+    group = np.where(ntype == 2, 0, np.where(ntype == 3, 1, -1)).astype(np.int32)
+    d_group = torch.from_numpy(group).cuda()
+    need = int(lib.gss_profile_topk_workspace_bytes(n, nc, G, k))
+    out.update(nodes=int(n), columns=int(nc), ld=ld, members=[int((group == g).sum()) for g in range(G)], workspace_bytes=need)
+    idx = torch.empty(nc, G, k, dtype=torch.int32, device="cuda")
+    val = torch.empty(nc, G, k, dtype=torch.float64, device="cuda")
+    cnt = torch.empty(nc, G, dtype=torch.int32, device="cuda")
+    ws = torch.empty((need + 7) // 8, dtype=torch.float64, device="cuda")
+
+    def topk_all():
+        _lib.check(lib.gss_profile_topk(n, x.data_ptr(), ld, nc, None, G, d_group.data_ptr(), k, idx.data_ptr(), val.data_ptr(), cnt.data_ptr(),
+                                        ws.data_ptr(), need, _lib.current_stream()), "gss_profile_topk")
+    out["1_gss_profile_topk"] = dict(timed(topk_all, a.reps),
+                                     note="device events around the entry point: null column list, the group check launch and its one "
+                                          "synchronisation, five panels of at most 512 columns, two launches each")
+    print("1 gss_profile_topk", json.dumps(out["1_gss_profile_topk"]), flush=True)
+    h_idx, h_cnt = idx.cpu().numpy(), cnt.cpu().numpy()
+
+    need_r = int(lib.gss_profile_rank_workspace_bytes(n, nc))
+    r = torch.empty(n, nc, dtype=torch.float64, device="cuda")
+    ws_r = torch.empty((need_r + 7) // 8, dtype=torch.float64, device="cuda")
+
+    def rank_all():
+        _lib.check(lib.gss_profile_rank(n, x.data_ptr(), ld, nc, None, r.data_ptr(), nc, ws_r.data_ptr(), need_r, _lib.current_stream()),
+                   "gss_profile_rank")
+    kernel = timed(rank_all, a.reps)
+    pinned = torch.empty(n, nc, dtype=torch.float64).pin_memory()
+    copy, _ = walled(lambda: pinned.copy_(r, non_blocking=True), a.reps)
+    out["2_gss_profile_rank_and_download"] = {"kernel": kernel, "download_pinned": copy, "bytes": int(n) * int(nc) * 8,
+                                              "ms_median_sum": kernel["ms_median"] + copy["ms_median"],
+                                              "note": "the rank matrix [N][columns] fp64 into pinned host memory; the host's selection from it is not included"}
+    print("2 gss_profile_rank + download", json.dumps(out["2_gss_profile_rank_and_download"]), flush=True)
+    del r, ws_r
+
+    def host_route():
+        host = pinned.copy_(x[:, :nc], non_blocking=False).numpy()
+        sel = []
+        for g in range(G):
+            m = np.flatnonzero(group == g)
+            part = np.argpartition(-host[m], k - 1, axis=0)[:k]                  # [k][columns], unordered
+            sel.append(m[part])
+        return sel
+    t_host, sel = walled(host_route, max(1, min(a.reps, 3)))
+    out["3_host_argpartition"] = dict(t_host, note="download of the profile matrix into pinned memory + np.argpartition along the node axis per group, one core; "
+                                                   "unordered selections")
+    print("3 host argpartition", json.dumps(out["3_host_argpartition"]), flush=True)
+    agree = all(set(h_idx[c, g, :h_cnt[c, g]].tolist()) == set(sel[g][:, c].tolist()) for c in range(nc) for g in range(G))
+    host = pinned.numpy()
+    ties = sum(1 for c in range(0, nc, 50) for g in range(G) if len(np.unique(host[h_idx[c, g], c])) < k)
+    out["selection_equals_argpartition_as_sets"] = bool(agree)
+    out["sampled_selections_with_tied_values"] = int(ties)
+    print("route 1 == route 3 as sets:", agree, "(ties in sampled selections:", ties, ")", flush=True)
+
+    drugs, inds = np.flatnonzero(ntype[starts] == 0), np.flatnonzero(ntype[starts] == 1)
+    pa = torch.from_numpy(np.repeat(drugs, len(inds)).astype(np.int32)).cuda()
+    pb = torch.from_numpy(np.tile(inds, len(drugs)).astype(np.int32)).cuda()
+    shared = torch.empty(len(pa), G, dtype=torch.int32, device="cuda")
+
+    def overlap_all():
+        _lib.check(lib.gss_topk_overlap(nc, G, k, idx.data_ptr(), cnt.data_ptr(), len(pa), pa.data_ptr(), pb.data_ptr(), shared.data_ptr(),
+                                        _lib.current_stream()), "gss_topk_overlap")
+    out["gss_topk_overlap"] = dict(timed(overlap_all, a.reps), pairs=int(len(pa)),
+                                   note="device events around the entry point, the list check and its synchronisation included")
+    print("gss_topk_overlap", json.dumps(out["gss_topk_overlap"]), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
