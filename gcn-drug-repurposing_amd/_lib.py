@@ -9,7 +9,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgssgcn.so")
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 _lib = None
 
@@ -191,6 +191,13 @@ SIGNATURES = {
     "gss_mark_rows_and_neighbours": (C.c_int, [_P, _P, _I32, _P, _P]),
     "gss_batch_bits": (C.c_int, [_P, _I32, _P, _I32, _P]),
     "gss_bits_fill": (C.c_int, [_P, _I64, _I64, _P]),
+    # for tests: the loss of a plan's step, stage by stage (tests/test_gpu_loss_step.py)
+    "gss_loss_workspace_bytes_parts": (_SZ, [_I32, _I32, _I32]),
+    "gss_loss_step": (C.c_int, [_I32, _I32, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, C.POINTER(_I32)]),
+    "gss_loss_slab_sweep": (C.c_int, [_I32, _I32, _F, _F, _P, _I32, _I32, _P, _P, _P]),
+    "gss_loss_gather_rows": (C.c_int, [_I32, _P, _P, _P, _I32, _P, C.POINTER(_P), _P]),
+    "gss_loss_gather_rows_mapped": (C.c_int, [_I32, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _I32, _P, C.POINTER(_P), _P]),
+    "gss_loss_gather_batch": (C.c_int, [_I32, _P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P, _P]),
 }
 
 

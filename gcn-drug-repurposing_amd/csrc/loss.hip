@@ -802,6 +802,9 @@ int loss_step(const LossStep &s, void *ws, void *stream, bool *dgrad_done) {
   LossLaunch L;
   loss_layout(d, b, ws, L);
   const float *e_b = s.e_b ? s.e_b : L.e_b;
+  // (before any launch: a refused call leaves every buffer as it was)
+  GSS_REQUIRE(!s.w1t || (d == 64 * L.ng && L.nz == 1 && L.ng <= 4),
+              "loss_step: the finish with the input gradient covers d in {64, 128, 256}, not d=%d (loss_dgrad_available says when)", d);
   if (s.de_x) {
     // second half of the row-slab form: the ranks' sums are in de_x ([b][d], the loss behind it was copied out by the caller) -- one
     // "slab" for the finish, no loss partials
@@ -813,7 +816,7 @@ int loss_step(const LossStep &s, void *ws, void *stream, bool *dgrad_done) {
   const int32_t *pos_ids = s.pos_ids ? s.pos_ids : s.rows;
   const int nloss = s.de_x ? 0 : L.ni * L.js;      // loss partials for the finish to sum (none: the loss came with de_x)
   *dgrad_done = false;
-  if (s.w1t) {   // (the caller asked loss_dgrad_available before it handed the weights over)
+  if (s.w1t) {
     FinishDgrad T{b, d, L.js, nloss, L.de_part, L.loss_part, s.alpha, e_b, s.rows, pos_ids, s.pos_set, s.keep, s.inv_den, s.p, s.c,
                   s.dx_b, s.dp_b, s.loss_out, s.w1t, s.w2t, s.gax_b, s.gam_b, s.dgrad_all ? 1 : 0};
     dim3 grid(L.ni), block(256);
@@ -856,5 +859,66 @@ size_t gss_loss_workspace_bytes_max(int32_t b_max, int32_t d) { return b_max > 0
 int gss_loss_fwd_bwd(int32_t n, int32_t d, const float *e, const int32_t *idx, int32_t b, float beta, float alpha,
                      float *loss_out, float *de_b, void *ws, void *stream) {
   return loss_fwd_bwd(n, d, e, idx, b, beta, alpha, loss_out, de_b, ws, stream);
+}
+// for tests (tests/test_gpu_loss_step.py): the loss of a plan's step, stage by stage
+size_t gss_loss_workspace_bytes_parts(int32_t b, int32_t d, int32_t parts) {
+  return (b > 0 && d > 0 && parts >= 1) ? loss_workspace_bytes(b, d, parts) : 0;
+}
+int gss_loss_step(int32_t d, int32_t b, float beta, float alpha, float *loss_out, const float *e_b, const int32_t *rows, const int32_t *pos_ids,
+                  int32_t *pos_set, const float *keep, const float *inv_den, const float *p, float c, float *dx_b, float *dp_b, const float *w1t,
+                  const float *w2t, float *gax_b, float *gam_b, int32_t dgrad_all, const float *de_x, void *ws, void *stream,
+                  int32_t *dgrad_done) {
+  GSS_REQUIRE(dgrad_done, "gss_loss_step: null dgrad_done");
+  LossStep s{};
+  s.d = d;
+  s.b = b;
+  s.beta = beta;
+  s.alpha = alpha;
+  s.loss_out = loss_out;
+  s.e_b = e_b;
+  s.rows = rows;
+  s.pos_ids = pos_ids;
+  s.pos_set = pos_set;
+  s.keep = keep;
+  s.inv_den = inv_den;
+  s.p = p;
+  s.c = c;
+  s.dx_b = dx_b;
+  s.dp_b = dp_b;
+  s.w1t = w1t;
+  s.w2t = w2t;
+  s.gax_b = gax_b;
+  s.gam_b = gam_b;
+  s.dgrad_all = dgrad_all != 0;
+  s.de_x = de_x;
+  bool done = false;
+  const int rc = loss_step(s, ws, stream, &done);
+  if (rc == GSS_OK) *dgrad_done = done ? 1 : 0;
+  return rc;
+}
+int gss_loss_slab_sweep(int32_t d, int32_t b, float beta, float alpha, const float *e_b, int32_t slab_rank, int32_t slab_parts, void *ws,
+                        float *de_x, void *stream) {
+  LossStep s{};
+  s.d = d;
+  s.b = b;
+  s.beta = beta;
+  s.alpha = alpha;
+  s.e_b = e_b;
+  s.slab_rank = slab_rank;
+  s.slab_parts = slab_parts;
+  return loss_step_slab_sweep(s, ws, de_x, stream);
+}
+int gss_loss_gather_rows(int32_t d, const float *e, const int32_t *rows, const float *keep, int32_t b, void *ws, float **e_b_out, void *stream) {
+  return loss_gather_rows(d, e, rows, keep, b, ws, e_b_out, stream);
+}
+int gss_loss_gather_rows_mapped(int32_t d, const float *e, const int32_t *idx, const int32_t *node_map, int32_t lo, int32_t nl,
+                                const int32_t *gid2op, int32_t *pid, int32_t *rloc, float *keep, int32_t b, void *ws, float **e_b_out,
+                                void *stream) {
+  return loss_gather_rows_mapped(d, e, idx, node_map, lo, nl, gid2op, pid, rloc, keep, b, ws, e_b_out, stream);
+}
+int gss_loss_gather_batch(int32_t d, const float *e, const float *p, const float *inv_den, const int32_t *idx, const int32_t *node_map, int32_t lo,
+                          int32_t nl, const int32_t *gid2op, int32_t *pid, int32_t *rloc, float *keep, const int32_t *rows, int32_t b,
+                          float *out, void *stream) {
+  return loss_gather_batch(d, e, p, inv_den, idx, node_map, lo, nl, gid2op, pid, rloc, keep, rows, b, out, stream);
 }
 }

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define GSS_ABI_VERSION 19  /* 19: exact typed top-k selection of listed profile columns and set overlap between selections -- gss_profile_topk, gss_profile_topk_workspace_bytes, gss_topk_overlap; 18: exact average-tie ranks of listed profile columns, the transform behind the spearman distance -- gss_profile_rank, gss_profile_rank_workspace_bytes; 17: gene knock-outs per column of the diffusion profiles -- gss_ppr_set_knockout; distances of listed column pairs of the profile matrix -- gss_profile_dist_pairs, gss_profile_dist_pairs_workspace_bytes; 16: ROC-AUC, average precision and hits@k per row in one launch -- gss_rank_metrics_rows, gss_rank_metrics_workspace_bytes; 15: entry points for tests of the row-sparse SpMM modes -- gss_spmm_bwd1_sparse_ex, gss_spmm_bwd2_sparse_res, gss_spmm_filtered, gss_mark_rows_and_neighbours, gss_batch_bits, gss_bits_fill; 14:indication x drug scores from the embedding tensor -- gss_embedding_scores; 13: pairwise distances between diffusion profiles -- gss_profile_dist; 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
+#define GSS_ABI_VERSION 20  /* 20: entry points for tests of the loss stages of a plan's step -- gss_loss_step, gss_loss_slab_sweep, gss_loss_workspace_bytes_parts, gss_loss_gather_rows, gss_loss_gather_rows_mapped, gss_loss_gather_batch; loss_step refuses input-gradient weights at widths outside {64, 128, 256}; 19: exact typed top-k selection of listed profile columns and set overlap between selections -- gss_profile_topk, gss_profile_topk_workspace_bytes, gss_topk_overlap; 18: exact average-tie ranks of listed profile columns, the transform behind the spearman distance -- gss_profile_rank, gss_profile_rank_workspace_bytes; 17: gene knock-outs per column of the diffusion profiles -- gss_ppr_set_knockout; distances of listed column pairs of the profile matrix -- gss_profile_dist_pairs, gss_profile_dist_pairs_workspace_bytes; 16: ROC-AUC, average precision and hits@k per row in one launch -- gss_rank_metrics_rows, gss_rank_metrics_workspace_bytes; 15: entry points for tests of the row-sparse SpMM modes -- gss_spmm_bwd1_sparse_ex, gss_spmm_bwd2_sparse_res, gss_spmm_filtered, gss_mark_rows_and_neighbours, gss_batch_bits, gss_bits_fill; 14:indication x drug scores from the embedding tensor -- gss_embedding_scores; 13: pairwise distances between diffusion profiles -- gss_profile_dist; 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
 
 #define GSS_OK 0
 #define GSS_EINVAL (-22)   /* bad argument (shape, null pointer, unsupported d) */
@@ -875,6 +875,41 @@ int gss_spmm_filtered(const gss_csr *a, int32_t d, const float *x, float *y, con
 int gss_mark_rows_and_neighbours(const gss_csr *a, const int32_t *rows, int32_t b, uint32_t *bits, void *stream);
 int gss_batch_bits(const int32_t *ids, int32_t b, uint32_t *bits, int32_t set, void *stream);
 int gss_bits_fill(uint32_t *bits, int64_t first, int64_t last, void *stream);
+
+/* ---- FOR TESTS: the loss of a plan's step, stage by stage ------------------------------------------------------------------------
+ * A plan reaches csrc/loss.hip through loss_step, loss_step_slab_sweep and the three gathers; these entry points call exactly those, so
+ * that tests/test_gpu_loss_step.py can hold each to its fp64 contract (tests/loss_step_mirror.py).  Nothing in the product calls them.
+ *   gss_loss_step: the sweep over the gathered rows e_b ([b][d]; NULL: the workspace's E_B, where gss_loss_gather_rows* put it), then
+ *     the finish: loss_out[0]; dx_b = (dE - e (e . dE)) * inv_den[row]; dp_b = c * dx_b (.) elu'(p[row]), both [b][d], zero rows where
+ *     keep[r] == 0 (keep nullable).  rows (nullable): row of inv_den / p per member, NULL = the member's position.  pos_set (nullable):
+ *     pos_set[key[r]] = r for keys >= 0, key = pos_ids, or rows when pos_ids is NULL.  w1t (nullable; then w2t, gax_b, gam_b too; d in
+ *     {64, 128, 256} only, other widths are refused): gax_b = dP W1, gam_b = dP W2 in the same launch, *dgrad_done = 1; dgrad_all != 0:
+ *     rows with keep[r] == 0 enter that product unmasked.  de_x (nullable): no sweep, [b][d] sums of the ranks' gss_loss_slab_sweep
+ *     buffers instead (the loss is not written then).  ws: gss_loss_workspace_bytes(b, d) bytes.
+ *   gss_loss_slab_sweep: the i tiles slab_rank, slab_rank + slab_parts, ... of the sweep.  de_x ([b d + 1] floats): those tiles' rows of
+ *     dE / 2, zeros on every other row, and this rank's share of the loss behind the last row.  ws: gss_loss_workspace_bytes_parts.
+ *   gss_loss_workspace_bytes_parts: the workspace of a sweep whose i tiles are dealt to `parts` ranks (parts = 1: gss_loss_workspace_bytes).
+ *   gss_loss_gather_rows: E_B = e[rows] (zero rows where keep[r] == 0) into the workspace; *e_b_out says where.
+ *   gss_loss_gather_rows_mapped: the same with the id translation folded in: id = node_map[idx[r]] (node_map nullable), rel = id - lo,
+ *     owned <=> 0 <= rel < nl; rloc[r] = rel clamped to [0, max(nl - 1, 0)], keep[r] = owned (keep nullable), pid[r] = gid2op[id], or
+ *     without gid2op rel when owned and -1 when not.
+ *   gss_loss_gather_batch: out = [E_B | P_B | inv_B] ([b (2 d + 1)] floats) of the owned members, zeros for the others; idx == NULL: the
+ *     prepared rows / keep are read instead of translated. */
+size_t gss_loss_workspace_bytes_parts(int32_t b, int32_t d, int32_t parts);
+int gss_loss_step(int32_t d, int32_t b, float beta, float alpha, float *loss_out, const float *e_b, const int32_t *rows,
+                  const int32_t *pos_ids, int32_t *pos_set, const float *keep, const float *inv_den, const float *p, float c, float *dx_b,
+                  float *dp_b, const float *w1t, const float *w2t, float *gax_b, float *gam_b, int32_t dgrad_all, const float *de_x,
+                  void *ws, void *stream, int32_t *dgrad_done);
+int gss_loss_slab_sweep(int32_t d, int32_t b, float beta, float alpha, const float *e_b, int32_t slab_rank, int32_t slab_parts, void *ws,
+                        float *de_x, void *stream);
+int gss_loss_gather_rows(int32_t d, const float *e, const int32_t *rows, const float *keep, int32_t b, void *ws, float **e_b_out,
+                         void *stream);
+int gss_loss_gather_rows_mapped(int32_t d, const float *e, const int32_t *idx, const int32_t *node_map, int32_t lo, int32_t nl,
+                                const int32_t *gid2op, int32_t *pid, int32_t *rloc, float *keep, int32_t b, void *ws, float **e_b_out,
+                                void *stream);
+int gss_loss_gather_batch(int32_t d, const float *e, const float *p, const float *inv_den, const int32_t *idx, const int32_t *node_map,
+                          int32_t lo, int32_t nl, const int32_t *gid2op, int32_t *pid, int32_t *rloc, float *keep, const int32_t *rows,
+                          int32_t b, float *out, void *stream);
 
 #ifdef __cplusplus
 }

@@ -470,8 +470,23 @@ def test_rownorm_fwd_and_bwd(G, n, d):
 
 # ---------------------------------------------------------------- K6 / K7
 @pytest.mark.parametrize("n,d,b", [(3000, 128, 2048), (500, 16, 500), (400, 64, 1), (900, 256, 333), (300, 32, 17), (2000, 128, 1288),
-                                   (700, 192, 200), (600, 512, 130), (500, 320, 77), (400, 48, 50), (2100, 256, 2048)])
+                                   (700, 192, 200), (600, 512, 130), (500, 320, 77), (400, 48, 50), (2100, 256, 2048),
+                                   (200, 576, 33), (200, 1024, 50)])      # d > 512: the sweep's second 512-feature slab, masked and exact
 def test_loss_fwd_bwd(G, n, d, b):
+    loss_fwd_bwd_case(G, n, d, b)
+
+
+@pytest.mark.parametrize("wgs", [64, 4096])
+def test_loss_fwd_bwd_loss_wgs(G, wgs):
+    """the knob that sets the j split: 65 row tiles at loss_wgs = 64 / 4096 sweep with js = 1 / 16 (the cap)"""
+    try:
+        G._lib.check(G.lib.gss_debug_set_option(b"loss_wgs", wgs))
+        loss_fwd_bwd_case(G, 2100, 64, 1040)
+    finally:
+        G._lib.check(G.lib.gss_debug_set_option(b"loss_wgs", 256))
+
+
+def loss_fwd_bwd_case(G, n, d, b):
     rng = np.random.RandomState(b)
     x = rng.randn(n, d)
     x[:, 0] += 1.0  # mostly positive similarities, some negative

@@ -22,3 +22,23 @@ TRAJ_EMB_REL = TRAJ_K * SPREAD_EMB_REL         # 2e-5     (measured: <= 1.3e-6)
 TRAJ_WEIGHT_LR = TRAJ_K * SPREAD_WEIGHT_LR     # 0.02 lr  (measured: <= 1.2e-3 lr)
 # end to end through the CLI (train.py: kNN graph, beta percentile, 12 steps, '%.18e' text): absolute difference of unit-norm rows
 TRAJ_CLI_EMB_ABS = 2e-5
+
+
+# ---- the loss of a plan's step, op by op (tests/test_gpu_loss_step.py against tests/loss_step_mirror.py in fp64) ----------------------
+# Loss and dE keep the bounds test_loss_fwd_bwd has always held gss_loss_fwd_bwd to.
+LOSS_STEP_LOSS_RTOL = 2e-6     # |loss - ref| / |ref|
+LOSS_STEP_DE_REL = 5e-6        # max |dE - ref| / max |ref|
+# The composite outputs (dx_b, dp_b, gax_b, gam_b, the slab sums) get no invented number.  LOSS_STEP_FP32 is the error of the REFERENCE's
+# own formulas evaluated in plain numpy float32 against float64: the largest over every GPU case, relative to the reference tensor's
+# largest entry.  tests/test_loss_step_mirror.py re-measures it on every run of the CPU suite (it may not exceed the figure recorded
+# here, nor fall below a quarter of it).  The GPU bound of a quantity is the larger of the project's bound for its last stage (3e-6:
+# test_rownorm_fwd_and_bwd for dx / dp, test_dense_bwd_input_dense_and_scattered for gax / gam) and LOSS_STEP_K x that figure; 8,
+# because the kernels accumulate sequentially along j and along k on MFMA chains where numpy sums pairwise and in blocks.
+# Measured on the CPU (numpy 2 / OpenBLAS, 1 and 16 threads): dx 8.11e-7, dp 7.24e-7, gax 7.49e-7, gam 9.24e-7, slab 6.34e-7.
+LOSS_STEP_FP32 = {"dx": 9.0e-7, "dp": 8.0e-7, "gax": 8.5e-7, "gam": 1.0e-6, "slab": 7.0e-7}
+LOSS_STEP_LAST_STAGE = 3e-6
+LOSS_STEP_K = 8
+LOSS_STEP_BOUND = {k: max(LOSS_STEP_LAST_STAGE, LOSS_STEP_K * v) for k, v in LOSS_STEP_FP32.items()}
+# = dx 7.2e-6, dp 6.4e-6, gax 6.8e-6, gam 8.0e-6, slab 5.6e-6.  Observed on an MI355X, the largest over every case of
+# test_gpu_loss_step.py (the tests print each figure before they assert): loss 9.0e-8 relative (6.7e-8 as the sum of the slab
+# form's shares), dE 4.2e-7, dx 6.2e-7, dp 5.8e-7, gax 8.4e-7, gam 7.4e-7, slab rows 2.4e-7 of the largest entry.
