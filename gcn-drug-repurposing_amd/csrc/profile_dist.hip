@@ -19,7 +19,7 @@
 //
 // Column lists: a thread that stages or reads column cols[i] adds that offset to a row pointer once; the loads of adjacent lanes coalesce by
 // address, so an ascending contiguous list costs what the null list (0 .. n - 1) costs, and a scattered one pays only for the lines it touches.
-#include "common.h"
+#include "profile_front.h"
 
 namespace gss {
 namespace {
@@ -29,24 +29,9 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 constexpr int kPdTile = 64;       // outputs per workgroup: 64 x 64
 constexpr int kPdSlab = 32;       // rows per staged slab (difference class): 2 panels x 32 x 64 x 8 bytes = 32 KiB of LDS
 constexpr int kPdThreads = 256;
-constexpr uint32_t kNoBad = 0xffffffffu;
 constexpr int kPdMaxList = 1 << 21;   // 32,768 tiles per grid dimension
 
 __device__ __forceinline__ int32_t col_at(const int32_t *cols, int32_t i) { return cols ? cols[i] : i; }
-
-// status[0] / status[1]: the first entry of cols_a / cols_b outside [0, ld) (kNoBad = none); the host set both words to kNoBad
-__global__ __launch_bounds__(kPdThreads) void pd_check_cols_kernel(int32_t na, const int32_t *__restrict__ cols_a, int32_t nb,
-                                                                    const int32_t *__restrict__ cols_b, int64_t ld, uint32_t *__restrict__ status) {
-  const int32_t t = blockIdx.x * kPdThreads + threadIdx.x;
-  if (cols_a && t < na) {
-    const int32_t c = cols_a[t];
-    if (c < 0 || c >= ld) atomicMin(&status[0], (uint32_t)t);
-  }
-  if (cols_b && t < nb) {
-    const int32_t c = cols_b[t];
-    if (c < 0 || c >= ld) atomicMin(&status[1], (uint32_t)t);
-  }
-}
 
 // one thread per list entry (a's entries, then b's): mean[e] (0 unless centre) and norm[e] = sqrt(sum_k (x[k][c] - mean)^2), rows in order
 __global__ __launch_bounds__(kPdThreads) void pd_stats_kernel(int32_t n, const double *__restrict__ x, int64_t ld, int32_t na,
@@ -240,7 +225,6 @@ __global__ __launch_bounds__(kPdThreads) void pd_diff_kernel(int32_t n, const do
 // order of a and b.
 constexpr int kPpRows = 32;       // rows per row block
 constexpr int kPpWaves = 4;       // row blocks per workgroup
-constexpr int kPpStatusBytes = 256;
 enum { kPpSums = 5, kPpDot = 6 };   // modes beside the three difference metrics: column sums (for the means), centred dot and norms
 
 template <int kMode>
@@ -335,13 +319,6 @@ int pp_run(int32_t n, const double *x, int64_t ld, int32_t T, const int32_t *col
   return GSS_OK;
 }
 
-struct DeviceScratch {   // freed on every way out of the call
-  void *p = nullptr;
-  ~DeviceScratch() {
-    if (p) (void)hipFree(p);
-  }
-};
-
 }  // namespace
 }  // namespace gss
 
@@ -378,20 +355,8 @@ int gss_profile_dist(int32_t n, const double *x, int64_t ld, int32_t na, const i
     }
   }
   if (lists) {   // nothing reads x through a list before every entry of it is known to be a column of x
-    uint32_t *status = static_cast<uint32_t *>(ws.p);
-    GSS_HIP(hipMemsetAsync(status, 0xff, 8, st));
-    hipLaunchKernelGGL(pd_check_cols_kernel, dim3(ceil_div(na > nb ? na : nb, kPdThreads)), dim3(kPdThreads), 0, st, na, cols_a, nb, cols_b, ld,
-                       status);
-    GSS_LAUNCH_CHECK("pd_check_cols_kernel");
-    uint32_t h[2] = {kNoBad, kNoBad};
-    GSS_HIP(hipMemcpyAsync(h, status, 8, hipMemcpyDeviceToHost, st));
-    GSS_HIP(hipStreamSynchronize(st));
-    for (int s = 0; s < 2; ++s) {
-      if (h[s] == kNoBad) continue;
-      int32_t c = 0;
-      GSS_HIP(hipMemcpy(&c, (s == 0 ? cols_a : cols_b) + h[s], 4, hipMemcpyDeviceToHost));
-      return fail(GSS_EINVAL, "profile_dist: cols_%c[%u] = %d is outside [0, ld=%lld)", s == 0 ? 'a' : 'b', h[s], c, (long long)ld);
-    }
+    const CheckedList a{cols_a, na, 0, ld, "cols_a", "ld"}, b{cols_b, nb, 0, ld, "cols_b", "ld"};
+    if (int rc = check_lists("profile_dist", a, b, static_cast<uint32_t *>(ws.p), st)) return rc;
   }
   const dim3 grid(ceil_div(nb, kPdTile), ceil_div(na, kPdTile)), block(kPdThreads);
   if (dot) {
@@ -419,7 +384,7 @@ int gss_profile_dist(int32_t n, const double *x, int64_t ld, int32_t na, const i
 size_t gss_profile_dist_pairs_workspace_bytes(int32_t n, int32_t T) {
   if (n < 1 || T < 0) return 0;
   const size_t n_blk = (size_t)ceil_div(n, kPpRows);
-  return kPpStatusBytes + sizeof(double) * (2 * (size_t)T + 3 * n_blk * (size_t)T);
+  return kStatusBytes + sizeof(double) * (2 * (size_t)T + 3 * n_blk * (size_t)T);
 }
 
 int gss_profile_dist_pairs(int32_t n, const double *x, int64_t ld, int32_t T, const int32_t *col_a, const int32_t *col_b, int32_t metric,
@@ -440,21 +405,11 @@ int gss_profile_dist_pairs(int32_t n, const double *x, int64_t ld, int32_t T, co
   GSS_REQUIRE(workspace_bytes >= want, "profile_dist_pairs: workspace of %zu bytes is below the %zu that n=%d, T=%d need", workspace_bytes, want,
               n, T);
   hipStream_t st = as_stream(stream);
-  uint32_t *status = static_cast<uint32_t *>(workspace);   // nothing reads x through a list before every entry of it is known to be a column of x
-  GSS_HIP(hipMemsetAsync(status, 0xff, 8, st));
-  hipLaunchKernelGGL(pd_check_cols_kernel, dim3(ceil_div(T, kPdThreads)), dim3(kPdThreads), 0, st, T, col_a, T, col_b, ld, status);
-  GSS_LAUNCH_CHECK("pd_check_cols_kernel");
-  uint32_t h[2] = {kNoBad, kNoBad};
-  GSS_HIP(hipMemcpyAsync(h, status, 8, hipMemcpyDeviceToHost, st));
-  GSS_HIP(hipStreamSynchronize(st));
-  for (int s = 0; s < 2; ++s) {
-    if (h[s] == kNoBad) continue;
-    int32_t c = 0;
-    GSS_HIP(hipMemcpy(&c, (s == 0 ? col_a : col_b) + h[s], 4, hipMemcpyDeviceToHost));
-    return fail(GSS_EINVAL, "profile_dist_pairs: col_%c[%u] = %d is outside [0, ld=%lld)", s == 0 ? 'a' : 'b', h[s], c, (long long)ld);
-  }
+  // nothing reads x through a list before every entry of it is known to be a column of x
+  const CheckedList a{col_a, T, 0, ld, "col_a", "ld"}, b{col_b, T, 0, ld, "col_b", "ld"};
+  if (int rc = check_lists("profile_dist_pairs", a, b, static_cast<uint32_t *>(workspace), st)) return rc;
   const int32_t n_blk = ceil_div(n, kPpRows);
-  double *mean = reinterpret_cast<double *>(static_cast<char *>(workspace) + kPpStatusBytes), *part = mean + 2 * (size_t)T;
+  double *mean = reinterpret_cast<double *>(static_cast<char *>(workspace) + kStatusBytes), *part = mean + 2 * (size_t)T;
   const int vec_ok = (ld & 1) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
   switch (metric) {
     case GSS_DIST_CITYBLOCK:

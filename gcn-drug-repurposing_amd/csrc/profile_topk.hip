@@ -2,9 +2,10 @@
 // share (gss_topk_overlap): "the proteins and biological functions" a treatment's diffusion profile runs through.
 //
 // include/gssgcn.h has the contract, DESIGN.md section 9.11 the cost model and the measurements.  A column of 29,960 keys is 240 KB and does not
-// fit the LDS, and k <= 1024 of them are wanted: the column is not sorted, the k-th key is SELECTED.  Per panel of kTkPanel listed columns:
-//   tk_keys_kernel    reads the panel's columns of x by rows (adjacent lanes = adjacent listed columns) and writes rank_keys.h's order-preserving
-//                     uint64 keys [panel][n] into the workspace through a 64 x 64 LDS tile (-0.0 folded into +0.0, NaN -> the all-ones key)
+// fit the LDS, and k <= 1024 of them are wanted: the column is not sorted, the k-th key is SELECTED.  Per panel of kKeyPanel listed columns:
+//   keys_kernel       (profile_front.h, shared with gss_profile_rank) reads the panel's columns of x by rows (adjacent lanes = adjacent listed
+//                     columns) and writes rank_keys.h's order-preserving uint64 keys [panel][n] into the workspace through a 64 x 64 LDS tile
+//                     (-0.0 folded into +0.0, NaN -> the all-ones key)
 //   tk_select_kernel  one workgroup per column, all G groups at once (node i's group is read beside its key):
 //                       sweep 0    counts every group's members and notes a NaN among them;
 //                       sweeps     a radix select, 8-bit digits from the top: every key that still matches its group's prefix adds one to
@@ -17,72 +18,19 @@
 //                       sort       the list is bitonic-sorted by (key descending, index ascending) -- a total order, so the slot order of
 //                                  the collection does not show -- and written out; val is read back from x, bit for bit.
 // Groups are in different phases in one sweep, and a finished group's keys are not read again.  The only atomics are integer counters in LDS.
-#include "rank_keys.h"
+// The checks of the column, group and selection lists are profile_front.h's.
+#include "profile_front.h"
 
 namespace gss {
 namespace {
 
-constexpr int kTkTile = 64;            // the transposing kernel moves 64 rows x 64 listed columns per workgroup
-constexpr int kTkTileThreads = 256;
 constexpr int kTkThreads = 512;        // the select kernel: 8 waves, wave g scans group g's histogram
-constexpr int kTkPanel = 512;          // listed columns per pass through the workspace
-constexpr int kTkMaxRows = 1 << 24;    // a node index is three 8-bit digits
 constexpr int kTkMaxK = 1024;
 constexpr int kTkMaxGroups = 8;
 constexpr int kTkBins = 256;
-constexpr int kTkStatusBytes = 256;    // the status words of the list checks, in front of the workspace
-constexpr uint32_t kTkNoBad = 0xffffffffu;
 constexpr int kTkKeyPhases = 8, kTkIdxPhases = 3, kTkDone = kTkKeyPhases + kTkIdxPhases;
 constexpr int kToThreads = 256;        // the overlap kernel
 static_assert(kTkThreads / kWave >= kTkMaxGroups, "one wave per group scans its histogram");
-
-// status[0]: the first entry of cols outside [0, ld); status[1]: the first entry of group outside [-1, G) (kTkNoBad = none; set by the host)
-__global__ __launch_bounds__(kTkTileThreads) void tk_check_kernel(int32_t nc, const int32_t *__restrict__ cols, int64_t ld, int32_t n,
-                                                                   const int32_t *__restrict__ group, int32_t G, uint32_t *__restrict__ status) {
-  const int32_t t = blockIdx.x * kTkTileThreads + threadIdx.x;
-  if (cols && t < nc) {
-    const int32_t c = cols[t];
-    if (c < 0 || c >= ld) atomicMin(&status[0], (uint32_t)t);
-  }
-  if (group && t < n) {
-    const int32_t g = group[t];
-    if (g < -1 || g >= G) atomicMin(&status[1], (uint32_t)t);
-  }
-}
-
-// status[0] / status[1]: the first entry of a / b outside [0, S)
-__global__ __launch_bounds__(kTkTileThreads) void to_check_kernel(int32_t T, const int32_t *__restrict__ a, const int32_t *__restrict__ b, int32_t S,
-                                                                   uint32_t *__restrict__ status) {
-  const int32_t t = blockIdx.x * kTkTileThreads + threadIdx.x;
-  if (t >= T) return;
-  if (a[t] < 0 || a[t] >= S) atomicMin(&status[0], (uint32_t)t);
-  if (b[t] < 0 || b[t] >= S) atomicMin(&status[1], (uint32_t)t);
-}
-
-// panel columns [j0, j0 + 64) x rows [r0, r0 + 64): load phase lane = column, store phase lane = row.  `first` = the panel's first list position
-__global__ __launch_bounds__(kTkTileThreads) void tk_keys_kernel(int32_t n, const double *__restrict__ x, int64_t ld, int32_t pw, int32_t first,
-                                                                  const int32_t *__restrict__ cols, uint64_t *__restrict__ keys) {
-  __shared__ uint64_t tile[kTkTile][kTkTile + 1];
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const int32_t r0 = blockIdx.x * kTkTile, j0 = blockIdx.y * kTkTile;
-  if (j0 + tx < pw) {
-    const int32_t c = cols ? cols[first + j0 + tx] : first + j0 + tx;
-    const double *p = x + c;
-#pragma unroll 4
-    for (int m = 0; m < kTkTile / 4; ++m) {
-      const int32_t row = r0 + ty + 4 * m;
-      if (row < n) tile[ty + 4 * m][tx] = order_key_nan_behind(p[(int64_t)row * ld]);
-    }
-  }
-  __syncthreads();
-  const int32_t row = r0 + tx;
-  if (row >= n) return;
-#pragma unroll 4
-  for (int m = 0; m < kTkTile / 4; ++m) {
-    const int32_t j = j0 + ty + 4 * m;
-    if (j < pw) keys[(size_t)j * n + row] = tile[tx][ty + 4 * m];
-  }
-}
 
 // hist[bin] += 1 for every active lane.  The lanes that share the first active lane's bin add once, together: a column's keys share their
 // leading digits, and 64 additions to one LDS word would queue.  EVERY lane of the wave must reach the call
@@ -306,13 +254,6 @@ __global__ __launch_bounds__(kToThreads) void to_overlap_kernel(int32_t G, int32
   if (tid == 0) shared[(size_t)t * G + g] = hits;
 }
 
-// first bad positions of two checked lists -> host, through the stream
-inline int read_status(uint32_t *status, uint32_t h[2], hipStream_t st) {
-  GSS_HIP(hipMemcpyAsync(h, status, 8, hipMemcpyDeviceToHost, st));
-  GSS_HIP(hipStreamSynchronize(st));
-  return GSS_OK;
-}
-
 }  // namespace
 }  // namespace gss
 
@@ -322,16 +263,16 @@ extern "C" {
 
 // status words, then the keys of a panel
 size_t gss_profile_topk_workspace_bytes(int32_t n, int32_t nc, int32_t G, int32_t k) {
-  if (n < 1 || n > kTkMaxRows || nc < 0 || G < 1 || G > kTkMaxGroups || k < 1 || k > kTkMaxK) return 0;
-  const size_t p = (size_t)(nc < kTkPanel ? nc : kTkPanel);
-  return kTkStatusBytes + p * (size_t)n * 8;
+  if (n < 1 || n > kKeyMaxRows || nc < 0 || G < 1 || G > kTkMaxGroups || k < 1 || k > kTkMaxK) return 0;
+  const size_t p = (size_t)(nc < kKeyPanel ? nc : kKeyPanel);
+  return kStatusBytes + p * (size_t)n * 8;
 }
 
 int gss_profile_topk(int32_t n, const double *x, int64_t ld, int32_t nc, const int32_t *cols, int32_t G, const int32_t *group, int32_t k,
                      int32_t *idx, double *val, int32_t *cnt, void *workspace, size_t workspace_bytes, void *stream) {
   GSS_REQUIRE(n >= 1, "profile_topk: n=%d rows must be >= 1", n);
-  GSS_REQUIRE(n <= kTkMaxRows, "profile_topk: n=%d rows is above the limit of %d (ties are resolved over three 8-bit digits of the node index)", n,
-              kTkMaxRows);
+  GSS_REQUIRE(n <= kKeyMaxRows, "profile_topk: n=%d rows is above the limit of %d (ties are resolved over three 8-bit digits of the node index)", n,
+              kKeyMaxRows);
   GSS_REQUIRE(k >= 1 && k <= kTkMaxK, "profile_topk: k=%d is outside [1, %d]", k, kTkMaxK);
   GSS_REQUIRE(G >= 1 && G <= kTkMaxGroups, "profile_topk: G=%d groups is outside [1, %d]", G, kTkMaxGroups);
   GSS_REQUIRE(nc >= 0, "profile_topk: nc=%d columns must be >= 0", nc);
@@ -349,33 +290,16 @@ int gss_profile_topk(int32_t n, const double *x, int64_t ld, int32_t nc, const i
   GSS_REQUIRE(workspace_bytes >= want, "profile_topk: workspace of %zu bytes is below the %zu that n=%d, nc=%d need", workspace_bytes, want, n, nc);
   hipStream_t st = as_stream(stream);
   if (cols || group) {   // nothing reads x through the list, or a histogram through a group, before every entry is known to be in range
-    uint32_t *status = static_cast<uint32_t *>(workspace);
-    GSS_HIP(hipMemsetAsync(status, 0xff, 8, st));
-    const int32_t most = group && n > nc ? n : nc;
-    hipLaunchKernelGGL(tk_check_kernel, dim3(ceil_div(most, kTkTileThreads)), dim3(kTkTileThreads), 0, st, nc, cols, ld, n, group, G, status);
-    GSS_LAUNCH_CHECK("tk_check_kernel");
-    uint32_t h[2] = {kTkNoBad, kTkNoBad};
-    if (int rc = read_status(status, h, st)) return rc;
-    if (h[0] != kTkNoBad) {
-      int32_t c = 0;
-      GSS_HIP(hipMemcpy(&c, cols + h[0], 4, hipMemcpyDeviceToHost));
-      return fail(GSS_EINVAL, "profile_topk: cols[%u] = %d is outside [0, ld=%lld)", h[0], c, (long long)ld);
-    }
-    if (h[1] != kTkNoBad) {
-      int32_t g = 0;
-      GSS_HIP(hipMemcpy(&g, group + h[1], 4, hipMemcpyDeviceToHost));
-      return fail(GSS_EINVAL, "profile_topk: group[%u] = %d is outside [-1, G=%d)", h[1], g, G);
-    }
+    const CheckedList a{cols, nc, 0, ld, "cols", "ld"}, b{group, group ? n : 0, -1, G, "group", "G"};
+    if (int rc = check_lists("profile_topk", a, b, static_cast<uint32_t *>(workspace), st)) return rc;
   }
-  uint64_t *keys = reinterpret_cast<uint64_t *>(static_cast<char *>(workspace) + kTkStatusBytes);
+  uint64_t *keys = reinterpret_cast<uint64_t *>(static_cast<char *>(workspace) + kStatusBytes);
   const int32_t cp = pow2_at_least(k);
   const size_t lds = (size_t)G * cp * 12 + (size_t)G * kTkBins * 4;
   const size_t lds_arg = lds_request(tk_select_kernel, lds);
-  for (int32_t first = 0; first < nc; first += kTkPanel) {   // the stream orders a panel's two launches and the panels after one another
-    const int32_t pw = nc - first < kTkPanel ? nc - first : kTkPanel;
-    hipLaunchKernelGGL(tk_keys_kernel, dim3(ceil_div(n, kTkTile), ceil_div(pw, kTkTile)), dim3(kTkTileThreads), 0, st, n, x, ld, pw, first, cols,
-                       keys);
-    GSS_LAUNCH_CHECK("tk_keys_kernel");
+  for (int32_t first = 0; first < nc; first += kKeyPanel) {   // the stream orders a panel's two launches and the panels after one another
+    const int32_t pw = nc - first < kKeyPanel ? nc - first : kKeyPanel;
+    if (int rc = launch_keys(n, x, ld, pw, first, cols, keys, st)) return rc;
     hipLaunchKernelGGL(tk_select_kernel, dim3(pw), dim3(kTkThreads), lds_arg, st, n, keys, group, G, k, cp, x, ld, first, cols, idx, val, cnt);
     GSS_LAUNCH_CHECK("tk_select_kernel");
   }
@@ -395,23 +319,11 @@ int gss_topk_overlap(int32_t S, int32_t G, int32_t k, const int32_t *idx, const 
   GSS_REQUIRE(b != nullptr, "topk_overlap: b is null");
   GSS_REQUIRE(shared != nullptr, "topk_overlap: shared is null");
   hipStream_t st = as_stream(stream);
-  uint32_t *status = nullptr;
-  GSS_HIP(hipMalloc(&status, 8));
-  uint32_t h[2] = {kTkNoBad, kTkNoBad};
-  int rc = GSS_OK;
-  if (hipMemsetAsync(status, 0xff, 8, st) != hipSuccess) rc = fail(GSS_EHIP, "topk_overlap: clearing the status words failed");
-  if (rc == GSS_OK) {
-    hipLaunchKernelGGL(to_check_kernel, dim3(ceil_div(T, kTkTileThreads)), dim3(kTkTileThreads), 0, st, T, a, b, S, status);
-    if (hipGetLastError() != hipSuccess) rc = fail(GSS_EHIP, "launch to_check_kernel failed");
-  }
-  if (rc == GSS_OK) rc = read_status(status, h, st);
-  (void)hipFree(status);
-  if (rc != GSS_OK) return rc;
-  for (int side = 0; side < 2; ++side) {
-    if (h[side] == kTkNoBad) continue;
-    int32_t v = 0;
-    GSS_HIP(hipMemcpy(&v, (side ? b : a) + h[side], 4, hipMemcpyDeviceToHost));
-    return fail(GSS_EINVAL, "topk_overlap: %s[%u] = %d is outside [0, S=%d)", side ? "b" : "a", h[side], v, S);
+  {   // nothing reads idx or cnt through a list before every entry of it is known to be a selection; the status words are freed before the launch
+    DeviceScratch status;
+    GSS_HIP(hipMalloc(&status.p, 8));
+    const CheckedList la{a, T, 0, S, "a", "S"}, lb{b, T, 0, S, "b", "S"};
+    if (int rc = check_lists("topk_overlap", la, lb, static_cast<uint32_t *>(status.p), st)) return rc;
   }
   const int32_t cp = pow2_at_least(k);
   hipLaunchKernelGGL(to_overlap_kernel, dim3(T, G), dim3(kToThreads), (size_t)cp * 8, st, G, k, cp, idx, cnt, a, b, shared);

@@ -203,6 +203,19 @@ def _row_stride(x):
     return x.stride(0) if x.shape[0] > 1 else x.shape[1]   # one row: no row stride is ever applied (torch leaves it unspecified)
 
 
+def _device_list(cols, dev):
+    """a host column list -> what a kernel takes for it: None when it is 0, 1, ... len - 1 ("the first columns" needs no list, and no check
+    of one), else a device int32 tensor"""
+    import torch
+    return None if np.array_equal(cols, np.arange(len(cols))) else torch.from_numpy(np.ascontiguousarray(cols, dtype=np.int32)).to(dev)
+
+
+def _workspace(need, dev):
+    """a device workspace of at least `need` bytes, 8-byte aligned"""
+    import torch
+    return torch.empty((need + 7) // 8, dtype=torch.float64, device=dev)
+
+
 def _rank_columns(x, cols):
     """average-tie ranks of the listed columns (host int32 array) of the device fp64 matrix x [N][width] -> device fp64 [N][len(cols)]
     (gss_profile_rank, csrc/profile_rank.hip; exact, a column with a NaN comes out NaN)"""
@@ -214,8 +227,7 @@ def _rank_columns(x, cols):
     lib = _lib.load()
     with torch.cuda.device(x.device):
         need = int(lib.gss_profile_rank_workspace_bytes(n, nc))
-        ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=x.device)
-        lst = None if np.array_equal(cols, np.arange(nc)) else torch.from_numpy(np.ascontiguousarray(cols, dtype=np.int32)).to(x.device)
+        ws, lst = _workspace(need, x.device), _device_list(cols, x.device)
         _lib.check(lib.gss_profile_rank(n, x.data_ptr(), _row_stride(x), nc, _lib.ptr(lst), r.data_ptr(), nc, ws.data_ptr(), need,
                                         _lib.current_stream()), "gss_profile_rank")
     return r
@@ -227,75 +239,66 @@ def _rank_referenced(x, lists):
     return _rank_columns(x, uniq), [np.searchsorted(uniq, c).astype(np.int32) for c in lists]
 
 
-def rank_profiles(profiles, cols=None, device="cuda"):
-    """average-tie ranks of the nodes within diffusion profiles -> device tensor fp64 [N][len(cols)], column j =
-    scipy.stats.rankdata(profile cols[j], method="average"), exactly (gss_profile_rank): the order of a profile's nodes, "the proteins and
-    functions a profile ranks highest", and the transform behind the "spearman" distance.  `profiles` is what compare_profiles accepts: the
-    device tensor x [N][kpad] (used in place; cols are column indices), a host array [K][N] (cols index its rows) or a {name: vector} dict
-    (cols are names).  cols may repeat and come in any order; None means every profile (not for a dict).  A profile that holds a NaN has
-    NaN for every rank.  No CPU fallback."""
+_SEL_ARG = {"row": "rows", "column": "cols"}   # a selection's word in a message -> the argument it came in (col_a and col_b are both)
+
+
+def _profile_source(profiles, sels, labels, who, required=None, lists_who=None):
+    """The one place that knows the three kinds of `profiles`: the device tensor x [N][kpad] (used in place; a selection lists column
+    indices), a host array [K][N] (a selection lists its rows) and a {name: vector} dict (a selection lists names).  sels: one or two
+    selections, labels: their words in a message ("column"; "row", "column"; "col_a", "col_b") -> (N, [one int32 column list per
+    selection], upload), where upload(dev) gives the device fp64 matrix [N][width] with unit column stride that the lists index.  The
+    selections of a dict share one key table, in the order of first appearance: every named profile is uploaded once.  A selection that
+    is None means every profile, which a dict cannot offer; with `required` it is refused in those words for every kind.  Refusals come
+    in the order source, selections; those of a list's entries carry lists_who (who unless given).  Nothing here touches the GPU."""
     import torch
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise _lib.GssError("profile ranks are computed on the GPU only (no CPU fallback)")
-    if isinstance(profiles, torch.Tensor):
-        x = profiles
-        if (x.dim() != 2 or x.dtype != torch.float64 or not x.is_cuda or x.shape[1] < 1 or (x.shape[1] > 1 and x.stride(1) != 1)
-                or (x.shape[0] > 1 and x.stride(0) < x.shape[1])):
-            raise ValueError("rank_profiles: a profile tensor must be a device fp64 matrix [N][columns] with unit column stride and "
-                             "a row stride of at least its width")
-        c = _column_list("column", cols, x.shape[1], who="rank_profiles")
-    elif isinstance(profiles, dict):
-        if cols is None:
-            raise ValueError("rank_profiles: cols must name the profiles of a dict")
-        keys = list(dict.fromkeys(cols))
-        c = _column_list("column", cols, len(keys), {k: i for i, k in enumerate(keys) if k in profiles}, who="rank_profiles")
+    absent = any(sel is None for sel in sels)
+    if isinstance(profiles, dict):
+        if absent:
+            raise ValueError(f"{who}: {required or ' and '.join(_SEL_ARG.get(l, l) for l in labels) + ' must name the profiles of a dict'}")
+        keys = list(dict.fromkeys(k for sel in sels for k in sel))
+        names = {k: i for i, k in enumerate(keys) if k in profiles}
+        lists = [_column_list(l, sel, len(keys), names, who=lists_who or who) for l, sel in zip(labels, sels)]
         host = [np.asarray(profiles[k], dtype=np.float64).reshape(-1) for k in keys]
         if len({len(v) for v in host}) > 1:
-            raise ValueError("rank_profiles: the profiles differ in length")
-        if not host:
-            raise ValueError("rank_profiles: no profile is named")
-        x = torch.from_numpy(np.stack(host)).to(dev).t().contiguous()
-    else:
-        host = np.ascontiguousarray(profiles, dtype=np.float64)
-        if host.ndim != 2:
-            raise ValueError(f"rank_profiles: a host profile array must be [K][N], not {host.shape}")
-        c = _column_list("column", cols, host.shape[0], who="rank_profiles")
-        x = torch.from_numpy(host).to(dev).t().contiguous()
-    if x.shape[0] < 1:
-        raise ValueError("rank_profiles: the profiles are empty")
-    return _rank_columns(x, c)
-
-
-MAX_TOP, MAX_GROUPS = 1024, 8   # gss_profile_topk's limits on k and G
-
-
-def _profile_source(profiles, cols, who):
-    """the three kinds of `profiles` rank_profiles accepts, resolved on the host -> (N, column list int32, upload), where upload(dev) gives
-    the device fp64 matrix [N][width] with unit column stride (a device tensor is used in place).  Nothing here touches the GPU"""
-    import torch
+            raise ValueError(f"{who}: the profiles differ in length")
+        if not host and len(sels) == 1:   # two empty selections are an empty result, one empty selection is a mistake
+            raise ValueError(f"{who}: no profile is named")
+        return len(host[0]) if host else 0, lists, lambda dev: torch.from_numpy(np.stack(host)).to(dev).t().contiguous()
     if isinstance(profiles, torch.Tensor):
         x = profiles
         if (x.dim() != 2 or x.dtype != torch.float64 or not x.is_cuda or x.shape[1] < 1 or (x.shape[1] > 1 and x.stride(1) != 1)
                 or (x.shape[0] > 1 and x.stride(0) < x.shape[1])):
             raise ValueError(f"{who}: a profile tensor must be a device fp64 matrix [N][columns] with unit column stride and "
                              "a row stride of at least its width")
-        return x.shape[0], _column_list("column", cols, x.shape[1], who=who), lambda dev: x
-    if isinstance(profiles, dict):
-        if cols is None:
-            raise ValueError(f"{who}: cols must name the profiles of a dict")
-        keys = list(dict.fromkeys(cols))
-        c = _column_list("column", cols, len(keys), {k: i for i, k in enumerate(keys) if k in profiles}, who=who)
-        host = [np.asarray(profiles[k], dtype=np.float64).reshape(-1) for k in keys]
-        if len({len(v) for v in host}) > 1:
-            raise ValueError(f"{who}: the profiles differ in length")
-        if not host:
-            raise ValueError(f"{who}: no profile is named")
-        return len(host[0]), c, lambda dev: torch.from_numpy(np.stack(host)).to(dev).t().contiguous()
-    host = np.ascontiguousarray(profiles, dtype=np.float64)
-    if host.ndim != 2:
-        raise ValueError(f"{who}: a host profile array must be [K][N], not {host.shape}")
-    return host.shape[1], _column_list("column", cols, host.shape[0], who=who), lambda dev: torch.from_numpy(host).to(dev).t().contiguous()
+        n, width, upload = x.shape[0], x.shape[1], lambda dev: x
+    else:
+        host = np.ascontiguousarray(profiles, dtype=np.float64)
+        if host.ndim != 2:
+            raise ValueError(f"{who}: a host profile array must be [K][N], not {host.shape}")
+        n, width, upload = host.shape[1], host.shape[0], lambda dev: torch.from_numpy(host).to(dev).t().contiguous()
+    if absent and required:
+        raise ValueError(f"{who}: {required}")
+    return n, [_column_list(l, sel, width, who=lists_who or who) for l, sel in zip(labels, sels)], upload
+
+
+def rank_profiles(profiles, cols=None, device="cuda"):
+    """average-tie ranks of the nodes within diffusion profiles -> device tensor fp64 [N][len(cols)], column j =
+    scipy.stats.rankdata(profile cols[j], method="average"), exactly (gss_profile_rank): the order of a profile's nodes, "the proteins and
+    functions a profile ranks highest", and the transform behind the "spearman" distance.  `profiles` is what compare_profiles accepts: the
+    device tensor x [N][kpad] (used in place; cols are column indices), a host array [K][N] (cols index its rows) or a {name: vector} dict
+    (cols are names).  cols may repeat and come in any order; None means every profile (not for a dict).  A profile that holds a NaN has
+    NaN for every rank.  A host array or dict is uploaded only after every refusal the host can make.  No CPU fallback."""
+    import torch
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.GssError("profile ranks are computed on the GPU only (no CPU fallback)")
+    n, (c,), upload = _profile_source(profiles, (cols,), ("column",), "rank_profiles")
+    if n < 1:
+        raise ValueError("rank_profiles: the profiles are empty")
+    return _rank_columns(upload(dev), c)
+
+
+MAX_TOP, MAX_GROUPS = 1024, 8   # gss_profile_topk's limits on k and G
 
 
 def top_nodes(profiles, cols=None, k=20, groups=None, n_groups=None, device="cuda"):
@@ -314,7 +317,7 @@ def top_nodes(profiles, cols=None, k=20, groups=None, n_groups=None, device="cud
         raise _lib.GssError("the top nodes of a profile are selected on the GPU only (no CPU fallback)")
     if not isinstance(k, (int, np.integer)) or not 1 <= k <= MAX_TOP:
         raise ValueError(f"top_nodes: k={k!r} is outside [1, {MAX_TOP}]")
-    n, c, upload = _profile_source(profiles, cols, "top_nodes")
+    n, (c,), upload = _profile_source(profiles, (cols,), ("column",), "top_nodes")
     if n < 1:
         raise ValueError("top_nodes: the profiles are empty")
     grp = None
@@ -351,8 +354,7 @@ def top_nodes(profiles, cols=None, k=20, groups=None, n_groups=None, device="cud
     lib = _lib.load()
     with torch.cuda.device(x.device):
         need = int(lib.gss_profile_topk_workspace_bytes(n, nc, G, int(k)))
-        ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=x.device)
-        lst = None if np.array_equal(c, np.arange(nc)) else torch.from_numpy(np.ascontiguousarray(c, dtype=np.int32)).to(x.device)
+        ws, lst = _workspace(need, x.device), _device_list(c, x.device)
         d_grp = None if grp is None else grp.to(device=x.device, dtype=torch.int32).contiguous()
         _lib.check(lib.gss_profile_topk(n, x.data_ptr(), _row_stride(x), nc, _lib.ptr(lst), G, _lib.ptr(d_grp), int(k), idx.data_ptr(),
                                         val.data_ptr(), cnt.data_ptr(), ws.data_ptr(), need, _lib.current_stream()), "gss_profile_topk")
@@ -408,96 +410,59 @@ def compare_profiles(profiles, rows, cols, metric, device="cuda"):
       * a host array [K][N] (one profile per row): uploaded once, transposed into the kernel's layout; rows / cols index its rows;
       * the {name: vector} dict DiffusionProfiles.load_diffusion_profiles fills: the named profiles are uploaded once; rows / cols are names.
     rows / cols may repeat and come in any order; None means every profile (not for a dict).  An unknown metric is refused by name before
-    the GPU is touched.  No CPU fallback."""
+    the GPU is touched, and a host array or dict is uploaded only after every refusal the host can make.  No CPU fallback."""
     metric_id = check_metric(metric)
     import torch
     dev = torch.device(device)
     if dev.type != "cuda":
         raise _lib.GssError("profile distances run on the GPU only (no CPU fallback)")
-    if isinstance(profiles, torch.Tensor):
-        x = profiles
-        if (x.dim() != 2 or x.dtype != torch.float64 or not x.is_cuda or x.shape[1] < 1 or (x.shape[1] > 1 and x.stride(1) != 1)
-                or (x.shape[0] > 1 and x.stride(0) < x.shape[1])):
-            raise ValueError("compare_profiles: a profile tensor must be a device fp64 matrix [N][columns] with unit column stride and "
-                             "a row stride of at least its width")
-        ca, cb = _column_list("row", rows, x.shape[1]), _column_list("column", cols, x.shape[1])
-    elif isinstance(profiles, dict):
-        if rows is None or cols is None:
-            raise ValueError("compare_profiles: rows and cols must name the profiles of a dict")
-        keys = list(dict.fromkeys(list(rows) + list(cols)))
-        pos = {k: i for i, k in enumerate(keys) if k in profiles}
-        ca, cb = _column_list("row", rows, len(keys), pos), _column_list("column", cols, len(keys), pos)
-        host = [np.asarray(profiles[k], dtype=np.float64).reshape(-1) for k in keys]
-        if len({len(v) for v in host}) > 1:
-            raise ValueError("compare_profiles: the profiles differ in length")
-        x = torch.from_numpy(np.stack(host)).to(dev).t().contiguous() if host else None
-    else:
-        host = np.ascontiguousarray(profiles, dtype=np.float64)
-        if host.ndim != 2:
-            raise ValueError(f"compare_profiles: a host profile array must be [K][N], not {host.shape}")
-        ca, cb = _column_list("row", rows, host.shape[0]), _column_list("column", cols, host.shape[0])
-        x = torch.from_numpy(host).to(dev).t().contiguous()
+    n, (ca, cb), upload = _profile_source(profiles, (rows, cols), ("row", "column"), "compare_profiles")
     out = torch.empty(len(ca), len(cb), dtype=torch.float64, device=dev)
     if len(ca) == 0 or len(cb) == 0:
         return out
-    if x.shape[0] < 1:
+    if n < 1:
         raise ValueError("compare_profiles: the profiles are empty")
+    x = upload(dev)
     if metric in RANK_METRICS:   # the referenced profiles are ranked once; metric_id is the base metric's, applied to the ranks
         x, (ca, cb) = _rank_referenced(x, [ca, cb])
-    lists = []
-    for c in (ca, cb):   # "the first n columns" needs no list (and no check of one)
-        lists.append(None if np.array_equal(c, np.arange(len(c))) else torch.from_numpy(c).to(x.device))
-    ld = _row_stride(x)
     with torch.cuda.device(x.device):
-        _lib.check(_lib.load().gss_profile_dist(x.shape[0], x.data_ptr(), ld, len(ca), _lib.ptr(lists[0]), len(cb), _lib.ptr(lists[1]),
-                                                metric_id, out.data_ptr(), len(cb), _lib.current_stream()),
-                   "gss_profile_dist")
+        la, lb = _device_list(ca, x.device), _device_list(cb, x.device)
+        _lib.check(_lib.load().gss_profile_dist(n, x.data_ptr(), _row_stride(x), len(ca), _lib.ptr(la), len(cb), _lib.ptr(lb), metric_id,
+                                                out.data_ptr(), len(cb), _lib.current_stream()), "gss_profile_dist")
     return out
 
 
 def compare_profile_pairs(profiles, col_a, col_b, metric, device="cuda"):
     """distance between listed pairs of diffusion profiles -> device tensor fp64 [T], entry t = scipy.spatial.distance's value of `metric`
     (one of ALL_METRICS; "spearman" as in compare_profiles) for profiles col_a[t] and col_b[t] (gss_profile_dist_pairs: T distances for the price of T, where compare_profiles
-    would compute T x T and keep the diagonal).  `profiles` is the device tensor PprEngine.run returned (x [N][kpad], profile c in column c,
-    used in place) or a host array [K][N] (uploaded once; the lists index its rows).  Pairs may repeat and come in any order; an entry's bits
-    do not depend on the rest of the list.  No CPU fallback."""
+    would compute T x T and keep the diagonal).  `profiles` is what compare_profiles accepts: the device tensor PprEngine.run returned
+    (x [N][kpad], profile c in column c, used in place), a host array [K][N] (the lists index its rows) or a {name: vector} dict (the lists
+    are names; the named profiles are uploaded once).  Pairs may repeat and come in any order; an entry's bits do not depend on the rest of
+    the list.  A host array or dict is uploaded only after every refusal the host can make.  No CPU fallback."""
     metric_id = check_metric(metric)
     import torch
     dev = torch.device(device)
     if dev.type != "cuda":
         raise _lib.GssError("profile distances run on the GPU only (no CPU fallback)")
-    if isinstance(profiles, torch.Tensor):
-        x = profiles
-        if (x.dim() != 2 or x.dtype != torch.float64 or not x.is_cuda or x.shape[1] < 1 or (x.shape[1] > 1 and x.stride(1) != 1)
-                or (x.shape[0] > 1 and x.stride(0) < x.shape[1])):
-            raise ValueError("compare_profile_pairs: a profile tensor must be a device fp64 matrix [N][columns] with unit column stride and "
-                             "a row stride of at least its width")
-    else:
-        host = np.ascontiguousarray(profiles, dtype=np.float64)
-        if host.ndim != 2:
-            raise ValueError(f"compare_profile_pairs: a host profile array must be [K][N], not {host.shape}")
-        x = torch.from_numpy(host).to(dev).t().contiguous()
-    if col_a is None or col_b is None:
-        raise ValueError("compare_profile_pairs: col_a and col_b must list the pairs")
-    width = x.shape[1]
-    ca, cb = _column_list("col_a", col_a, width), _column_list("col_b", col_b, width)
+    n, (ca, cb), upload = _profile_source(profiles, (col_a, col_b), ("col_a", "col_b"), "compare_profile_pairs",
+                                          required="col_a and col_b must list the pairs", lists_who="compare_profiles")
     if len(ca) != len(cb):
         raise ValueError(f"compare_profile_pairs: col_a lists {len(ca)} profiles and col_b {len(cb)}")
-    out = torch.empty(len(ca), dtype=torch.float64, device=x.device)
     if len(ca) == 0:
-        return out
-    if x.shape[0] < 1:
+        return torch.empty(0, dtype=torch.float64, device=profiles.device if isinstance(profiles, torch.Tensor) else dev)
+    if n < 1:
         raise ValueError("compare_profile_pairs: the profiles are empty")
+    x = upload(dev)
+    out = torch.empty(len(ca), dtype=torch.float64, device=x.device)
     if metric in RANK_METRICS:
         x, (ca, cb) = _rank_referenced(x, [ca, cb])
-    ld = _row_stride(x)
     lib = _lib.load()
     with torch.cuda.device(x.device):
-        need = int(lib.gss_profile_dist_pairs_workspace_bytes(x.shape[0], len(ca)))
-        ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=x.device)
+        need = int(lib.gss_profile_dist_pairs_workspace_bytes(n, len(ca)))
+        ws = _workspace(need, x.device)
         da, db = torch.from_numpy(ca).to(x.device), torch.from_numpy(cb).to(x.device)
-        _lib.check(lib.gss_profile_dist_pairs(x.shape[0], x.data_ptr(), ld, len(ca), da.data_ptr(), db.data_ptr(), metric_id, out.data_ptr(),
-                                              ws.data_ptr(), need, _lib.current_stream()), "gss_profile_dist_pairs")
+        _lib.check(lib.gss_profile_dist_pairs(n, x.data_ptr(), _row_stride(x), len(ca), da.data_ptr(), db.data_ptr(), metric_id,
+                                              out.data_ptr(), ws.data_ptr(), need, _lib.current_stream()), "gss_profile_dist_pairs")
     return out
 
 

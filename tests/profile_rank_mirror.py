@@ -4,8 +4,8 @@ chunk and key, (acc + 1) / 2, NaN propagation) and the seeded inputs the tests r
 import numpy as np
 
 CHUNK = 16384                      # kRkChunk
-PANEL = 512                        # kRkPanel
-STATUS_BYTES = 256                 # kRkStatusBytes
+PANEL = 512                        # kKeyPanel (profile_front.h)
+STATUS_BYTES = 256                 # kStatusBytes (profile_front.h)
 BEHIND = np.uint64(0xFFFFFFFFFFFFFFFF)
 SIZES = (1, 2, 63, 64, 65, 1000, 16383, 16384, 16385, 32768, 32769, 40000)
 KINDS = ("uniform", "small_integers", "zeros_and_tails", "all_equal")

@@ -6,9 +6,9 @@ import numpy as np
 
 from profile_rank_mirror import BEHIND, KINDS, column, keys  # noqa: F401  (the key and the input kinds are gss_profile_rank's)
 
-PANEL = 512                        # kTkPanel
+PANEL = 512                        # kKeyPanel (profile_front.h)
 THREADS = 512                      # kTkThreads
-STATUS_BYTES = 256                 # kTkStatusBytes
+STATUS_BYTES = 256                 # kStatusBytes (profile_front.h)
 MAX_K, MAX_GROUPS, MAX_ROWS = 1024, 8, 1 << 24
 # the issue's sizes; 511 / 512 / 513: one sweep of the select kernel's 512 threads and the next; 255 / 256 / 257 and 65535 / 65536 / 65537:
 # a node index gains its second and its third 8-bit digit (the tie-break among equal keys runs over those digits)

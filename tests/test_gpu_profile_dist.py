@@ -149,6 +149,39 @@ def test_refusals_by_name():
     rc, msg = _call(8, x, 6, 2, i32([5, 0]), 6, None, 0, out, 6)
     assert rc == 0, msg
     M.compare(out[:2].cpu().numpy(), scipy_dist(x.cpu().numpy().T[[5, 0]], x.cpu().numpy().T, "cityblock"), "cityblock", 8)
+    # lists of more than one 256-thread block of the check: the least offending position is named, cols_a's before cols_b's, nothing is
+    # written, and the status words are armed again by every call
+    n, ld, L = 70, 8, 300
+    x = torch.rand(n, ld, dtype=torch.float64, device="cuda")
+    h = x.cpu().numpy().T
+    rng = np.random.RandomState(3)
+    ga, gb = rng.randint(0, ld, L), rng.randint(0, ld, L)
+
+    def with_bad(v, *entries):
+        w = v.copy()
+        for at, e in entries:
+            w[at] = e
+        return i32(w)
+    out = torch.full((L, L), -7.0, dtype=torch.float64, device="cuda")
+    for ca, cb, message in ((with_bad(ga, (290, 8), (270, -3)), i32(gb), "cols_a[270] = -3 is outside [0, ld=8)"),
+                            (with_bad(ga, (290, 8)), with_bad(gb, (5, 9)), "cols_a[290] = 8 is outside [0, ld=8)"),
+                            (i32(ga), with_bad(gb, (299, 8)), "cols_b[299] = 8 is outside [0, ld=8)"),
+                            (None, with_bad(gb, (299, -1)), "cols_b[299] = -1 is outside [0, ld=8)")):
+        rc, msg = _call(n, x, ld, L if ca is not None else ld, ca, L, cb, 0, out, L)
+        assert rc == -22 and msg.startswith("profile_dist: ") and message in msg, (message, rc, msg)
+        assert bool((out == -7.0).all()), message
+    rc, msg = _call(n, x, ld, L, i32(ga), L, i32(gb), 0, out, L)             # the same buffers, valid lists
+    assert rc == 0, msg
+    M.compare(out.cpu().numpy(), scipy_dist(h[ga], h[gb], "cityblock"), "cityblock", n)
+    every = i32(np.arange(ld))
+    for mi in range(len(M.METRICS)):                                         # a null list beside a given one == the explicit 0 .. ld - 1, bit for bit
+        explicit = torch.empty(ld, L, dtype=torch.float64, device="cuda")
+        null_a, null_b = torch.empty(ld, L, dtype=torch.float64, device="cuda"), torch.empty(L, ld, dtype=torch.float64, device="cuda")
+        assert _call(n, x, ld, ld, every, L, i32(gb), mi, explicit, L)[0] == 0 and _call(n, x, ld, ld, None, L, i32(gb), mi, null_a, L)[0] == 0
+        assert torch.equal(null_a.view(torch.int64), explicit.view(torch.int64)), mi
+        explicit = torch.empty(L, ld, dtype=torch.float64, device="cuda")
+        assert _call(n, x, ld, L, i32(ga), ld, every, mi, explicit, ld)[0] == 0 and _call(n, x, ld, L, i32(ga), ld, None, mi, null_b, ld)[0] == 0
+        assert torch.equal(null_b.view(torch.int64), explicit.view(torch.int64)), mi
 
 
 def _gold():

@@ -211,3 +211,27 @@ def test_refusals_by_name():
     rc, msg = call(8, x, 6, 3, a, b, 0, out, ws, need)
     assert rc == 0, msg
     M.compare(out.cpu().numpy(), scipy_pairs(x.cpu().numpy().T, [0, 1, 2], [3, 4, 5], "cityblock"), "cityblock", 8)
+    # lists of more than one 256-thread block of the check: the least offending position is named, col_a's before col_b's, nothing is
+    # written, and the status words are armed again by every call.  (Neither list may be null here: there is no null-list case.)
+    n, ld, L = 70, 8, 300
+    x = torch.rand(n, ld, dtype=torch.float64, device="cuda")
+    rng = np.random.RandomState(3)
+    ga, gb = rng.randint(0, ld, L), rng.randint(0, ld, L)
+
+    def with_bad(v, *entries):
+        w = v.copy()
+        for at, e in entries:
+            w[at] = e
+        return i32(w)
+    need = lib.gss_profile_dist_pairs_workspace_bytes(n, L)
+    out = torch.full((L,), SENTINEL, dtype=torch.float64, device="cuda")
+    ws = torch.zeros(need // 8, dtype=torch.float64, device="cuda")
+    for ca, cb, message in ((with_bad(ga, (290, 8), (270, -3)), i32(gb), "col_a[270] = -3 is outside [0, ld=8)"),
+                            (with_bad(ga, (290, 8)), with_bad(gb, (5, 9)), "col_a[290] = 8 is outside [0, ld=8)"),
+                            (i32(ga), with_bad(gb, (299, 8)), "col_b[299] = 8 is outside [0, ld=8)")):
+        rc, msg = call(n, x, ld, L, ca, cb, 0, out, ws, need)
+        assert rc == -22 and msg.startswith("profile_dist_pairs: ") and message in msg, (message, rc, msg)
+        assert bool((out == SENTINEL).all()), message
+    rc, msg = call(n, x, ld, L, i32(ga), i32(gb), 0, out, ws, need)          # the same buffers, valid lists
+    assert rc == 0, msg
+    M.compare(out.cpu().numpy(), scipy_pairs(x.cpu().numpy().T, ga, gb, "cityblock"), "cityblock", n)

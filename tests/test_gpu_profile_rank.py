@@ -142,6 +142,31 @@ def test_refusals_by_name():
     rc, msg = call(n, x, k, 2, i32([5, 0]), r, k, ws, need)
     assert rc == 0, msg
     assert np.array_equal(r[:, :2].cpu().numpy(), rankdata(x.cpu().numpy()[:, [5, 0]], axis=0)) and bool((r[:, 2:] == SENTINEL).all())
+    # a list of more than one 256-thread block of the check: the least offending position is named, nothing is written, and the status
+    # words are armed again by every call.  (One list: there is no second list to report behind it.)
+    n, ld, L = 70, 8, 300
+    x = torch.rand(n, ld, dtype=torch.float64, device="cuda")
+    want = rankdata(x.cpu().numpy(), axis=0)
+    g = np.random.RandomState(3).randint(0, ld, L)
+    bad = g.copy()
+    bad[290], bad[270] = 8, -3
+    r = torch.full((n, L), SENTINEL, dtype=torch.float64, device="cuda")
+    need = R.workspace_bytes(n, L)
+    ws = torch.zeros(need, dtype=torch.uint8, device="cuda")
+    rc, msg = call(n, x, ld, L, i32(bad), r, L, ws, need)
+    assert rc == -22 and msg.startswith("profile_rank: ") and "cols[270] = -3 is outside [0, ld=8)" in msg, (rc, msg)
+    bad[270] = 0
+    rc, msg = call(n, x, ld, L, i32(bad), r, L, ws, need)
+    assert rc == -22 and "cols[290] = 8 is outside [0, ld=8)" in msg, (rc, msg)
+    assert bool((r == SENTINEL).all())
+    rc, msg = call(n, x, ld, L, i32(g), r, L, ws, need)                        # the same buffers, a valid list
+    assert rc == 0, msg
+    assert np.array_equal(r.cpu().numpy(), want[:, g])
+    rc, msg = call(n, x, ld, ld, None, r, L, ws, need)                         # the null list == the explicit 0 .. ld - 1, bit for bit
+    assert rc == 0, msg
+    null = r[:, :ld].clone()
+    rc, msg = call(n, x, ld, ld, i32(np.arange(ld)), r, L, ws, need)
+    assert rc == 0 and torch.equal(r[:, :ld].view(torch.int64), null.view(torch.int64)) and np.array_equal(null.cpu().numpy(), want), msg
 
 
 def test_rank_profiles_on_the_three_kinds_of_input():

@@ -218,7 +218,62 @@ def test_refusals_by_name():
     want = expected(x.cpu().numpy().T[[5, 0]], group.cpu().numpy(), G, k)
     assert np.array_equal(idx[:2].cpu().numpy(), want[0]) and np.array_equal(cnt[:2].cpu().numpy(), want[2])
     assert np.array_equal(val[:2].cpu().numpy().view(np.int64), want[1]) and bool((idx[2:] == SENT_I).all()) and bool((cnt[2:] == SENT_I).all())
+    # lists of more than one 256-thread block of the check: the least offending position is named, cols' before group's, nothing is
+    # written, and the status words are armed again by every call
+    n, w, L = 70, 8, 300
+    x = torch.rand(n, w, dtype=torch.float64, device="cuda")
+    h = x.cpu().numpy().T
+    rng = np.random.RandomState(3)
+    g_cols, g_group = rng.randint(0, w, L), T.groups(n, G, 5)
 
+    def with_bad(v, *entries):
+        u = np.array(v)
+        for at, e in entries:
+            u[at] = e
+        return i32(u)
+    idx = torch.full((L, G, k), SENT_I, dtype=torch.int32, device="cuda")
+    val = torch.full((L, G, k), SENT_V, dtype=torch.float64, device="cuda")
+    cnt = torch.full((L, G), SENT_I, dtype=torch.int32, device="cuda")
+    need = T.workspace_bytes(n, L, G, k)
+    ws = torch.zeros(need, dtype=torch.uint8, device="cuda")
+    ok = dict(n=n, x=x, ld=w, nc=L, cols=i32(g_cols), G=G, group=i32(g_group), k=k, idx=idx, val=val, cnt=cnt, ws=ws, ws_bytes=need)
+    tall = torch.rand(L, w, dtype=torch.float64, device="cuda")                # n = 300, nc = 2: the group list is the longer one
+    tall_group = T.groups(L, G, 6)
+    tall_case = dict(n=L, x=tall, nc=2, cols=i32([7, 1]), ws_bytes=T.workspace_bytes(L, 2, G, k))
+    assert tall_case["ws_bytes"] <= need
+    for change, message in ((dict(cols=with_bad(g_cols, (290, 8), (270, -3))), "cols[270] = -3 is outside [0, ld=8)"),
+                            (dict(cols=with_bad(g_cols, (290, 8)), group=with_bad(g_group, (5, 2))), "cols[290] = 8 is outside [0, ld=8)"),
+                            (dict(group=with_bad(g_group, (69, -2))), "group[69] = -2 is outside [-1, G=2)"),
+                            (dict(cols=None, nc=w, group=with_bad(g_group, (69, 2))), "group[69] = 2 is outside [-1, G=2)"),
+                            (dict(tall_case, group=with_bad(tall_group, (299, 2))), "group[299] = 2 is outside [-1, G=2)")):
+        rc, msg = call(**dict(ok, **change))
+        assert rc == -22 and msg.startswith("profile_topk: ") and message in msg, (message, rc, msg)
+        assert bool((idx == SENT_I).all()) and bool((val == SENT_V).all()) and bool((cnt == SENT_I).all()), message
+
+    def host(rows):
+        return idx[:rows].cpu().numpy(), val[:rows].cpu().numpy().view(np.int64), cnt[:rows].cpu().numpy()
+    rc, msg = call(**ok)                                                        # the same buffers, valid lists
+    assert rc == 0, msg
+    check(host(L), expected(h[g_cols], g_group, G, k), "after the refusals")
+    rc, msg = call(**dict(ok, **dict(tall_case, group=i32(tall_group))))
+    assert rc == 0, msg
+    check(host(2), expected(tall.cpu().numpy().T[[7, 1]], tall_group, G, k), "the longer group list")
+    # a null list beside a given one == the explicit list, bit for bit: cols null with a group list, a column list with group null
+
+    def run(**change):
+        idx.fill_(SENT_I), val.fill_(SENT_V), cnt.fill_(SENT_I)
+        rc, msg = call(**dict(ok, **change))
+        assert rc == 0, msg
+        return idx.flatten().cpu().numpy(), val.flatten().cpu().numpy().view(np.int64), cnt.flatten().cpu().numpy()
+
+    def first(got, rows, groups):
+        return got[0][:rows * groups * k].reshape(rows, groups, k), got[1][:rows * groups * k].reshape(rows, groups, k), got[2][:rows * groups].reshape(rows, groups)
+    null = run(cols=None, nc=w)
+    check(null, run(cols=i32(np.arange(w)), nc=w), "null cols, whole buffers")
+    check(first(null, w, G), expected(h, g_group, G, k), "null cols")
+    null = run(group=None, G=1)
+    check(null, run(group=i32(np.zeros(n)), G=1), "null group, whole buffers")
+    check(first(null, L, 1), expected(h[g_cols], None, 1, k), "null group")
 
 # ---- gss_topk_overlap -------------------------------------------------------------------------------------------------------------------------
 
@@ -281,6 +336,36 @@ def test_overlap_refusals_by_name():
     assert rc == 0, msg
     rc, msg = overlap_call(**ok)
     assert rc == 0 and bool((shared == 0).all()), msg                           # cnt = 0 everywhere: nothing shared
+    # lists of more than one 256-thread block of the check: the least offending position is named, a's before b's, nothing is written,
+    # and the status words are armed again by every call.  (Neither list may be null here: there is no null-list case.)
+    S, L = 8, 300
+    rng = np.random.RandomState(3)
+    h_idx = np.stack([np.stack([rng.permutation(12)[:k] for _ in range(G)]) for _ in range(S)]).astype(np.int32)
+    h_cnt = rng.randint(0, k + 1, size=(S, G)).astype(np.int32)
+    h_cnt[3, 1] = -1                                                            # a flagged selection
+    for s in range(S):
+        for g in range(G):
+            h_idx[s, g, max(h_cnt[s, g], 0):] = -1
+    idx, cnt = torch.from_numpy(h_idx).cuda(), torch.from_numpy(h_cnt).cuda()
+    ga, gb = rng.randint(0, S, L), rng.randint(0, S, L)
+
+    def with_bad(v, *entries):
+        u = v.copy()
+        for at, e in entries:
+            u[at] = e
+        return i32(u)
+    shared = torch.full((L, G), SENT_I, dtype=torch.int32, device="cuda")
+    ok = dict(S=S, G=G, k=k, idx=idx, cnt=cnt, T_=L, a=i32(ga), b=i32(gb), shared=shared)
+    for change, message in ((dict(a=with_bad(ga, (290, 8), (270, -3))), "a[270] = -3 is outside [0, S=8)"),
+                            (dict(a=with_bad(ga, (290, 8)), b=with_bad(gb, (5, 9))), "a[290] = 8 is outside [0, S=8)"),
+                            (dict(b=with_bad(gb, (299, 8))), "b[299] = 8 is outside [0, S=8)")):
+        rc, msg = overlap_call(**dict(ok, **change))
+        assert rc == -22 and msg.startswith("topk_overlap: ") and message in msg, (message, rc, msg)
+        assert bool((shared == SENT_I).all()), message
+    rc, msg = overlap_call(**ok)                                                # the same buffers, valid lists
+    assert rc == 0, msg
+    want = T.expected_overlap(h_idx, h_cnt, ga, gb)
+    assert (want == -1).any() and (want > 0).any() and np.array_equal(shared.cpu().numpy(), want)
 
 
 # ---- diffusion.top_nodes / top_overlap --------------------------------------------------------------------------------------------------------

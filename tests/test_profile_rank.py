@@ -23,9 +23,10 @@ SIX = M.METRICS + ("spearman",)
 
 
 def test_mirror_constants_are_the_kernels():
-    text = open(os.path.join(ROOT, "gcn-drug-repurposing_amd", "csrc", "profile_rank.hip")).read()
-    for name, value in (("kRkChunk", R.CHUNK), ("kRkPanel", R.PANEL), ("kRkStatusBytes", R.STATUS_BYTES)):
-        assert int(re.search(r"constexpr int %s = (\d+);" % name, text).group(1)) == value
+    csrc = os.path.join(ROOT, "gcn-drug-repurposing_amd", "csrc")
+    text = open(os.path.join(csrc, "profile_rank.hip")).read() + open(os.path.join(csrc, "profile_front.h")).read()   # the shared front end
+    for name, value in (("kRkChunk", R.CHUNK), ("kKeyPanel", R.PANEL), ("kStatusBytes", R.STATUS_BYTES)):
+        assert [int(v) for v in re.findall(r"constexpr int %s = (\d+);" % name, text)] == [value]                  # stated once
 
 
 def test_keys_order_as_ieee_comparison_orders():

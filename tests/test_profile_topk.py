@@ -24,11 +24,12 @@ def same(got, want):
 
 
 def test_mirror_constants_are_the_kernels():
-    text = open(os.path.join(ROOT, "gcn-drug-repurposing_amd", "csrc", "profile_topk.hip")).read()
-    for name, value in (("kTkPanel", T.PANEL), ("kTkThreads", T.THREADS), ("kTkStatusBytes", T.STATUS_BYTES), ("kTkMaxK", T.MAX_K),
+    csrc = os.path.join(ROOT, "gcn-drug-repurposing_amd", "csrc")
+    text = open(os.path.join(csrc, "profile_topk.hip")).read() + open(os.path.join(csrc, "profile_front.h")).read()   # the shared front end
+    for name, value in (("kKeyPanel", T.PANEL), ("kTkThreads", T.THREADS), ("kStatusBytes", T.STATUS_BYTES), ("kTkMaxK", T.MAX_K),
                         ("kTkMaxGroups", T.MAX_GROUPS)):
-        assert int(re.search(r"constexpr int %s = (\d+);" % name, text).group(1)) == value
-    assert re.search(r"constexpr int kTkMaxRows = 1 << 24;", text) and T.MAX_ROWS == 1 << 24
+        assert [int(v) for v in re.findall(r"constexpr int %s = (\d+);" % name, text)] == [value]                  # stated once
+    assert len(re.findall(r"constexpr int kKeyMaxRows = 1 << 24;", text)) == 1 and T.MAX_ROWS == 1 << 24
 
 
 def test_generator_holds_what_the_kernel_must_survive():

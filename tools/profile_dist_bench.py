@@ -3,7 +3,8 @@
 columns, left on the device by PprEngine.run): per metric the device-event time of the indications x drugs and the drugs x drugs comparison
 (median of --reps calls after two warm-up calls), element pairs per second, the share of the fp64 peak (78.6 TFLOP/s, vector and matrix alike: the
 public MI355X figure) on the operations the metric needs, and scipy's cdist on a stated sub-block with the extrapolation to the full block
-labelled as such.  --auc adds evaluate_auc.py's median / mean AUC on the stand-in for 'visit' and the five metrics.
+labelled as such; and of compare_profile_pairs (gss_profile_dist_pairs) on 256 drug-indication pairs, knockout.py's chunk.  --auc adds
+evaluate_auc.py's median / mean AUC on the stand-in for 'visit' and the five metrics.
 Writes profiles/profile_dist_bench.json.   python tools/profile_dist_bench.py [--reps 10] [--auc]"""
 import argparse
 import json
@@ -32,9 +33,9 @@ def main():
     import torch
     from scipy.spatial.distance import cdist
     from gcn_drug_repurposing_amd import _lib, synth
-    from gcn_drug_repurposing_amd.diffusion import METRICS, PprEngine, PprProblem, compare_profiles
+    from gcn_drug_repurposing_amd.diffusion import METRICS, PprEngine, PprProblem, compare_profile_pairs, compare_profiles
     hashes = _lib.source_hashes()
-    out = {"graph": "synth.whole_graph_standin(seed=1)", "source_hash": {"profile_dist.hip": hashes["profile_dist.hip"], "*": hashes["*"]},
+    out = {"graph": "synth.whole_graph_standin(seed=1)", "source_hash": {k: hashes[k] for k in ("profile_dist.hip", "profile_front.h", "rank_keys.h", "*")},
            "reps": a.reps, "peak_fp64_flops": PEAK_FP64, "ops_per_pair": OPS}
     adj, ntype, _ = synth.whole_graph_standin(seed=1)
     m0 = sp.csr_matrix(adj, dtype=np.float64)
@@ -51,6 +52,7 @@ def main():
                indication_columns_contiguous=bool(np.array_equal(inds, np.arange(inds[0], inds[0] + len(inds)))))
     host = x[:, :len(starts)].t().contiguous().cpu().numpy()
     sub = 64
+    pair_a, pair_b = drugs[np.arange(256) % len(drugs)], inds[np.arange(256) % len(inds)]
     out["metrics"] = {}
     for m in METRICS:
         rec = {}
@@ -66,7 +68,7 @@ def main():
                     ms.append(e0.elapsed_time(e1))
             pairs = float(len(rows)) * len(cols) * n
             t = float(np.median(ms)) * 1e-3
-            rec[label] = {"ms_median": float(np.median(ms)), "ms_min": float(min(ms)), "element_pairs": pairs, "element_pairs_per_s": pairs / t,
+            rec[label] = {"ms_median": float(np.median(ms)), "ms_min": float(min(ms)), "ms_max": float(max(ms)), "element_pairs": pairs, "element_pairs_per_s": pairs / t,
                           "share_of_fp64_peak": pairs * OPS[m] / t / PEAK_FP64,
                           "note": "device events around the entry point: list upload, column check, scratch allocation, statistics pass and kernel"}
         t0 = time.perf_counter()
@@ -77,8 +79,19 @@ def main():
                               "extrapolated_s_indications_x_drugs": t_host * len(inds) * len(drugs) / (sub * sub),
                               "note": "one host core; the full-block figure is an extrapolation, not timed",
                               "max_abs_difference_to_device_on_block": float(np.nanmax(np.abs(got - want)))}
+        ms = []                                                        # gss_profile_dist_pairs at knockout.py's size: 256 listed pairs
+        for r in range(a.reps + 2):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            compare_profile_pairs(x, pair_a, pair_b, m)
+            e1.record()
+            torch.cuda.synchronize()
+            if r >= 2:
+                ms.append(e0.elapsed_time(e1))
+        rec["pairs_T256"] = {"ms_median": float(np.median(ms)), "ms_min": float(min(ms)), "ms_max": float(max(ms)),
+                             "note": "device events around compare_profile_pairs: list upload, column check, workspace and kernels"}
         out["metrics"][m] = rec
-        print(m, json.dumps(rec["indications_x_drugs"]), flush=True)
+        print(m, json.dumps(rec["indications_x_drugs"]), json.dumps(rec["pairs_T256"]), flush=True)
     del eng, x
     if a.auc:
         from gcn_drug_repurposing_amd import evaluate

@@ -70,7 +70,7 @@ def main():
     hashes = _lib.source_hashes()
     lib = _lib.load()
     assert lib.gss_source_hash(b"profile_rank.hip").decode() == hashes["profile_rank.hip"], "the library was not built from this tree"
-    out = {"graph": "synth.whole_graph_standin(seed=1)", "source_hash": {k: hashes[k] for k in ("profile_rank.hip", "rank_keys.h", "*")},
+    out = {"graph": "synth.whole_graph_standin(seed=1)", "source_hash": {k: hashes[k] for k in ("profile_rank.hip", "profile_front.h", "rank_keys.h", "*")},
            "reps": a.reps}
     adj, ntype, _ = synth.whole_graph_standin(seed=1)
     m0 = sp.csr_matrix(adj, dtype=np.float64)
