@@ -9,7 +9,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgssgcn.so")
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 _lib = None
 
@@ -198,6 +198,20 @@ SIGNATURES = {
     "gss_loss_gather_rows": (C.c_int, [_I32, _P, _P, _P, _I32, _P, C.POINTER(_P), _P]),
     "gss_loss_gather_rows_mapped": (C.c_int, [_I32, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _I32, _P, C.POINTER(_P), _P]),
     "gss_loss_gather_batch": (C.c_int, [_I32, _P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P, _P]),
+    # for tests: the dense half of a plan's step, launcher by launcher (tests/test_gpu_dense_step.py)
+    "gss_dense_fwd_rows": (C.c_int, [_I32, _I32, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _I32, _P]),
+    "gss_dense_fwd_first": (C.c_int, [_I32, _I32, _P, _P, _P, _P]),
+    "gss_dense_fwd_split_available": (C.c_int, [_I32, _I32]),
+    "gss_dense_fwd_norm": (C.c_int, [_I32, _I32, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _I32, _P]),
+    "gss_rownorm_fwd_rows": (C.c_int, [_I32, _I32, _P, _P, _P, _P, _P]),
+    "gss_wgrad_slices": (C.c_int, [_I32, _I32]),
+    "gss_wgrad_slices_max": (C.c_int, [_I32, _I32]),
+    "gss_wgrad_partial": (C.c_int, [_I32, _I32, _P, _P, _P, _P, _P, _I32, _I32, C.POINTER(_I32), _P]),
+    "gss_wgrad_partial_pair": (C.c_int, [_I32, _I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _I32, _P, _I32, C.POINTER(_I32), C.POINTER(_I32), _P]),
+    "gss_wgrad_reduce": (C.c_int, [_I32, _P, _I32, _I32, _P, _P, _P, _P, _I32, _P]),
+    "gss_wgrad_reduce_adam": (C.c_int, [_I32, _P, _I32, _I32, _P * 4, _P * 4, _P * 4, _P * 4, _I32, _F, _F, _F, _F, _P, _P, _P, _P, _I32, _P]),
+    "gss_adam_step4": (C.c_int, [_P * 4, _P * 4, _P * 4, _P * 4, _I64 * 4, _I32, _F, _F, _F, _F, _P, _P, _I32, _P, _P, _I32, _P]),
+    "gss_transpose2": (C.c_int, [_I32, _P, _P, _P, _P, _P]),
 }
 
 

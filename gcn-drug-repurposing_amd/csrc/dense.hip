@@ -842,7 +842,11 @@ static int launch_gemm(const GemmArgs &g, int d, hipStream_t st) {
     // W-staging redundancy of small tiles costs more than that buys (profiles/r03_projection_pipeline_experiments.txt), and so it does once
     // the grid is many waves of workgroups deep (d = 128: N = 1M 791 -> 753 us, N = 4M 3061 -> 2913 us with 128-node tiles)
     const int mt = K().gemm_variant == 3 ? 2 : ((d >= 256 || g.n >= 262144) ? 2 : 1);
-    if (PART == 0 && EPI != EPI_SPLIT && g.rows && (int64_t)ceil_div(g.n, 64) * (g.J / (16 * nt)) < 256) {
+    // A row list under the fused row norm at d = 256 (nt = 16) takes the whole-row kernel WHATEVER its length: the staged tiles further
+    // down have a 16-block form without a row list only, and their switch would give a long list (16,321 rows or more) the one-block
+    // tile with grid.y = 1 -- 16 of a row's 256 features written, and the row normalised over those 16.
+    const bool short_list = (int64_t)ceil_div(g.n, 64) * (g.J / (16 * nt)) < 256;
+    if (PART == 0 && EPI != EPI_SPLIT && g.rows && (short_list || nt == 16)) {
       // forward over a short row list: 16 listed rows per workgroup.  Whole rows of 64 / 128 / 256 features: 4 waves that split the
       // features (gemm_rows_split_kernel, same bits); other widths: one wave per 16 x 16 nt tile
       if (EPI != EPI_SPLIT && g.J == d && g.jsplit == d && (d == 64 || d == 128 || d == 256)) {
@@ -1541,5 +1545,40 @@ size_t gss_wgrad_workspace_bytes(int32_t n, int32_t d) { return wgrad_workspace_
 int gss_dense_bwd_weight(int32_t n, int32_t d, const float *dp, const float *ax, const float *am, const int32_t *rows,
                          float *gw1, float *gw2, float *gb, int accumulate, void *ws, void *stream) {
   return dense_bwd_weight(n, d, dp, ax, am, rows, gw1, gw2, gb, nullptr, accumulate, ws, stream);
+}
+// for tests (tests/test_gpu_dense_step.py): the forms of the projection and of the weight gradient that only a plan reaches, as the plan calls them
+int gss_dense_fwd_rows(int32_t n, int32_t d, const float *ax, const float *am, const float *w1, const float *b1, const float *w2,
+                       const float *b2, const float *p_prev, float decay, float *p, float *x_next, const int32_t *row_list,
+                       int32_t acc_in_p, void *stream) {
+  return dense_fwd(n, d, ax, am, w1, b1, w2, b2, p_prev, decay, p, x_next, stream, row_list, acc_in_p != 0);
+}
+int gss_dense_fwd_first(int32_t n, int32_t d, const float *ax, const float *w1, float *acc, void *stream) {
+  return dense_fwd_first(n, d, ax, w1, acc, stream);
+}
+int gss_dense_fwd_split_available(int32_t n, int32_t d) { return dense_fwd_split_available(n, d) ? 1 : 0; }
+int gss_dense_fwd_norm(int32_t n, int32_t d, const float *ax, const float *am, const float *w1, const float *b1, const float *w2,
+                       const float *b2, const float *p_prev, float decay, float *p, float *e, float *inv_den, const int32_t *row_list,
+                       float *rows_out, const int32_t *rows_out_pos, int32_t acc_in_p, void *stream) {
+  return dense_fwd_norm(n, d, ax, am, w1, b1, w2, b2, p_prev, decay, p, e, inv_den, stream, row_list, rows_out, rows_out_pos, acc_in_p != 0);
+}
+int gss_wgrad_slices(int32_t n, int32_t d) { return wgrad_slices(n, d); }
+int gss_wgrad_slices_max(int32_t n_max, int32_t d) { return wgrad_slices_max(n_max, d); }
+int gss_wgrad_partial(int32_t n, int32_t d, const float *dp, const float *ax, const float *am, const int32_t *rows, void *ws,
+                      int32_t total_slices, int32_t slice0, int32_t *nslices_out, void *stream) {
+  return wgrad_partial(n, d, dp, ax, am, rows, ws, total_slices, slice0, nslices_out, stream);
+}
+int gss_wgrad_partial_pair(int32_t d, int32_t n0, const float *dp0, const float *ax0, const float *am0, const int32_t *rows0,
+                           int32_t slice0_0, int32_t n1, const float *dp1, const float *ax1, const float *am1, const int32_t *rows1,
+                           int32_t slice0_1, void *ws, int32_t total_slices, int32_t *ns0_out, int32_t *ns1_out, void *stream) {
+  return wgrad_partial_pair(d, n0, dp0, ax0, am0, rows0, slice0_0, n1, dp1, ax1, am1, rows1, slice0_1, ws, total_slices, ns0_out, ns1_out, stream);
+}
+int gss_wgrad_reduce(int32_t d, void *ws, int32_t total_slices, int32_t nslices, float *gw1, float *gw2, float *gb, float *gb2,
+                     int32_t accumulate, void *stream) {
+  return wgrad_reduce(d, ws, total_slices, nslices, gw1, gw2, gb, gb2, accumulate, stream);
+}
+int gss_wgrad_reduce_adam(int32_t d, void *ws, int32_t total_slices, int32_t nslices, float *const grad[4], float *const param[4],
+                          float *const m[4], float *const v[4], int32_t step, float lr, float beta1, float beta2, float eps, float *w1t,
+                          float *w2t, int32_t *pos_clear, const int32_t *idx, int32_t b, void *stream) {
+  return wgrad_reduce_adam(d, ws, total_slices, nslices, grad, param, m, v, step, lr, beta1, beta2, eps, w1t, w2t, pos_clear, idx, b, stream);
 }
 }

@@ -646,4 +646,18 @@ int gss_adam_step(int64_t count, float *param, const float *grad, float *exp_avg
 // for tests (tests/test_gpu_sparse_ops.py): the bitmap builders of the row-sparse SpMM modes, as the plan calls them
 int gss_batch_bits(const int32_t *ids, int32_t b, uint32_t *bits, int32_t set, void *stream) { return batch_bits(ids, b, bits, set, stream); }
 int gss_bits_fill(uint32_t *bits, int64_t first, int64_t last, void *stream) { return bits_fill(bits, first, last, stream); }
+// for tests (tests/test_gpu_dense_step.py): the row norm over a row list, the four-tensor Adam and the weight transposes, as the plan calls them
+int gss_rownorm_fwd_rows(int32_t n, int32_t d, const float *x, float *e, float *inv_den, const int32_t *rows, void *stream) {
+  return rownorm_fwd(n, d, x, e, inv_den, stream, rows);
+}
+int gss_adam_step4(float *const param[4], const float *const grad[4], float *const m[4], float *const v[4], const int64_t count[4],
+                   int32_t step, float lr, float beta1, float beta2, float eps, float *w1t, float *w2t, int32_t dim, int32_t *pos_clear,
+                   const int32_t *ids, int32_t b, void *stream) {
+  AdamTensor t[4];
+  for (int k = 0; k < 4; ++k) t[k] = AdamTensor{param[k], grad[k], m[k], v[k], count[k]};
+  return adam_step4(t, step, lr, beta1, beta2, eps, w1t, w2t, dim, stream, pos_clear, ids, b);
+}
+int gss_transpose2(int32_t dim, const float *a, const float *b, float *at, float *bt, void *stream) {
+  return transpose2(dim, a, b, at, bt, stream);
+}
 }

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define GSS_ABI_VERSION 20  /* 20: entry points for tests of the loss stages of a plan's step -- gss_loss_step, gss_loss_slab_sweep, gss_loss_workspace_bytes_parts, gss_loss_gather_rows, gss_loss_gather_rows_mapped, gss_loss_gather_batch; loss_step refuses input-gradient weights at widths outside {64, 128, 256}; 19: exact typed top-k selection of listed profile columns and set overlap between selections -- gss_profile_topk, gss_profile_topk_workspace_bytes, gss_topk_overlap; 18: exact average-tie ranks of listed profile columns, the transform behind the spearman distance -- gss_profile_rank, gss_profile_rank_workspace_bytes; 17: gene knock-outs per column of the diffusion profiles -- gss_ppr_set_knockout; distances of listed column pairs of the profile matrix -- gss_profile_dist_pairs, gss_profile_dist_pairs_workspace_bytes; 16: ROC-AUC, average precision and hits@k per row in one launch -- gss_rank_metrics_rows, gss_rank_metrics_workspace_bytes; 15: entry points for tests of the row-sparse SpMM modes -- gss_spmm_bwd1_sparse_ex, gss_spmm_bwd2_sparse_res, gss_spmm_filtered, gss_mark_rows_and_neighbours, gss_batch_bits, gss_bits_fill; 14:indication x drug scores from the embedding tensor -- gss_embedding_scores; 13: pairwise distances between diffusion profiles -- gss_profile_dist; 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
+#define GSS_ABI_VERSION 21  /* 21: entry points for tests of the dense half of a plan's step -- gss_dense_fwd_rows, gss_dense_fwd_first, gss_dense_fwd_split_available, gss_dense_fwd_norm, gss_rownorm_fwd_rows, gss_wgrad_slices, gss_wgrad_slices_max, gss_wgrad_partial, gss_wgrad_partial_pair, gss_wgrad_reduce, gss_wgrad_reduce_adam, gss_adam_step4, gss_transpose2; 20: entry points for tests of the loss stages of a plan's step -- gss_loss_step, gss_loss_slab_sweep, gss_loss_workspace_bytes_parts, gss_loss_gather_rows, gss_loss_gather_rows_mapped, gss_loss_gather_batch; loss_step refuses input-gradient weights at widths outside {64, 128, 256}; 19: exact typed top-k selection of listed profile columns and set overlap between selections -- gss_profile_topk, gss_profile_topk_workspace_bytes, gss_topk_overlap; 18: exact average-tie ranks of listed profile columns, the transform behind the spearman distance -- gss_profile_rank, gss_profile_rank_workspace_bytes; 17: gene knock-outs per column of the diffusion profiles -- gss_ppr_set_knockout; distances of listed column pairs of the profile matrix -- gss_profile_dist_pairs, gss_profile_dist_pairs_workspace_bytes; 16: ROC-AUC, average precision and hits@k per row in one launch -- gss_rank_metrics_rows, gss_rank_metrics_workspace_bytes; 15: entry points for tests of the row-sparse SpMM modes -- gss_spmm_bwd1_sparse_ex, gss_spmm_bwd2_sparse_res, gss_spmm_filtered, gss_mark_rows_and_neighbours, gss_batch_bits, gss_bits_fill; 14:indication x drug scores from the embedding tensor -- gss_embedding_scores; 13: pairwise distances between diffusion profiles -- gss_profile_dist; 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
 
 #define GSS_OK 0
 #define GSS_EINVAL (-22)   /* bad argument (shape, null pointer, unsupported d) */
@@ -910,6 +910,55 @@ int gss_loss_gather_rows_mapped(int32_t d, const float *e, const int32_t *idx, c
 int gss_loss_gather_batch(int32_t d, const float *e, const float *p, const float *inv_den, const int32_t *idx, const int32_t *node_map,
                           int32_t lo, int32_t nl, const int32_t *gid2op, int32_t *pid, int32_t *rloc, float *keep, const int32_t *rows,
                           int32_t b, float *out, void *stream);
+
+/* ---- FOR TESTS: the dense half of a plan's step, launcher by launcher ------------------------------------------------------------
+ * A plan reaches csrc/dense.hip and the optimizer kernels of csrc/elementwise.hip through the launchers below; these entry points pass
+ * their arguments straight through, so that tests/test_gpu_dense_step.py can hold each form to its fp64 contract
+ * (tests/dense_step_mirror.py).  Nothing in the product calls them.
+ *   gss_dense_fwd_rows: gss_dense_fwd with a row list (nullable): the n tile rows are node rows row_list[0..n) of every operand, a
+ *     negative entry is skipped (nothing of it is written); listed rows get the bits of the pass without a list.  acc_in_p != 0: the
+ *     second of two launches -- p holds gss_dense_fwd_first's accumulators; the pair gives the bits of one launch.
+ *   gss_dense_fwd_first: acc = AX W1^T, raw, [n][d].  gss_dense_fwd_split_available: 1 where the two-launch form exists under the current
+ *     knobs (d in {64, 128, 256}, no row list, not the weight-stationary kernel); elsewhere both launches are refused with GSS_EINVAL.
+ *   gss_dense_fwd_norm: the last layer -- p as gss_dense_fwd, e = x / max(|x|, 1e-12) with x = elu(p) or p_prev + decay elu(p), inv_den
+ *     = 1 / max(|x|, 1e-12) per row; d in {16, 32, 64, 128, 256}.  rows_out (nullable) goes with exactly one of row_list (rows_out[t] =
+ *     e[row_list[t]] for entries >= 0) and rows_out_pos (rows_out[rows_out_pos[r]] = e[r] where that is >= 0).
+ *   gss_rownorm_fwd_rows: gss_rownorm_fwd over the n listed rows of x / e / inv_den (rows nullable; negative entries skipped).
+ *   gss_wgrad_slices / gss_wgrad_slices_max: the slices gss_wgrad_partial writes for n rows / a bound over every n in [1, n_max].
+ *   gss_wgrad_partial: the partial sums of one problem (dp [n][d] compact, ax / am indexed by rows when given) into slices [slice0,
+ *     slice0 + *nslices_out) of ws = [total_slices][d][2 d] weight slabs followed by [total_slices][d] bias slabs.
+ *   gss_wgrad_partial_pair: two problems in one launch (d a multiple of 64 and both non-empty), in two launches otherwise.
+ *   gss_wgrad_reduce: gw1, gw2, gb (and gb2, nullable) = the sum of slices [0, nslices), in slice order; accumulate != 0 adds to them.
+ *   gss_wgrad_reduce_adam: the same sum into grad[] (order w1, b1, w2, b2; b1 and b2 get the same gradient) and torch's Adam on param[]
+ *     / m[] / v[] in the same launch; w1t, w2t (nullable): transposed copies of the updated W1, W2; pos_clear (nullable):
+ *     pos_clear[idx[r]] = -1 for the b entries idx[r] >= 0.
+ *   gss_adam_step4: Adam on four tensors of count[k] elements in one launch, with the same transposed copies and reset.
+ *   gss_transpose2: at = a^T, bt = b^T for two [dim][dim] matrices. */
+int gss_dense_fwd_rows(int32_t n, int32_t d, const float *ax, const float *am, const float *w1, const float *b1, const float *w2,
+                       const float *b2, const float *p_prev, float decay, float *p, float *x_next, const int32_t *row_list,
+                       int32_t acc_in_p, void *stream);
+int gss_dense_fwd_first(int32_t n, int32_t d, const float *ax, const float *w1, float *acc, void *stream);
+int gss_dense_fwd_split_available(int32_t n, int32_t d);
+int gss_dense_fwd_norm(int32_t n, int32_t d, const float *ax, const float *am, const float *w1, const float *b1, const float *w2,
+                       const float *b2, const float *p_prev, float decay, float *p, float *e, float *inv_den, const int32_t *row_list,
+                       float *rows_out, const int32_t *rows_out_pos, int32_t acc_in_p, void *stream);
+int gss_rownorm_fwd_rows(int32_t n, int32_t d, const float *x, float *e, float *inv_den, const int32_t *rows, void *stream);
+int gss_wgrad_slices(int32_t n, int32_t d);
+int gss_wgrad_slices_max(int32_t n_max, int32_t d);
+int gss_wgrad_partial(int32_t n, int32_t d, const float *dp, const float *ax, const float *am, const int32_t *rows, void *ws,
+                      int32_t total_slices, int32_t slice0, int32_t *nslices_out, void *stream);
+int gss_wgrad_partial_pair(int32_t d, int32_t n0, const float *dp0, const float *ax0, const float *am0, const int32_t *rows0,
+                           int32_t slice0_0, int32_t n1, const float *dp1, const float *ax1, const float *am1, const int32_t *rows1,
+                           int32_t slice0_1, void *ws, int32_t total_slices, int32_t *ns0_out, int32_t *ns1_out, void *stream);
+int gss_wgrad_reduce(int32_t d, void *ws, int32_t total_slices, int32_t nslices, float *gw1, float *gw2, float *gb, float *gb2,
+                     int32_t accumulate, void *stream);
+int gss_wgrad_reduce_adam(int32_t d, void *ws, int32_t total_slices, int32_t nslices, float *const grad[4], float *const param[4],
+                          float *const m[4], float *const v[4], int32_t step, float lr, float beta1, float beta2, float eps, float *w1t,
+                          float *w2t, int32_t *pos_clear, const int32_t *idx, int32_t b, void *stream);
+int gss_adam_step4(float *const param[4], const float *const grad[4], float *const m[4], float *const v[4], const int64_t count[4],
+                   int32_t step, float lr, float beta1, float beta2, float eps, float *w1t, float *w2t, int32_t dim, int32_t *pos_clear,
+                   const int32_t *ids, int32_t b, void *stream);
+int gss_transpose2(int32_t dim, const float *a, const float *b, float *at, float *bt, void *stream);
 
 #ifdef __cplusplus
 }

@@ -42,3 +42,22 @@ LOSS_STEP_BOUND = {k: max(LOSS_STEP_LAST_STAGE, LOSS_STEP_K * v) for k, v in LOS
 # = dx 7.2e-6, dp 6.4e-6, gax 6.8e-6, gam 8.0e-6, slab 5.6e-6.  Observed on an MI355X, the largest over every case of
 # test_gpu_loss_step.py (the tests print each figure before they assert): loss 9.0e-8 relative (6.7e-8 as the sum of the slab
 # form's shares), dE 4.2e-7, dx 6.2e-7, dp 5.8e-7, gax 8.4e-7, gam 7.4e-7, slab rows 2.4e-7 of the largest entry.
+
+
+# ---- the dense half of a plan's step, launcher by launcher (tests/test_gpu_dense_step.py against tests/dense_step_mirror.py in fp64) ----
+# P, x_next, gW and gb keep the 3e-6 of the largest entry that test_dense_fwd and test_dense_bwd_weight hold the plain forms to; Adam keeps
+# test_adam_matches_torch_semantics' 2.5e-7 x max(1, |ref|).  E, inv_den and E_B (rows_out) follow the LOSS_STEP scheme above:
+# DENSE_STEP_FP32 is the error of the mirror's formulas in plain numpy float32 against float64, the largest over every case of the fused
+# norm and of the row norm -- E relative to the reference's largest entry, inv_den relative per row (zero rows excluded: they are checked
+# exactly).  tests/test_dense_step_mirror.py re-measures it on every run of the CPU suite (not above the record, not below a quarter of
+# it).  The GPU bound is max(3e-6, 8 x that figure): 8 as above, for sequential MFMA accumulation against numpy's pairwise sums.
+# Measured on the CPU (numpy 2 / OpenBLAS): E 6.48e-7, inv_den 2.07e-7.
+DENSE_STEP_PLAIN = 3e-6
+DENSE_STEP_ADAM = 2.5e-7
+DENSE_STEP_FP32 = {"e": 7.0e-7, "inv_den": 2.3e-7}
+DENSE_STEP_K = 8
+DENSE_STEP_BOUND = {k: max(DENSE_STEP_PLAIN, DENSE_STEP_K * v) for k, v in DENSE_STEP_FP32.items()}
+DENSE_STEP_BOUND["rows_out"] = DENSE_STEP_BOUND["e"]          # E_B copies E's rows bit for bit
+# = E 5.6e-6, inv_den 3.0e-6.  Observed on an MI355X, the largest over every case of test_gpu_dense_step.py (the tests print each figure
+# before they assert): P 1.9e-6, x_next 1.9e-6, AX W1^T 6.3e-7, E 1.0e-6 of the largest entry, inv_den 2.8e-7 per row, gW1 1.5e-7, gW2
+# 2.0e-7, gb 1.6e-7; Adam from the state each launch reads: parameters 3.3e-8, m 1.2e-7, v 1.1e-7.
