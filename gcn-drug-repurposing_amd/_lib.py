@@ -9,7 +9,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgssgcn.so")
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 _lib = None
 
@@ -132,6 +132,7 @@ SIGNATURES = {
     "gss_plan_step_lazy": (C.c_int, [_P, _P, _I32, _F, _P]),
     "gss_plan_activation": (_P, [_P, C.c_int, C.c_int]),
     "gss_plan_device_bytes": (_SZ, [_P]),
+    "gss_plan_l1_ahead": (C.c_int, [_P]),
     "gss_plan_check_guards": (C.c_int, [_P]),
     "gss_plan_lazy_halo_rows": (C.c_int, [_P, C.POINTER(_I64)]),
     "gss_plan_comm_stats": (C.c_int, [_P, C.POINTER(_I64)]),
@@ -189,6 +190,7 @@ SIGNATURES = {
     "gss_spmm_bwd2_sparse_res": (C.c_int, [_P, _I32, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _I32, _P]),
     "gss_spmm_filtered": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gss_mark_rows_and_neighbours": (C.c_int, [_P, _P, _I32, _P, _P]),
+    "gss_spmm_fwd_pair": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P]),
     "gss_batch_bits": (C.c_int, [_P, _I32, _P, _I32, _P]),
     "gss_bits_fill": (C.c_int, [_P, _I64, _I64, _P]),
     # for tests: the loss of a plan's step, stage by stage (tests/test_gpu_loss_step.py)

@@ -106,6 +106,17 @@ int spmm_fwd(const gss_csr *a, int32_t d, const float *x, float *y, const float 
              const float *y_in = nullptr,
              const uint32_t *gather_bits = nullptr,   // plain product only: neighbours whose bit is clear are skipped (their rows are zero)
              const BatchPrep *prep = nullptr);        // balanced SpMM only: the batch preparation as a side job of this launch
+// Two unfiltered forward products over ONE matrix -- y_k = A x_k, and m_k = y_k (.) h_k when m_k is given (both or neither) -- in one launch
+// where the balanced SpMM has a paired form, in two otherwise (spmm.hip decides; *paired_out says which).  Same bits as two spmm_fwd calls.
+// prep rides with the first product as in spmm_fwd.
+struct SpmmFwdArgs {
+  const float *x;
+  float *y;
+  const float *h;
+  float *m;
+};
+int spmm_fwd_pair(const gss_csr *a, int32_t d, const SpmmFwdArgs &p0, const SpmmFwdArgs &p1, void *stream, const BatchPrep *prep = nullptr,
+                  int *paired_out = nullptr);
 int mark_rows_and_neighbours(const gss_csr *a, const int32_t *rows, int32_t b, uint32_t *bits, void *stream);
 int spmm_bwd1(const gss_csr *at, int32_t d, const float *g_am, const float *g_ax, const float *x_in, const float *ax,
               float *u, float *t, void *stream, const float *y_in = nullptr);

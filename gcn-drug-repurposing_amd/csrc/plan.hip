@@ -45,6 +45,15 @@ struct gss_plan {
   void *loss_ws, *wgrad_ws;
   int32_t step;
   bool layer1_valid;
+  // layer 1 one pass ahead, in place (one GPU, L >= 2, neither cache_layer1 nor pipeline_layer1; option "l1_ahead"): layer 1's two SpMMs
+  // read constants only (A_hat, X), and they are the same kernel over the same descriptors as layer 2's.  So a FULL forward pass runs them
+  // for the NEXT pass as the second halves of layer 2's two launches (spmm_fwd_pair): AX_1 -> ax[0], M_1 -> l1_m (below), A_hat M_1 ->
+  // am[0].  Same stream, no events, no second buffer set for AX / AM: their only readers are this pass's layer-1 projection (earlier in
+  // the stream) and this step's weight gradient (later, and the values are identical).  l1_ahead = ax[0] / am[0] hold layer 1 for the
+  // next pass, which then runs no layer-1 SpMM.  Cleared when a pass consumes it (so a pass that fails leaves it clear) and at creation.
+  // The features and A_hat are the plan's constants, as for cache_layer1: there is no entry point that rebinds them.
+  bool l1_ahead;
+  int l1_ahead_opt;   // -1 = automatic (l1_ahead_auto below), 0 = never, 1 = wherever the conditions above hold
   // software pipelining of layer 1 across steps (desc.pipeline_layer1): its two SpMMs read only constants (A_hat, X), so
   // step t+1's run on `side` underneath step t's MFMA-bound kernels, into the other half of a double buffer
   hipStream_t side;
@@ -61,6 +70,7 @@ struct gss_plan {
   bool prof_on;
   std::vector<hipEvent_t> ev;      // pairs: 2 k = start, 2 k + 1 = stop
   std::vector<int> ev_cls;
+  std::vector<int> ev_n;           // launches (products) the bracket stands for: 2 for a paired SpMM launch, else 1
   size_t ev_used;
   double prof_ms[GSS_PROF_CLASSES];
   int64_t prof_cnt[GSS_PROF_CLASSES];
@@ -162,16 +172,26 @@ struct ProfScope {
       p->ev.push_back(a);
       p->ev.push_back(b);
       p->ev_cls.push_back(cls);
+      p->ev_n.push_back(1);
     }
     slot = p->ev_used++;
     p->ev_cls[slot] = cls;
+    p->ev_n[slot] = 1;
     (void)hipEventRecord(p->ev[2 * slot], st);
   }
   ~ProfScope() {
     if (on) (void)hipEventRecord(p->ev[2 * slot + 1], st);
   }
+  // the bracket holds one launch that computes n products of this class: booked as n launches that share its time, so the per-launch
+  // averages of the class stay per product
+  void products(int n) {
+    if (on) p->ev_n[slot] = n;
+  }
 };
 #define PROF(cls) ProfScope prof_scope_##__LINE__(p, cls, stream)
+
+// option "l1_ahead" = -1: layer 1 one pass ahead wherever a plan qualifies (gss_plan::l1_ahead; the measurement is DESIGN.md section 4)
+constexpr bool l1_ahead_auto() { return true; }
 
 // Every carved buffer is followed by a 256-byte guard (kGuardByte everywhere, written once at creation).  No kernel may touch one:
 // gss_plan_check_guards reads them back -- a buffer sized for the wrong worst case shows up there instead of silently running into
@@ -435,6 +455,8 @@ int plan_create_impl(gss_plan **out, const gss_plan_desc *desc, const gss_shard_
   p->grad[3] = io->gb2;
   p->step = 0;
   p->layer1_valid = false;
+  p->l1_ahead = false;
+  p->l1_ahead_opt = -1;
   p->wt_valid = false;
 
   p->prof_on = false;
@@ -856,6 +878,17 @@ int plan_forward_impl(gss_plan *p, void *stream, const int32_t *lazy_rows = null
     p->am[0] = p->am0[p->cur0];
     have_l0 = true;
   }
+  if (p->l1_ahead) {
+    // the previous full pass computed this pass's layer 1 in layer 2's launches (gss_plan::l1_ahead): consumed here, whatever follows
+    p->l1_ahead = false;
+    have_l0 = true;
+  }
+  // this pass carries the next one's layer 1 when it is a full pass of a plan that qualifies
+  const bool ahead = p->P == 1 && L >= 2 && !D.cache_layer1 && !D.pipeline_layer1 && !lazy_rows && D.n > 0 &&
+                     (p->l1_ahead_opt == 1 || (p->l1_ahead_opt < 0 && l1_ahead_auto()));
+  // M_1 of the next pass lives between the two paired launches only; m0op is m_tmp on one GPU, where layer 2's own M goes at the same
+  // time, so it borrows dP: the backward pass writes every row of it before it reads any, and nothing in a forward pass touches it
+  float *l1_m = p->dp;
   for (int l = 0; l < L; ++l) {
     float *xl = p->xin[l];
     const bool cached = (l == 0 && ((D.cache_layer1 && p->layer1_valid) || have_l0));
@@ -891,9 +924,13 @@ int plan_forward_impl(gss_plan *p, void *stream, const int32_t *lazy_rows = null
       {
         const uint32_t *rbits = (lazy_l && p->needbits) ? p->needbits : nullptr;
         auto full = [&]() {
-          PROF(GSS_PROF_SPMM_FWD_HAD);
+          ProfScope prof(p, GSS_PROF_SPMM_FWD_HAD, stream);
           const BatchPrep *prep = p->prep_pending;     // the step's batch preparation as a side job of its first forward SpMM
           p->prep_pending = nullptr;
+          if (ahead && l == 1) {   // + the next pass's AX_1 = A_hat X, M_1 = AX_1 (.) X
+            prof.products(2);
+            return spmm_fwd_pair(p->a, D.d, SpmmFwdArgs{xl, p->ax[l], xl, m}, SpmmFwdArgs{p->xin[0], p->ax[0], p->xin[0], l1_m}, stream, prep);
+          }
           return spmm_fwd(p->a, D.d, xl, p->ax[l], xl, m, stream, nullptr, rbits, nullptr, nullptr, prep);
         };
         if (l == 0 || (l == 1 && p->recompute)) {
@@ -932,7 +969,13 @@ int plan_forward_impl(gss_plan *p, void *stream, const int32_t *lazy_rows = null
         const int32_t *rpos = lazy_l ? p->pos : nullptr;
         LiveHint hint_b(lazy_l ? (int64_t)lazy_b : 0);   // (A_hat M on the batch rows only)
         auto full = [&]() {
-          PROF(GSS_PROF_SPMM_FWD);
+          ProfScope prof(p, GSS_PROF_SPMM_FWD, stream);
+          if (ahead && l == 1) {   // + the next pass's A_hat M_1; from here on ax[0] / am[0] hold layer 1 of the next pass
+            prof.products(2);
+            const int rc = spmm_fwd_pair(p->a, D.d, SpmmFwdArgs{m, p->am[l], nullptr, nullptr}, SpmmFwdArgs{l1_m, p->am[0], nullptr, nullptr}, stream);
+            p->l1_ahead = rc == GSS_OK;
+            return rc;
+          }
           return spmm_fwd(p->a, D.d, m, p->am[l], nullptr, nullptr, stream, rpos);
         };
         if (l == 0 && p->m0_ready) {   // layer 1's M: boundary rows are constants, fetched in the first step
@@ -1385,6 +1428,12 @@ void gss_plan_destroy(gss_plan *p) {
 int gss_plan_debug_set_option(gss_plan *p, const char *name, int value) {
   GSS_REQUIRE(p && name, "plan_debug_set_option: null argument");
   static const char *const kLive[] = {"gemm_variant", "spmm_slices", "spmm_pin", "gemm_ws", "spmm_list_blocks", "proj_split"};
+  if (strcmp(name, "l1_ahead") == 0) {
+    // a PLAN option, not a process-wide knob: it picks between launches over the same buffers, and a set flag stays valid across a switch
+    GSS_REQUIRE(value >= -1 && value <= 1, "l1_ahead must be -1 (automatic), 0 or 1");
+    p->l1_ahead_opt = value;
+    return GSS_OK;
+  }
   bool ok = false;
   for (const char *k : kLive) ok = ok || strcmp(k, name) == 0;
   GSS_REQUIRE(ok, "plan_debug_set_option: only kernel-selection knobs can change on a live plan");
@@ -1449,7 +1498,7 @@ static int plan_step_impl(gss_plan *p, const int32_t *idx, int32_t b, float beta
   const gss_plan_desc &D0 = p->desc;
   const bool mapped0 = plan_batch_mapped(p);
   const bool sparse0 = D0.num_layers > 1 && spmm_sparse_available() && p->pos;
-  const bool l0_runs = !(D0.cache_layer1 && p->layer1_valid) && !p->prefetched;
+  const bool l0_runs = !(D0.cache_layer1 && p->layer1_valid) && !p->prefetched && !p->l1_ahead;
   const bool host_prep = p->P == 1 && sparse0 && K().prep_side != 0 && idx && b >= 1 && b <= D0.max_batch &&
                          (l0_runs || !(lazy && p->needbits));
   BatchPrep prep{idx, b, D0.node_map, p->lo, D0.n, p->gid2op_t, mapped0 ? p->rloc : nullptr, mapped0 ? p->pid : nullptr, p->keep, p->pos, p->rlist};
@@ -1565,6 +1614,7 @@ const float *gss_plan_activation(const gss_plan *p, int layer, int which) {
   return which == 0 ? p->ax[layer] : which == 1 ? p->am[layer] : which == 2 ? p->p[layer] : which == 3 ? p->dp : which == 4 ? p->dp_b : nullptr;
 }
 size_t gss_plan_device_bytes(const gss_plan *p) { return p ? p->slab_bytes : 0; }
+int gss_plan_l1_ahead(const gss_plan *p) { return p && p->l1_ahead ? 1 : 0; }
 
 int gss_plan_lazy_halo_rows(const gss_plan *p, int64_t *out6) {
   GSS_REQUIRE(p && out6, "plan_lazy_halo_rows: null argument");
@@ -1631,7 +1681,7 @@ int gss_plan_profile_read(gss_plan *p, double *ms_out, int64_t *count_out, void 
     float ms = 0.f;
     GSS_HIP(hipEventElapsedTime(&ms, p->ev[2 * k], p->ev[2 * k + 1]));
     p->prof_ms[p->ev_cls[k]] += ms;
-    p->prof_cnt[p->ev_cls[k]] += 1;
+    p->prof_cnt[p->ev_cls[k]] += p->ev_n[k];
   }
   p->ev_used = 0;
   for (int k = 0; k < GSS_PROF_CLASSES; ++k) {

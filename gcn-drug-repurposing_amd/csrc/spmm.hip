@@ -580,6 +580,21 @@ __device__ __forceinline__ void spmm_balanced_block(const CsrView &a, const int4
 }
 
 
+// batch_prepare_kernel's body for the whole batch, by one workgroup of a forward launch (BatchPrep, ops.h)
+__device__ __forceinline__ void batch_prep_block(const BatchPrep &q) {
+  for (int i = threadIdx.x; i < q.b; i += kBalThreads) {
+    const int id = q.node_map ? q.node_map[q.idx[i]] : q.idx[i];
+    const int rel = id - q.lo;
+    const bool mine = rel >= 0 && rel < q.nl;
+    const int op = q.gid2op ? q.gid2op[id] : (mine ? rel : -1);
+    if (q.rloc) q.rloc[i] = min(max(rel, 0), max(q.nl - 1, 0));
+    if (q.pid) q.pid[i] = op;
+    if (q.keep) q.keep[i] = mine ? 1.f : 0.f;
+    if (q.rlist) q.rlist[i] = mine ? rel : -1;
+    if (op >= 0) q.pos[op] = i;
+  }
+}
+
 template <int MODE, int LPR_LOG2, int VPL, bool NARROW>
 __global__ __launch_bounds__(kBalThreads) void spmm_balanced_kernel(CsrView a, const int4 *__restrict__ segs, int d4,
                                                                    const float *__restrict__ x, SpmmEpi ep, int rowstride_f, int pin_ns, int3 hot) {
@@ -595,23 +610,42 @@ __global__ __launch_bounds__(kBalThreads) void spmm_balanced_kernel(CsrView a, c
   const int sidx = pin_ns > 0 ? bx % pin_ns : (int)blockIdx.y;
   if (has_prep && blockIdx.x == 0) {
     // the side job (workgroup-uniform branch): batch_prepare_kernel's body for the whole batch
-    if (blockIdx.y == 0) {
-      const BatchPrep &q = ep.prep;
-      for (int i = threadIdx.x; i < q.b; i += kBalThreads) {
-        const int id = q.node_map ? q.node_map[q.idx[i]] : q.idx[i];
-        const int rel = id - q.lo;
-        const bool mine = rel >= 0 && rel < q.nl;
-        const int op = q.gid2op ? q.gid2op[id] : (mine ? rel : -1);
-        if (q.rloc) q.rloc[i] = min(max(rel, 0), max(q.nl - 1, 0));
-        if (q.pid) q.pid[i] = op;
-        if (q.keep) q.keep[i] = mine ? 1.f : 0.f;
-        if (q.rlist) q.rlist[i] = mine ? rel : -1;
-        if (op >= 0) q.pos[op] = i;
-      }
-    }
+    if (blockIdx.y == 0) batch_prep_block(ep.prep);
     return;
   }
   spmm_balanced_block<MODE, LPR_LOG2, VPL, NARROW>(a, segs, d4, x, ep, rowstride_f, sblk, sidx, hot, part);
+}
+
+// ---- two products in one launch ---------------------------------------------------------------------------------------------------
+// Two whole-dispatch products over the SAME matrix, descriptors, width, slicing and hot policy, each with its own operand and epilogue:
+// the grid is the first product's workgroups followed by the second's (`half` = workgroups per product along x), the batch-preparation
+// workgroup still first.  A workgroup of the second half subtracts `half` and runs spmm_balanced_block as it stands on the second operand
+// set (workgroup-uniform branch), so every row is summed by the same lane groups in the same order as in a launch of its own: the bits of
+// a paired launch are the bits of two launches.  What it saves is the boundary between them -- the second product's first (hub)
+// workgroups start while the first product's last (leaf) ones drain.
+// XCD pinning: slice = (linear id - prep workgroup) mod pin_ns in BOTH halves, because `half` = segment blocks x pin_ns is a multiple of
+// pin_ns; with the prep workgroup every id is shifted by one in both halves alike, so an XCD still only ever gathers one slice's columns
+// of either operand (the XCD -> slice map is the unpaired launch's).
+template <int MODE, int LPR_LOG2, int VPL, bool NARROW>
+__global__ __launch_bounds__(kBalThreads) void spmm_balanced_pair_kernel(CsrView a, const int4 *__restrict__ segs, int d4, const float *__restrict__ x0,
+                                                                        SpmmEpi ep0, const float *__restrict__ x1, SpmmEpi ep1, int rowstride_f,
+                                                                        int pin_ns, int3 hot, int half) {
+  static_assert(MODE == SPMM_FWD1 || MODE == SPMM_PLAIN, "only the forward products are paired");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float4 *part = reinterpret_cast<float4 *>(smem);  // [16 waves][d4]
+  const bool has_prep = MODE == SPMM_FWD1 && ep0.prep.idx != nullptr;   // (the side job belongs to the first product; ep1 carries none)
+  if (has_prep && blockIdx.x == 0) {
+    if (blockIdx.y == 0) batch_prep_block(ep0.prep);
+    return;
+  }
+  int bx = (int)blockIdx.x - (has_prep ? 1 : 0);
+  const bool second = bx >= half;
+  if (second) bx -= half;
+  const int sblk = pin_ns > 0 ? bx / pin_ns : bx;
+  const int sidx = pin_ns > 0 ? bx % pin_ns : (int)blockIdx.y;
+  // (one copy of the block's code: the operand set is picked field by field with scalar selects)
+  const SpmmEpi &ep = second ? ep1 : ep0;
+  spmm_balanced_block<MODE, LPR_LOG2, VPL, NARROW>(a, segs, d4, second ? x1 : x0, ep, rowstride_f, sblk, sidx, hot, part);
 }
 
 // ---- row-filtered products over MANY workgroups (round 6) ----------------------------------------------------------------------
@@ -727,8 +761,15 @@ int csr_segments(const gss_csr *a, int gpw_log2, const int4 **out, int *n_blocks
 // 0 = automatic (see launch_balanced)   [knob spmm_slices, common.h Knobs]
 // with a manual "spmm_slices": slices pinned to XCDs (1) or time-separated (0)   [knob spmm_pin, common.h Knobs]
 
+// the second problem of a paired launch (spmm_balanced_pair_kernel): its own operand and epilogue, everything else the first one's
+struct SpmmSecond {
+  const float *x;
+  SpmmEpi ep;
+};
+
 template <int MODE, int LPR_LOG2, int VPL>
-static int launch_balanced_t(const gss_csr *a, int d4_slice, int nslices, bool pin, const float *x, const SpmmEpi &ep_in, hipStream_t st) {
+static int launch_balanced_t(const gss_csr *a, int d4_slice, int nslices, bool pin, const float *x, const SpmmEpi &ep_in, hipStream_t st,
+                             const SpmmSecond *second = nullptr) {
   const int4 *segs = nullptr;
   int nblk = 0;
   if (int rc = csr_segments(a, 6 - LPR_LOG2, &segs, &nblk)) return rc;
@@ -773,6 +814,20 @@ static int launch_balanced_t(const gss_csr *a, int d4_slice, int nslices, bool p
       return GSS_OK;
     }
   }
+  if constexpr (MODE == SPMM_PLAIN || MODE == SPMM_FWD1) {
+    if (second) {   // (spmm_pair_ok let it through: no filter, so the list form above was not taken)
+      const int half = pin ? nblk * nslices : nblk;
+      const dim3 grid = pin ? dim3(2 * half + extra) : dim3(2 * half + extra, nslices);
+      if (narrow)
+        hipLaunchKernelGGL((spmm_balanced_pair_kernel<MODE, LPR_LOG2, VPL, true>), grid, dim3(kBalThreads), lds, st, v, segs, d4_slice, x, ep, second->x,
+                           second->ep, d4_slice * nslices * 4, pin ? nslices : 0, make_int3(-1, 0, 0), half);
+      else
+        hipLaunchKernelGGL((spmm_balanced_pair_kernel<MODE, LPR_LOG2, VPL, false>), grid, dim3(kBalThreads), lds, st, v, segs, d4_slice, x, ep, second->x,
+                           second->ep, d4_slice * nslices * 4, pin ? nslices : 0, hot, half);
+      GSS_LAUNCH_CHECK("spmm_balanced_pair_kernel");
+      return GSS_OK;
+    }
+  }
   if (narrow)
     hipLaunchKernelGGL((spmm_balanced_kernel<MODE, LPR_LOG2, VPL, true>), pin ? dim3(nblk * nslices + extra) : dim3(nblk + extra, nslices), dim3(kBalThreads),
                        lds, st, v, segs, d4_slice, x, ep, d4_slice * nslices * 4, pin ? nslices : 0, make_int3(-1, 0, 0));
@@ -784,7 +839,7 @@ static int launch_balanced_t(const gss_csr *a, int d4_slice, int nslices, bool p
 }
 
 template <int MODE>
-static int launch_balanced(const gss_csr *a, int d4, const float *x, const SpmmEpi &ep, hipStream_t st) {
+static int launch_balanced(const gss_csr *a, int d4, const float *x, const SpmmEpi &ep, hipStream_t st, const SpmmSecond *second = nullptr) {
   int ns = K().spmm_slices;
   bool pin = K().spmm_pin != 0;
   if (ns == 0) {
@@ -808,13 +863,13 @@ static int launch_balanced(const gss_csr *a, int d4, const float *x, const SpmmE
   if (ns < 1 || d4 % ns != 0 || (d4 / ns) < 4 || MODE == SPMM_BWD1S) ns = 1;  // the sparse mode gathers few rows anyway
   pin = pin && ns > 1;
   const int ds = d4 / ns;
-  if (ds <= 4) return launch_balanced_t<MODE, 2, 1>(a, ds, ns, pin, x, ep, st);
-  if (ds <= 8) return launch_balanced_t<MODE, 3, 1>(a, ds, ns, pin, x, ep, st);
-  if (ds <= 16) return launch_balanced_t<MODE, 4, 1>(a, ds, ns, pin, x, ep, st);
-  if (ds <= 32) return launch_balanced_t<MODE, 5, 1>(a, ds, ns, pin, x, ep, st);
-  if (ds <= 64) return launch_balanced_t<MODE, 6, 1>(a, ds, ns, pin, x, ep, st);
-  if (ds <= 128) return launch_balanced_t<MODE, 6, 2>(a, ds, ns, pin, x, ep, st);
-  return launch_balanced_t<MODE, 6, 4>(a, ds, ns, pin, x, ep, st);
+  if (ds <= 4) return launch_balanced_t<MODE, 2, 1>(a, ds, ns, pin, x, ep, st, second);
+  if (ds <= 8) return launch_balanced_t<MODE, 3, 1>(a, ds, ns, pin, x, ep, st, second);
+  if (ds <= 16) return launch_balanced_t<MODE, 4, 1>(a, ds, ns, pin, x, ep, st, second);
+  if (ds <= 32) return launch_balanced_t<MODE, 5, 1>(a, ds, ns, pin, x, ep, st, second);
+  if (ds <= 64) return launch_balanced_t<MODE, 6, 1>(a, ds, ns, pin, x, ep, st, second);
+  if (ds <= 128) return launch_balanced_t<MODE, 6, 2>(a, ds, ns, pin, x, ep, st, second);
+  return launch_balanced_t<MODE, 6, 4>(a, ds, ns, pin, x, ep, st, second);
 }
 
 }  // namespace gss
@@ -1019,6 +1074,44 @@ int spmm_fwd(const gss_csr *a, int32_t d, const float *x, float *y, const float 
   ep.gather_bits = gather_bits;
   ep.rowbits = row_bits;
   return launch_spmm<SPMM_PLAIN>(a, d, x, ep, stream);
+}
+
+// Two forward products over one matrix, one launch where a paired form exists (spmm_balanced_pair_kernel), two launches otherwise -- the ONE
+// place that decides.  Paired: the whole-dispatch form of the balanced SpMM, both products Hadamard-fused or both plain.  Not paired:
+// spmm_variant 1, a matrix with giant rows (three passes per product), an empty matrix.  The row and gather filters, the listed-workgroup
+// form and the two-pass (y_in) products have no way in here: a caller that needs one of them calls spmm_fwd twice.
+int spmm_fwd_pair(const gss_csr *a, int32_t d, const SpmmFwdArgs &p0, const SpmmFwdArgs &p1, void *stream, const BatchPrep *prep, int *paired_out) {
+  if (paired_out) *paired_out = 0;
+  if (int rc = check_d(d)) return rc;
+  GSS_REQUIRE(a && p0.x && p0.y && p1.x && p1.y, "spmm_fwd_pair: null operand");
+  GSS_REQUIRE((p0.m != nullptr) == (p1.m != nullptr), "spmm_fwd_pair: both products Hadamard-fused or both plain");
+  GSS_REQUIRE((!p0.m || p0.h) && (!p1.m || p1.h), "spmm_fwd_pair: m given without h");
+  bool pair = K().spmm_variant == 2 && a->n_rows > 0 && a->nnz > 0;
+  if (pair) {
+    gss_giant_rows *g = nullptr;
+    if (int rc = csr_giant_rows(a, &g)) return rc;
+    pair = g == nullptr;
+  }
+  if (!pair) {
+    if (int rc = spmm_fwd(a, d, p0.x, p0.y, p0.h, p0.m, stream, nullptr, nullptr, nullptr, nullptr, prep)) return rc;
+    return spmm_fwd(a, d, p1.x, p1.y, p1.h, p1.m, stream);
+  }
+  GSS_REQUIRE(!prep || (p0.m && prep->idx && prep->pos && prep->b > 0), "spmm_fwd_pair: the batch-preparation side job goes with the Hadamard-fused product");
+  hipStream_t st = as_stream(stream);
+  SpmmSecond second{p1.x, SpmmEpi{}};
+  int rc;
+  if (p0.m) {
+    SpmmEpi ep{p0.h, nullptr, nullptr, p0.y, p0.m, 0.f, nullptr, nullptr, nullptr};
+    if (prep) ep.prep = *prep;
+    second.ep = SpmmEpi{p1.h, nullptr, nullptr, p1.y, p1.m, 0.f, nullptr, nullptr, nullptr};
+    rc = launch_balanced<SPMM_FWD1>(a, d / 4, p0.x, ep, st, &second);
+  } else {
+    SpmmEpi ep{nullptr, nullptr, nullptr, p0.y, nullptr, 0.f, nullptr, nullptr, nullptr};
+    second.ep = SpmmEpi{nullptr, nullptr, nullptr, p1.y, nullptr, 0.f, nullptr, nullptr, nullptr};
+    rc = launch_balanced<SPMM_PLAIN>(a, d / 4, p0.x, ep, st, &second);
+  }
+  if (rc == GSS_OK && paired_out) *paired_out = 1;
+  return rc;
 }
 
 int spmm_bwd1(const gss_csr *at, int32_t d, const float *g_am, const float *g_ax, const float *x_in, const float *ax,
@@ -1310,6 +1403,17 @@ int gss_spmm_filtered(const gss_csr *a, int32_t d, const float *x, float *y, con
                       const uint32_t *row_bits, const float *y_in, const uint32_t *gather_bits, void *stream) {
   GSS_REQUIRE(a && x && y, "gss_spmm_filtered: null operand");
   return spmm_fwd(a, d, x, y, h, m, stream, row_pos, row_bits, y_in, gather_bits);
+}
+// two forward products over one matrix (tests/test_gpu_spmm_pair.py; what the plan's layer-1-ahead launches call): include/gssgcn.h
+int gss_spmm_fwd_pair(const gss_csr *a, int32_t d, const float *x0, float *y0, const float *h0, float *m0, const float *x1, float *y1,
+                      const float *h1, float *m1, const int32_t *prep_idx, int32_t prep_b, const int32_t *prep_node_map, int32_t *prep_rloc,
+                      int32_t *prep_pid, int32_t *prep_pos, int32_t *paired_out, void *stream) {
+  GSS_REQUIRE(a, "gss_spmm_fwd_pair: null handle");
+  const BatchPrep bp{prep_idx, prep_b, prep_node_map, 0, a->n_rows, nullptr, prep_rloc, prep_pid, nullptr, prep_pos, nullptr};
+  int paired = 0;
+  const int rc = spmm_fwd_pair(a, d, SpmmFwdArgs{x0, y0, h0, m0}, SpmmFwdArgs{x1, y1, h1, m1}, stream, prep_idx ? &bp : nullptr, &paired);
+  if (paired_out) *paired_out = paired;
+  return rc;
 }
 int gss_mark_rows_and_neighbours(const gss_csr *a, const int32_t *rows, int32_t b, uint32_t *bits, void *stream) {
   return mark_rows_and_neighbours(a, rows, b, bits, stream);

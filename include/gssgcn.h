@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define GSS_ABI_VERSION 21  /* 21: entry points for tests of the dense half of a plan's step -- gss_dense_fwd_rows, gss_dense_fwd_first, gss_dense_fwd_split_available, gss_dense_fwd_norm, gss_rownorm_fwd_rows, gss_wgrad_slices, gss_wgrad_slices_max, gss_wgrad_partial, gss_wgrad_partial_pair, gss_wgrad_reduce, gss_wgrad_reduce_adam, gss_adam_step4, gss_transpose2; 20: entry points for tests of the loss stages of a plan's step -- gss_loss_step, gss_loss_slab_sweep, gss_loss_workspace_bytes_parts, gss_loss_gather_rows, gss_loss_gather_rows_mapped, gss_loss_gather_batch; loss_step refuses input-gradient weights at widths outside {64, 128, 256}; 19: exact typed top-k selection of listed profile columns and set overlap between selections -- gss_profile_topk, gss_profile_topk_workspace_bytes, gss_topk_overlap; 18: exact average-tie ranks of listed profile columns, the transform behind the spearman distance -- gss_profile_rank, gss_profile_rank_workspace_bytes; 17: gene knock-outs per column of the diffusion profiles -- gss_ppr_set_knockout; distances of listed column pairs of the profile matrix -- gss_profile_dist_pairs, gss_profile_dist_pairs_workspace_bytes; 16: ROC-AUC, average precision and hits@k per row in one launch -- gss_rank_metrics_rows, gss_rank_metrics_workspace_bytes; 15: entry points for tests of the row-sparse SpMM modes -- gss_spmm_bwd1_sparse_ex, gss_spmm_bwd2_sparse_res, gss_spmm_filtered, gss_mark_rows_and_neighbours, gss_batch_bits, gss_bits_fill; 14:indication x drug scores from the embedding tensor -- gss_embedding_scores; 13: pairwise distances between diffusion profiles -- gss_profile_dist; 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
+#define GSS_ABI_VERSION 22  /* 22: two forward products in one launch and layer 1 one pass ahead -- gss_spmm_fwd_pair, gss_plan_l1_ahead, plan option "l1_ahead"; 21: entry points for tests of the dense half of a plan's step -- gss_dense_fwd_rows, gss_dense_fwd_first, gss_dense_fwd_split_available, gss_dense_fwd_norm, gss_rownorm_fwd_rows, gss_wgrad_slices, gss_wgrad_slices_max, gss_wgrad_partial, gss_wgrad_partial_pair, gss_wgrad_reduce, gss_wgrad_reduce_adam, gss_adam_step4, gss_transpose2; 20: entry points for tests of the loss stages of a plan's step -- gss_loss_step, gss_loss_slab_sweep, gss_loss_workspace_bytes_parts, gss_loss_gather_rows, gss_loss_gather_rows_mapped, gss_loss_gather_batch; loss_step refuses input-gradient weights at widths outside {64, 128, 256}; 19: exact typed top-k selection of listed profile columns and set overlap between selections -- gss_profile_topk, gss_profile_topk_workspace_bytes, gss_topk_overlap; 18: exact average-tie ranks of listed profile columns, the transform behind the spearman distance -- gss_profile_rank, gss_profile_rank_workspace_bytes; 17: gene knock-outs per column of the diffusion profiles -- gss_ppr_set_knockout; distances of listed column pairs of the profile matrix -- gss_profile_dist_pairs, gss_profile_dist_pairs_workspace_bytes; 16: ROC-AUC, average precision and hits@k per row in one launch -- gss_rank_metrics_rows, gss_rank_metrics_workspace_bytes; 15: entry points for tests of the row-sparse SpMM modes -- gss_spmm_bwd1_sparse_ex, gss_spmm_bwd2_sparse_res, gss_spmm_filtered, gss_mark_rows_and_neighbours, gss_batch_bits, gss_bits_fill; 14:indication x drug scores from the embedding tensor -- gss_embedding_scores; 13: pairwise distances between diffusion profiles -- gss_profile_dist; 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
 
 #define GSS_OK 0
 #define GSS_EINVAL (-22)   /* bad argument (shape, null pointer, unsupported d) */
@@ -47,8 +47,17 @@ const char *gss_source_hash(const char *file);
 /* measurement aid (tools/ab_live.py): changes one KERNEL-SELECTION knob ("gemm_variant", "gemm_ws", "spmm_slices", "spmm_pin", "spmm_list_blocks") in a live
  * plan's snapshot, so that one plan -- the same buffers at the same addresses --
  * can be timed under alternating settings; knobs that size a workspace or steer the plan's bookkeeping are refused (GSS_EINVAL).
- * Not thread-safe against gss_debug_set_option on another thread. */
+ * Not thread-safe against gss_debug_set_option on another thread.
+ * One name is a PLAN OPTION and exists here only (it is none of the 19 process-wide knobs): "l1_ahead" = -1 (default: automatic) / 0 / 1.
+ * A one-GPU plan with two or more layers and neither cache_layer1 nor pipeline_layer1 computes layer 1's two SpMMs -- functions of
+ * A_hat and X alone -- one pass AHEAD: every full forward pass (gss_plan_step, gss_plan_forward) carries them for the next pass as the
+ * second halves of layer 2's two SpMM launches (gss_spmm_fwd_pair), into the layer-1 buffers themselves, and a pass that finds them there
+ * runs no layer-1 SpMM.  Every step still computes its six products, in ten launches instead of twelve at two layers; same bits.  A lazy
+ * step consumes what a full pass left and leaves nothing.  With profiling on, a paired launch counts as two launches of its class that
+ * share its time.  As with cache_layer1, X and A_hat must not change under a live plan. */
 int gss_plan_debug_set_option(gss_plan *plan, const char *name, int value);
+/* 1 while the plan's layer-1 buffers hold layer 1 for the NEXT forward pass (option "l1_ahead"), else 0 */
+int gss_plan_l1_ahead(const gss_plan *plan);
 const char *gss_last_error(void);
 
 /* ---- K11  preprocess_graph, helpers/helper.py:82-89 (+ fp32 cast helper.py:95) ----------
@@ -873,6 +882,15 @@ int gss_spmm_bwd2_sparse_res(const gss_csr *at, int32_t d, const float *u, const
 int gss_spmm_filtered(const gss_csr *a, int32_t d, const float *x, float *y, const float *h, float *m, const int32_t *row_pos,
                       const uint32_t *row_bits, const float *y_in, const uint32_t *gather_bits, void *stream);
 int gss_mark_rows_and_neighbours(const gss_csr *a, const int32_t *rows, int32_t b, uint32_t *bits, void *stream);
+/* Two unfiltered forward products over ONE matrix: y_k = A x_k and, when m_k is given (for both or for neither), m_k = y_k (.) h_k.  One
+ * launch of twice the workgroups where the balanced SpMM has a paired form -- *paired_out = 1 --, two launches otherwise -- 0: spmm_variant
+ * 1, a matrix with giant rows (gss_csr_giant_rows), an empty matrix.  Either way the bits of two gss_spmm calls.  prep_idx != NULL (needs
+ * m_k): the batch preparation rides in the launch as with a plan's first forward SpMM -- for i < prep_b, r = node_map[idx[i]] (idx[i]
+ * without a map): prep_rloc[i] = prep_pid[i] = r (both nullable), prep_pos[r] = i.  What the second product writes may be what a later
+ * launch gathers; no buffer of one product may be written by the other. */
+int gss_spmm_fwd_pair(const gss_csr *a, int32_t d, const float *x0, float *y0, const float *h0, float *m0, const float *x1, float *y1,
+                      const float *h1, float *m1, const int32_t *prep_idx, int32_t prep_b, const int32_t *prep_node_map, int32_t *prep_rloc,
+                      int32_t *prep_pid, int32_t *prep_pos, int32_t *paired_out, void *stream);
 int gss_batch_bits(const int32_t *ids, int32_t b, uint32_t *bits, int32_t set, void *stream);
 int gss_bits_fill(uint32_t *bits, int64_t first, int64_t last, void *stream);
 
