@@ -9,7 +9,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgssgcn.so")
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 _lib = None
 
@@ -214,6 +214,18 @@ SIGNATURES = {
     "gss_wgrad_reduce_adam": (C.c_int, [_I32, _P, _I32, _I32, _P * 4, _P * 4, _P * 4, _P * 4, _I32, _F, _F, _F, _F, _P, _P, _P, _P, _I32, _P]),
     "gss_adam_step4": (C.c_int, [_P * 4, _P * 4, _P * 4, _P * 4, _I64 * 4, _I32, _F, _F, _F, _F, _P, _P, _I32, _P, _P, _I32, _P]),
     "gss_transpose2": (C.c_int, [_I32, _P, _P, _P, _P, _P]),
+    # for tests: the halo bookkeeping and the batch preparation of a sharded plan (tests/test_gpu_halo_ops.py)
+    "gss_pack_rows": (C.c_int, [_I32, _P, _P, _I64, _P, _P]),
+    "gss_unpack_rows": (C.c_int, [_I32, _P, _P, _I64, _P, _P]),
+    "gss_halo_need_mark": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P]),
+    "gss_send_slot_bits": (C.c_int, [_P, _P, _I32, _P, _P, _I64, _P, _P]),
+    "gss_bits_clear": (C.c_int, [_P, _I64, _I64, _P]),
+    "gss_bits_set_list": (C.c_int, [_P, _P, _I64, _P]),
+    "gss_bits_compact_scratch_bytes": (_SZ, [_I32, _P]),
+    "gss_bits_compact": (C.c_int, [_P, _I32, _P, _P, _P, _P, _I32, _P, _P, _P, _SZ, _P]),
+    "gss_batch_prepare": (C.c_int, [_P, _I32, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "gss_scatter_add_rows_ex": (C.c_int, [_I32, _P, _P, _P, _I32, _P, _P, _P, _P]),
+    "gss_spmm_prep_side": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _I32, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 

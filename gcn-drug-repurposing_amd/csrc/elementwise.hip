@@ -660,4 +660,34 @@ int gss_adam_step4(float *const param[4], const float *const grad[4], float *con
 int gss_transpose2(int32_t dim, const float *a, const float *b, float *at, float *bt, void *stream) {
   return transpose2(dim, a, b, at, bt, stream);
 }
+// for tests (tests/test_gpu_halo_ops.py): the halo bookkeeping and the batch preparation of a sharded plan, as the plan calls them
+int gss_pack_rows(int32_t d, const float *src, const int32_t *rows, int64_t n, float *out, void *stream) {
+  return pack_rows(d, src, rows, n, out, stream);
+}
+int gss_unpack_rows(int32_t d, const float *src, const int32_t *rows, int64_t n, float *dst, void *stream) {
+  return unpack_rows(d, src, rows, n, dst, stream);
+}
+int gss_halo_need_mark(const gss_csr *a, const int32_t *rows, int32_t b, int32_t n, int32_t P, const int64_t *d_recv_off,
+                       const int64_t *d_wrecv_off, uint32_t *needw, void *stream) {
+  return halo_need_mark(a, rows, b, n, P, d_recv_off, d_wrecv_off, needw, stream);
+}
+int gss_send_slot_bits(const uint32_t *bits, const int32_t *send_rows, int32_t P, const int64_t *d_send_off, const int64_t *d_wsend_off,
+                       int64_t n_words, uint32_t *out, void *stream) {
+  return send_slot_bits(bits, send_rows, P, d_send_off, d_wsend_off, n_words, out, stream);
+}
+int gss_bits_clear(uint32_t *bits, int64_t first, int64_t last, void *stream) { return bits_clear(bits, first, last, stream); }
+int gss_bits_set_list(uint32_t *bits, const int32_t *list, int64_t n, void *stream) { return bits_set_list(bits, list, n, stream); }
+size_t gss_bits_compact_scratch_bytes(int32_t P, const int64_t *h_woff) { return bits_compact_scratch_bytes(P, h_woff); }
+int gss_bits_compact(const uint32_t *words, int32_t P, const int64_t *d_woff, const int64_t *h_woff, const int64_t *d_slot_off,
+                     const int32_t *map, int32_t add, int32_t *out, int64_t *d_out_off, void *scratch, size_t scratch_bytes, void *stream) {
+  return bits_compact(words, P, d_woff, h_woff, d_slot_off, map, add, out, d_out_off, stream, scratch, scratch_bytes);
+}
+int gss_batch_prepare(const int32_t *idx, int32_t b, const int32_t *node_map, int32_t lo, int32_t nl, const int32_t *gid2op,
+                      int32_t *rloc, int32_t *pid, float *keep, int32_t *pos, int32_t *rlist, void *stream) {
+  return batch_prepare(idx, b, node_map, lo, nl, gid2op, rloc, pid, keep, pos, stream, rlist);
+}
+int gss_scatter_add_rows_ex(int32_t d, const float *src, const int32_t *rows, const float *keep, int32_t b, float *dst,
+                            int32_t *pos_clear, const int32_t *pos_ids, void *stream) {
+  return scatter_add_rows(d, src, rows, keep, b, dst, pos_clear, pos_ids, stream);
+}
 }

@@ -1418,4 +1418,11 @@ int gss_spmm_fwd_pair(const gss_csr *a, int32_t d, const float *x0, float *y0, c
 int gss_mark_rows_and_neighbours(const gss_csr *a, const int32_t *rows, int32_t b, uint32_t *bits, void *stream) {
   return mark_rows_and_neighbours(a, rows, b, bits, stream);
 }
+// for tests (tests/test_gpu_halo_ops.py): a forward product that carries the batch preparation with every argument of a sharded plan
+int gss_spmm_prep_side(const gss_csr *a, int32_t d, const float *x, float *y, const float *h, float *m, const uint32_t *row_bits,
+                       const int32_t *idx, int32_t b, const int32_t *node_map, int32_t lo, int32_t nl, const int32_t *gid2op,
+                       int32_t *rloc, int32_t *pid, float *keep, int32_t *pos, int32_t *rlist, void *stream) {
+  const BatchPrep bp{idx, b, node_map, lo, nl, gid2op, rloc, pid, keep, pos, rlist};
+  return spmm_fwd(a, d, x, y, h, m, stream, nullptr, row_bits, nullptr, nullptr, &bp);
+}
 }

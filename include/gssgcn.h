@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define GSS_ABI_VERSION 22  /* 22: two forward products in one launch and layer 1 one pass ahead -- gss_spmm_fwd_pair, gss_plan_l1_ahead, plan option "l1_ahead"; 21: entry points for tests of the dense half of a plan's step -- gss_dense_fwd_rows, gss_dense_fwd_first, gss_dense_fwd_split_available, gss_dense_fwd_norm, gss_rownorm_fwd_rows, gss_wgrad_slices, gss_wgrad_slices_max, gss_wgrad_partial, gss_wgrad_partial_pair, gss_wgrad_reduce, gss_wgrad_reduce_adam, gss_adam_step4, gss_transpose2; 20: entry points for tests of the loss stages of a plan's step -- gss_loss_step, gss_loss_slab_sweep, gss_loss_workspace_bytes_parts, gss_loss_gather_rows, gss_loss_gather_rows_mapped, gss_loss_gather_batch; loss_step refuses input-gradient weights at widths outside {64, 128, 256}; 19: exact typed top-k selection of listed profile columns and set overlap between selections -- gss_profile_topk, gss_profile_topk_workspace_bytes, gss_topk_overlap; 18: exact average-tie ranks of listed profile columns, the transform behind the spearman distance -- gss_profile_rank, gss_profile_rank_workspace_bytes; 17: gene knock-outs per column of the diffusion profiles -- gss_ppr_set_knockout; distances of listed column pairs of the profile matrix -- gss_profile_dist_pairs, gss_profile_dist_pairs_workspace_bytes; 16: ROC-AUC, average precision and hits@k per row in one launch -- gss_rank_metrics_rows, gss_rank_metrics_workspace_bytes; 15: entry points for tests of the row-sparse SpMM modes -- gss_spmm_bwd1_sparse_ex, gss_spmm_bwd2_sparse_res, gss_spmm_filtered, gss_mark_rows_and_neighbours, gss_batch_bits, gss_bits_fill; 14:indication x drug scores from the embedding tensor -- gss_embedding_scores; 13: pairwise distances between diffusion profiles -- gss_profile_dist; 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
+#define GSS_ABI_VERSION 23  /* 23: entry points for tests of the halo bookkeeping and the batch preparation of a sharded plan -- gss_pack_rows, gss_unpack_rows, gss_halo_need_mark, gss_send_slot_bits, gss_bits_clear, gss_bits_set_list, gss_bits_compact, gss_bits_compact_scratch_bytes, gss_batch_prepare, gss_scatter_add_rows_ex, gss_spmm_prep_side; 22: two forward products in one launch and layer 1 one pass ahead -- gss_spmm_fwd_pair, gss_plan_l1_ahead, plan option "l1_ahead"; 21: entry points for tests of the dense half of a plan's step -- gss_dense_fwd_rows, gss_dense_fwd_first, gss_dense_fwd_split_available, gss_dense_fwd_norm, gss_rownorm_fwd_rows, gss_wgrad_slices, gss_wgrad_slices_max, gss_wgrad_partial, gss_wgrad_partial_pair, gss_wgrad_reduce, gss_wgrad_reduce_adam, gss_adam_step4, gss_transpose2; 20: entry points for tests of the loss stages of a plan's step -- gss_loss_step, gss_loss_slab_sweep, gss_loss_workspace_bytes_parts, gss_loss_gather_rows, gss_loss_gather_rows_mapped, gss_loss_gather_batch; loss_step refuses input-gradient weights at widths outside {64, 128, 256}; 19: exact typed top-k selection of listed profile columns and set overlap between selections -- gss_profile_topk, gss_profile_topk_workspace_bytes, gss_topk_overlap; 18: exact average-tie ranks of listed profile columns, the transform behind the spearman distance -- gss_profile_rank, gss_profile_rank_workspace_bytes; 17: gene knock-outs per column of the diffusion profiles -- gss_ppr_set_knockout; distances of listed column pairs of the profile matrix -- gss_profile_dist_pairs, gss_profile_dist_pairs_workspace_bytes; 16: ROC-AUC, average precision and hits@k per row in one launch -- gss_rank_metrics_rows, gss_rank_metrics_workspace_bytes; 15: entry points for tests of the row-sparse SpMM modes -- gss_spmm_bwd1_sparse_ex, gss_spmm_bwd2_sparse_res, gss_spmm_filtered, gss_mark_rows_and_neighbours, gss_batch_bits, gss_bits_fill; 14:indication x drug scores from the embedding tensor -- gss_embedding_scores; 13: pairwise distances between diffusion profiles -- gss_profile_dist; 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
 
 #define GSS_OK 0
 #define GSS_EINVAL (-22)   /* bad argument (shape, null pointer, unsupported d) */
@@ -977,6 +977,56 @@ int gss_adam_step4(float *const param[4], const float *const grad[4], float *con
                    int32_t step, float lr, float beta1, float beta2, float eps, float *w1t, float *w2t, int32_t dim, int32_t *pos_clear,
                    const int32_t *ids, int32_t b, void *stream);
 int gss_transpose2(int32_t dim, const float *a, const float *b, float *at, float *bt, void *stream);
+
+/* ---- FOR TESTS: the halo bookkeeping and the batch preparation of a sharded plan, launcher by launcher ---------------------------
+ * A sharded plan's lazy halo and its batch preparation are integers, bitmaps and row copies in csrc/elementwise.hip (and one copy of the
+ * batch preparation in csrc/spmm.hip); these entry points pass their arguments straight through to the launchers the plan calls, so that
+ * tests/test_gpu_halo_ops.py can hold each to its numpy mirror (tests/halo_ops_mirror.py), bit for bit.  Nothing in the product calls them.
+ * THE BITMAP CONTRACTS (what the plan guarantees and every kernel below relies on): bitmaps are uint32 words, bit i = word i >> 5, bit
+ * i & 31.  A bitmap over the slots of P peers is P word RANGES: peer q's slots [off[q], off[q + 1]) are bits 0 .. of the words
+ * [woff[q], woff[q + 1]), woff[q + 1] - woff[q] = ceil((off[q + 1] - off[q]) / 32) -- every range starts on a word, so ranges can be sent
+ * to their peers as they stand.  The PADDING bits of a range's last word are clear, always: a set one would be listed as a slot of the
+ * next peer.  Buffers of woff[P] words are allocated with one guard word more (woff[P] + 1), which no kernel writes.  Offsets are
+ * int64 arrays of P + 1 entries on the device; gss_bits_compact takes the word offsets on the host as well (it sizes its launches by them).
+ *   gss_pack_rows: out[k] = src[rows[k]] for k < n, rows of d floats; rows may repeat.  gss_unpack_rows: dst[rows[k]] = src[k]; rows
+ *     are distinct.  Both copy bits (NaN payloads survive); unlisted rows of the destination are not written.
+ *   gss_halo_need_mark: for the b listed rows of `a` (negative entries skipped), every entry with a column c >= n is halo slot h = c - n
+ *     of the owner q with recv_off[q] <= h < recv_off[q + 1]: needw |= bit (h - recv_off[q]) of q's range.  Nothing is cleared.
+ *   gss_send_slot_bits: out word w of peer q's range = bits[send_rows[s]] of its up to 32 send slots s = send_off[q] + 32 (w -
+ *     wsend_off[q]) ...; all n_words = wsend_off[P] words are written, padding bits as zeros.
+ *   gss_bits_clear: bits [first, last) := 0, other bits untouched; nothing for last <= first.
+ *   gss_bits_set_list: bits[list[k]] := 1 for k < n (ids may repeat, none is negative), other bits untouched.
+ *   gss_bits_compact: the set bits of the P ranges in ascending order as a list: bit j of range q is slot slot_off[q] + j; out holds
+ *     map[slot] (map != NULL) or slot + add.  out_off[q + 1] = entries up to and including range q (out_off[0] = 0); out behind
+ *     out_off[P] is not written.  scratch (nullable): gss_bits_compact_scratch_bytes(P, h_woff) bytes; NULL or fewer bytes: the call
+ *     allocates stream-ordered scratch of its own.
+ *   gss_batch_prepare: for i < b: id = node_map[idx[i]] (idx[i] without a map), rel = id - lo, owned <=> 0 <= rel < nl, op = gid2op[id]
+ *     (without gid2op: rel when owned, -1 when not).  rloc[i] = rel clamped to [0, max(nl - 1, 0)], pid[i] = op, keep[i] = owned as
+ *     1.f / 0.f, rlist[i] = rel when owned and -1 when not (all four nullable), pos[op] = i where op >= 0.  ids with op >= 0 are distinct.
+ *   gss_scatter_add_rows_ex: gss_scatter_add_rows with every argument: member r is skipped when rows[r] < 0 or keep[r] == 0 (keep
+ *     nullable), else dst[rows[r]] += src[r] (kept rows are distinct).  pos_clear (nullable; then pos_ids too): pos_clear[pos_ids[r]] =
+ *     -1 for every r with pos_ids[r] >= 0, skipped members included.
+ *   gss_spmm_prep_side: gss_spmm (Hadamard-fused: m and h given; row_bits nullable as in gss_spmm_filtered) whose launch carries
+ *     gss_batch_prepare's job for the same arguments as one more workgroup; needs the balanced SpMM and b >= 1.  Same bits as the two
+ *     calls apart. */
+int gss_pack_rows(int32_t d, const float *src, const int32_t *rows, int64_t n, float *out, void *stream);
+int gss_unpack_rows(int32_t d, const float *src, const int32_t *rows, int64_t n, float *dst, void *stream);
+int gss_halo_need_mark(const gss_csr *a, const int32_t *rows, int32_t b, int32_t n, int32_t P, const int64_t *d_recv_off,
+                       const int64_t *d_wrecv_off, uint32_t *needw, void *stream);
+int gss_send_slot_bits(const uint32_t *bits, const int32_t *send_rows, int32_t P, const int64_t *d_send_off, const int64_t *d_wsend_off,
+                       int64_t n_words, uint32_t *out, void *stream);
+int gss_bits_clear(uint32_t *bits, int64_t first, int64_t last, void *stream);
+int gss_bits_set_list(uint32_t *bits, const int32_t *list, int64_t n, void *stream);
+size_t gss_bits_compact_scratch_bytes(int32_t P, const int64_t *h_woff);
+int gss_bits_compact(const uint32_t *words, int32_t P, const int64_t *d_woff, const int64_t *h_woff, const int64_t *d_slot_off,
+                     const int32_t *map, int32_t add, int32_t *out, int64_t *d_out_off, void *scratch, size_t scratch_bytes, void *stream);
+int gss_batch_prepare(const int32_t *idx, int32_t b, const int32_t *node_map, int32_t lo, int32_t nl, const int32_t *gid2op,
+                      int32_t *rloc, int32_t *pid, float *keep, int32_t *pos, int32_t *rlist, void *stream);
+int gss_scatter_add_rows_ex(int32_t d, const float *src, const int32_t *rows, const float *keep, int32_t b, float *dst,
+                            int32_t *pos_clear, const int32_t *pos_ids, void *stream);
+int gss_spmm_prep_side(const gss_csr *a, int32_t d, const float *x, float *y, const float *h, float *m, const uint32_t *row_bits,
+                       const int32_t *idx, int32_t b, const int32_t *node_map, int32_t lo, int32_t nl, const int32_t *gid2op,
+                       int32_t *rloc, int32_t *pid, float *keep, int32_t *pos, int32_t *rlist, void *stream);
 
 #ifdef __cplusplus
 }

@@ -543,8 +543,10 @@ def test_lazy_halo_fetches_only_what_the_batch_rows_read(world, case, relabel, s
 
 
 def test_subset_exchanges_at_a_halo_of_several_compaction_trips():
-    """RMAT 600k nodes / 6M edges on two ranks: the request bitmaps are several thousand words long, so the workgroup that lists their set
-    bits (bits_compact_kernel) makes several trips of 1024 words with its running total carried across them and across the peers' ranges.
+    """RMAT 600k nodes / 6M edges on two ranks: the request bitmaps are several thousand words long, so the three kernels that list their
+    set bits (bits_count_kernel, bits_scan_kernel, bits_write_kernel) cut each peer's range into several blocks of 1024 words: every block
+    counts its bits, one workgroup scans the counts into the blocks' bases and the ranges' offsets, every block writes its entries behind
+    its base.  (The scan's second trip -- more than 1024 blocks -- is reached in tests/test_gpu_halo_ops.py, not here.)
     Lazy and full steps with the subset exchanges forced on equal the whole-halo plan's bit for bit."""
     import gcn_drug_repurposing_amd as pkg
     from gcn_drug_repurposing_amd.dist import local_comms
