@@ -9,7 +9,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgssgcn.so")
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 _lib = None
 
@@ -184,6 +184,8 @@ SIGNATURES = {
     "gss_profile_topk_workspace_bytes": (_SZ, [_I32, _I32, _I32, _I32]),
     "gss_profile_topk": (C.c_int, [_I32, _P, _I64, _I32, _P, _I32, _P, _I32, _P, _P, _P, _P, _SZ, _P]),
     "gss_topk_overlap": (C.c_int, [_I32, _I32, _I32, _P, _P, _I32, _P, _P, _P, _P]),
+    "gss_pair_sums_lists": (C.c_int, [_I32, _P, _I64, _I32, _P, _P, _P, _P]),
+    "gss_pair_sums_random": (C.c_int, [_I32, _P, _I64, C.c_uint64, _I64, _I32, _I32, _P, _P, _P, _P]),
     "gss_embedding_scores": (C.c_int, [_I32, _I32, _P, _I64, _I32, _P, _I32, _P, _I32, _P, _I64, _P]),
     # for tests: the row-sparse SpMM modes and their bitmap builders (tests/test_gpu_sparse_ops.py)
     "gss_spmm_bwd1_sparse_ex": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _P]),

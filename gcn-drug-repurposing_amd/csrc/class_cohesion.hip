@@ -1,0 +1,188 @@
+// class_cohesion.hip -- sums of a distance matrix over the pairs of a drug set: of listed sets (gss_pair_sums_lists, the observed statistic of
+// an ATC class) and of the prefixes of seeded random permutations (gss_pair_sums_random, the null of every class size at once).
+//
+// include/gssgcn.h has the contract, DESIGN.md section 9.12 the definitions, the cost model and the measurements.  One statement of the sum
+// serves both entry points (pair_prefix_sums): for an ordered list a[0 .. m) of rows of the symmetric fp64 matrix d,
+//   r_j  = sum over i < j of d[a[j]][a[i]]    one wave per row j: lane l adds the terms i = l, l + 64, ... in ascending order from +0.0, the
+//                                              64 partial sums meet in wave_sum_d's butterfly -- an order that depends on j alone;
+//   T(m) = r_1 + r_2 + ... + r_{m-1}          added in that order by one thread that walks j and writes T at each requested size.
+// So T(m) is a function of the ordered list and d: its bits do not depend on the grid, on the other lists or samples of the call, on the
+// other sizes asked for, or on the chunks the rows are taken in.  Nothing is accumulated with atomics.
+//   cc_lists_kernel    one workgroup per list; the list is read from global memory, r_j goes through an LDS buffer of kCcRowChunk rows;
+//   cc_random_kernel   one workgroup per sample s: the keys rng_key(seed, kRngClassPerm, s, i, 0) of i = 0 .. n - 1 (counter_rng.h) are sorted
+//                      in LDS by (key, i) ascending -- rank_keys.h's bitonic network with the index as the second word of the comparison, so
+//                      that the permutation is a total order and equal keys cannot make it depend on the network -- and the first
+//                      sizes[n_sizes - 1] places are the list; r_j reuses the keys' LDS.
+// The first m places of a uniformly random permutation are a uniformly random m-subset for every m: one permutation per sample serves every size.
+#include "profile_front.h"
+
+#include <memory>
+
+#include "counter_rng.h"
+
+namespace gss {
+namespace {
+
+constexpr int kCcThreads = 256;
+constexpr int kCcWaves = kCcThreads / kWave;
+constexpr int kCcMaxN = 4096;       // the permutation of a sample is sorted in LDS: 4,096 x 12 B
+constexpr int kCcRowChunk = 1024;   // rows of a list whose sums wait in LDS for the walking thread
+
+// r_j of the list a (global memory or LDS); every lane of the wave must reach the call, and every lane returns the sum
+__device__ __forceinline__ double row_pair_sum(const double *__restrict__ d, int64_t ld, const int32_t *a, int32_t j, int lane) {
+  const double *__restrict__ row = d + (int64_t)a[j] * ld;
+  double v = 0.0;
+  for (int32_t i = lane; i < j; i += kWave) v += row[a[i]];
+  return wave_sum_d(v);
+}
+
+// T(sizes[k]) of the list a[0 .. m) -> out[k] for the n_sizes sizes (strictly ascending, in [2, m]); r: LDS, cap doubles.  Rows are taken cap
+// at a time; thread 0 carries T across the chunks.  Made of barriers: EVERY thread of the workgroup must reach the call, with the same m
+__device__ __forceinline__ void pair_prefix_sums(const double *__restrict__ d, int64_t ld, const int32_t *a, int32_t m, const int32_t *sizes,
+                                                 int32_t n_sizes, double *__restrict__ out, double *r, int32_t cap, int32_t tid) {
+  const int wave = tid / kWave, lane = tid % kWave;
+  double T = 0.0;
+  int32_t k = 0;
+  for (int32_t j0 = 1; j0 < m; j0 += cap) {
+    const int32_t j1 = j0 + cap < m ? j0 + cap : m;
+    for (int32_t j = j0 + wave; j < j1; j += kCcWaves) {
+      const double v = row_pair_sum(d, ld, a, j, lane);
+      if (lane == 0) r[j - j0] = v;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      for (int32_t j = j0; j < j1; ++j) {
+        T = j == 1 ? r[0] : T + r[j - j0];
+        if (k < n_sizes && sizes[k] == j + 1) out[k++] = T;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(kCcThreads) void cc_lists_kernel(const double *__restrict__ d, int64_t ld, const int32_t *__restrict__ ptr,
+                                                               const int32_t *__restrict__ idx, double *__restrict__ sum_out) {
+  __shared__ double r[kCcRowChunk];
+  __shared__ int32_t len;
+  const int32_t c = blockIdx.x, tid = threadIdx.x;
+  const int32_t b = ptr[c], m = ptr[c + 1] - b;   // uniform over the workgroup
+  if (m < 2) {
+    if (tid == 0) sum_out[c] = 0.0;
+    return;
+  }
+  if (tid == 0) len = m;
+  __syncthreads();
+  pair_prefix_sums(d, ld, idx + b, m, &len, 1, sum_out + c, r, kCcRowChunk, tid);
+}
+
+// sort_keys (rank_keys.h) over the pairs (key[i], idx[i]), ascending by key, then by index
+__device__ __forceinline__ void sort_pairs(uint64_t *key, int32_t *idx, int32_t cpad, int32_t tid) {
+  for (int32_t k = 2; k <= cpad; k <<= 1) {
+    for (int32_t j = k >> 1; j > 0; j >>= 1) {
+      for (int32_t i = tid; i < cpad / 2; i += kCcThreads) {
+        const int32_t lo = ((i & ~(j - 1)) << 1) | (i & (j - 1)), hi = lo + j;
+        const uint64_t x = key[lo], y = key[hi];
+        const int32_t ix = idx[lo], iy = idx[hi];
+        const bool above = x > y || (x == y && ix > iy);
+        if (above == ((lo & k) == 0)) {
+          key[lo] = y;
+          key[hi] = x;
+          idx[lo] = iy;
+          idx[hi] = ix;
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// sample s0 + blockIdx.x.  LDS: key [cpad] then idx [cpad]; the padding (kBehind, i >= n) sorts behind every (key, i < n)
+__global__ __launch_bounds__(kCcThreads) void cc_random_kernel(int32_t n, const double *__restrict__ d, int64_t ld, uint64_t seed, int64_t s0,
+                                                                int32_t cpad, int32_t n_sizes, const int32_t *__restrict__ sizes, int32_t m_max,
+                                                                double *__restrict__ sums_out, int32_t *__restrict__ perm_out) {
+  extern __shared__ uint64_t cc_lds[];
+  uint64_t *key = cc_lds;
+  int32_t *idx = reinterpret_cast<int32_t *>(key + cpad);
+  const int32_t tid = threadIdx.x;
+  const uint64_t s = (uint64_t)(s0 + blockIdx.x);
+  for (int32_t i = tid; i < cpad; i += kCcThreads) {
+    key[i] = i < n ? rng_key(seed, kRngClassPerm, s, (uint64_t)i, 0) : kBehind;
+    idx[i] = i;
+  }
+  __syncthreads();
+  sort_pairs(key, idx, cpad, tid);
+  if (perm_out)
+    for (int32_t i = tid; i < m_max; i += kCcThreads) perm_out[(int64_t)blockIdx.x * m_max + i] = idx[i];
+  // the keys have done their work: their LDS holds the row sums (m_max - 1 <= cpad of them, one chunk)
+  pair_prefix_sums(d, ld, idx, m_max, sizes, n_sizes, sums_out + (int64_t)blockIdx.x * n_sizes, reinterpret_cast<double *>(key), cpad, tid);
+}
+
+int check_matrix(const char *who, int32_t n, const double *d, int64_t ld) {
+  GSS_REQUIRE(d != nullptr, "%s: d is null", who);
+  GSS_REQUIRE(ld >= n, "%s: ld=%lld is below n=%d", who, (long long)ld, n);
+  return GSS_OK;
+}
+
+}  // namespace
+}  // namespace gss
+
+using namespace gss;
+
+extern "C" {
+
+int gss_pair_sums_lists(int32_t n, const double *d, int64_t ld, int32_t C, const int32_t *ptr, const int32_t *idx, double *sum_out, void *stream) {
+  GSS_REQUIRE(n >= 1, "pair_sums_lists: n=%d must be >= 1", n);
+  if (int rc = check_matrix("pair_sums_lists", n, d, ld)) return rc;
+  GSS_REQUIRE(C >= 0, "pair_sums_lists: C=%d lists must be >= 0", C);
+  if (C == 0) return GSS_OK;
+  GSS_REQUIRE(ptr != nullptr, "pair_sums_lists: ptr is null");
+  GSS_REQUIRE(sum_out != nullptr, "pair_sums_lists: sum_out is null");
+  hipStream_t st = as_stream(stream);
+  std::unique_ptr<int32_t[]> h(new (std::nothrow) int32_t[(size_t)C + 1]);
+  if (!h) return fail(GSS_ENOMEM, "pair_sums_lists: host copy of ptr, %d lists", C);
+  GSS_HIP(hipMemcpyAsync(h.get(), ptr, ((size_t)C + 1) * 4, hipMemcpyDeviceToHost, st));
+  GSS_HIP(hipStreamSynchronize(st));
+  GSS_REQUIRE(h[0] == 0, "pair_sums_lists: ptr[0] = %d must be 0", h[0]);
+  for (int32_t c = 0; c < C; ++c)
+    GSS_REQUIRE(h[c + 1] >= h[c], "pair_sums_lists: ptr[%d] = %d is below ptr[%d] = %d", c + 1, h[c + 1], c, h[c]);
+  const int32_t total = h[C];
+  if (total > 0) {   // nothing reads d through a list before every entry of it is known to be a row; the status words are freed before the launch
+    GSS_REQUIRE(idx != nullptr, "pair_sums_lists: idx is null");
+    DeviceScratch status;
+    GSS_HIP(hipMalloc(&status.p, 8));
+    const CheckedList la{idx, total, 0, n, "idx", "n"}, none{nullptr, 0, 0, 0, "", ""};
+    if (int rc = check_lists("pair_sums_lists", la, none, static_cast<uint32_t *>(status.p), st)) return rc;
+  }
+  hipLaunchKernelGGL(cc_lists_kernel, dim3(C), dim3(kCcThreads), 0, st, d, ld, ptr, idx, sum_out);
+  GSS_LAUNCH_CHECK("cc_lists_kernel");
+  return GSS_OK;
+}
+
+int gss_pair_sums_random(int32_t n, const double *d, int64_t ld, uint64_t seed, int64_t s0, int32_t P, int32_t n_sizes, const int32_t *sizes,
+                         double *sums_out, int32_t *perm_out, void *stream) {
+  GSS_REQUIRE(n >= 2 && n <= kCcMaxN, "pair_sums_random: n=%d is outside [2, %d] (a sample's permutation is sorted in LDS)", n, kCcMaxN);
+  if (int rc = check_matrix("pair_sums_random", n, d, ld)) return rc;
+  GSS_REQUIRE(P >= 1, "pair_sums_random: P=%d samples must be >= 1", P);
+  GSS_REQUIRE(s0 >= 0 && s0 + (int64_t)P <= (int64_t)1 << 31, "pair_sums_random: samples s0=%lld .. s0 + P=%lld are outside [0, 2^31]", (long long)s0,
+              (long long)(s0 + (int64_t)P));
+  GSS_REQUIRE(n_sizes >= 1 && n_sizes <= n - 1, "pair_sums_random: n_sizes=%d is outside [1, n - 1 = %d]", n_sizes, n - 1);
+  GSS_REQUIRE(sizes != nullptr, "pair_sums_random: sizes is null");
+  GSS_REQUIRE(sums_out != nullptr, "pair_sums_random: sums_out is null");
+  hipStream_t st = as_stream(stream);
+  std::unique_ptr<int32_t[]> h(new (std::nothrow) int32_t[(size_t)n_sizes]);
+  if (!h) return fail(GSS_ENOMEM, "pair_sums_random: host copy of %d sizes", n_sizes);
+  GSS_HIP(hipMemcpyAsync(h.get(), sizes, (size_t)n_sizes * 4, hipMemcpyDeviceToHost, st));
+  GSS_HIP(hipStreamSynchronize(st));
+  for (int32_t k = 0; k < n_sizes; ++k) {
+    GSS_REQUIRE(h[k] >= 2 && h[k] <= n, "pair_sums_random: sizes[%d] = %d is outside [2, n=%d]", k, h[k], n);
+    GSS_REQUIRE(k == 0 || h[k] > h[k - 1], "pair_sums_random: sizes[%d] = %d is not above sizes[%d] = %d (strictly ascending)", k, h[k], k - 1,
+                h[k - 1]);
+  }
+  const int32_t cpad = pow2_at_least(n);
+  hipLaunchKernelGGL(cc_random_kernel, dim3(P), dim3(kCcThreads), (size_t)cpad * 12, st, n, d, ld, seed, s0, cpad, n_sizes, sizes, h[n_sizes - 1],
+                     sums_out, perm_out);
+  GSS_LAUNCH_CHECK("cc_random_kernel");
+  return GSS_OK;
+}
+
+}  // extern "C"

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define GSS_ABI_VERSION 23  /* 23: entry points for tests of the halo bookkeeping and the batch preparation of a sharded plan -- gss_pack_rows, gss_unpack_rows, gss_halo_need_mark, gss_send_slot_bits, gss_bits_clear, gss_bits_set_list, gss_bits_compact, gss_bits_compact_scratch_bytes, gss_batch_prepare, gss_scatter_add_rows_ex, gss_spmm_prep_side; 22: two forward products in one launch and layer 1 one pass ahead -- gss_spmm_fwd_pair, gss_plan_l1_ahead, plan option "l1_ahead"; 21: entry points for tests of the dense half of a plan's step -- gss_dense_fwd_rows, gss_dense_fwd_first, gss_dense_fwd_split_available, gss_dense_fwd_norm, gss_rownorm_fwd_rows, gss_wgrad_slices, gss_wgrad_slices_max, gss_wgrad_partial, gss_wgrad_partial_pair, gss_wgrad_reduce, gss_wgrad_reduce_adam, gss_adam_step4, gss_transpose2; 20: entry points for tests of the loss stages of a plan's step -- gss_loss_step, gss_loss_slab_sweep, gss_loss_workspace_bytes_parts, gss_loss_gather_rows, gss_loss_gather_rows_mapped, gss_loss_gather_batch; loss_step refuses input-gradient weights at widths outside {64, 128, 256}; 19: exact typed top-k selection of listed profile columns and set overlap between selections -- gss_profile_topk, gss_profile_topk_workspace_bytes, gss_topk_overlap; 18: exact average-tie ranks of listed profile columns, the transform behind the spearman distance -- gss_profile_rank, gss_profile_rank_workspace_bytes; 17: gene knock-outs per column of the diffusion profiles -- gss_ppr_set_knockout; distances of listed column pairs of the profile matrix -- gss_profile_dist_pairs, gss_profile_dist_pairs_workspace_bytes; 16: ROC-AUC, average precision and hits@k per row in one launch -- gss_rank_metrics_rows, gss_rank_metrics_workspace_bytes; 15: entry points for tests of the row-sparse SpMM modes -- gss_spmm_bwd1_sparse_ex, gss_spmm_bwd2_sparse_res, gss_spmm_filtered, gss_mark_rows_and_neighbours, gss_batch_bits, gss_bits_fill; 14:indication x drug scores from the embedding tensor -- gss_embedding_scores; 13: pairwise distances between diffusion profiles -- gss_profile_dist; 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
+#define GSS_ABI_VERSION 24  /* 24: sums of a distance matrix over the pairs of listed sets and of the prefixes of seeded random permutations, the statistic and the null of ATC class coherence -- gss_pair_sums_lists, gss_pair_sums_random; 23: entry points for tests of the halo bookkeeping and the batch preparation of a sharded plan -- gss_pack_rows, gss_unpack_rows, gss_halo_need_mark, gss_send_slot_bits, gss_bits_clear, gss_bits_set_list, gss_bits_compact, gss_bits_compact_scratch_bytes, gss_batch_prepare, gss_scatter_add_rows_ex, gss_spmm_prep_side; 22: two forward products in one launch and layer 1 one pass ahead -- gss_spmm_fwd_pair, gss_plan_l1_ahead, plan option "l1_ahead"; 21: entry points for tests of the dense half of a plan's step -- gss_dense_fwd_rows, gss_dense_fwd_first, gss_dense_fwd_split_available, gss_dense_fwd_norm, gss_rownorm_fwd_rows, gss_wgrad_slices, gss_wgrad_slices_max, gss_wgrad_partial, gss_wgrad_partial_pair, gss_wgrad_reduce, gss_wgrad_reduce_adam, gss_adam_step4, gss_transpose2; 20: entry points for tests of the loss stages of a plan's step -- gss_loss_step, gss_loss_slab_sweep, gss_loss_workspace_bytes_parts, gss_loss_gather_rows, gss_loss_gather_rows_mapped, gss_loss_gather_batch; loss_step refuses input-gradient weights at widths outside {64, 128, 256}; 19: exact typed top-k selection of listed profile columns and set overlap between selections -- gss_profile_topk, gss_profile_topk_workspace_bytes, gss_topk_overlap; 18: exact average-tie ranks of listed profile columns, the transform behind the spearman distance -- gss_profile_rank, gss_profile_rank_workspace_bytes; 17: gene knock-outs per column of the diffusion profiles -- gss_ppr_set_knockout; distances of listed column pairs of the profile matrix -- gss_profile_dist_pairs, gss_profile_dist_pairs_workspace_bytes; 16: ROC-AUC, average precision and hits@k per row in one launch -- gss_rank_metrics_rows, gss_rank_metrics_workspace_bytes; 15: entry points for tests of the row-sparse SpMM modes -- gss_spmm_bwd1_sparse_ex, gss_spmm_bwd2_sparse_res, gss_spmm_filtered, gss_mark_rows_and_neighbours, gss_batch_bits, gss_bits_fill; 14:indication x drug scores from the embedding tensor -- gss_embedding_scores; 13: pairwise distances between diffusion profiles -- gss_profile_dist; 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
 
 #define GSS_OK 0
 #define GSS_EINVAL (-22)   /* bad argument (shape, null pointer, unsupported d) */
@@ -602,6 +602,33 @@ int gss_profile_topk(int32_t n, const double *x, int64_t ld, int32_t nc, const i
  * untouched. */
 int gss_topk_overlap(int32_t S, int32_t G, int32_t k, const int32_t *idx, const int32_t *cnt, int32_t T, const int32_t *a, const int32_t *b,
                      int32_t *shared, void *stream);
+
+/* ---- sums of a symmetric distance matrix over the pairs of a set: the coherence of a drug class and its null (drug_classes.py; the reference
+ * ships data/drug_classification_df.tsv, multiscale/README.md dataset 7, and has no code that reads it)
+ * d: device fp64 [n][ld], ld >= n, assumed symmetric (diffusion.compare_profiles' drug x drug matrix is, bit for bit); only d[a][b] with a
+ * later in its list than b is read.  For an ordered list a[0 .. m):
+ *   r_j  = sum over i < j of d[a[j]][a[i]]: the 64 partial sums p[l] = the terms i = l, l + 64, l + 128 ... (ascending, from +0.0), combined
+ *          by the butterfly p[l] = p[l] + p[l ^ o] for o = 32, 16, 8, 4, 2, 1 -- an order that depends on j alone;
+ *   T(m) = r_1 + r_2 + ... + r_{m-1}, added in that order (T(2) = r_1).
+ * T is a function of the ordered list and d only: bit-equal run to run, under any grid, whatever other lists, samples or sizes the call
+ * carries, and between the two entry points.  Nothing is accumulated with atomics.
+ * gss_pair_sums_lists: C lists in CSR form, device int32 ptr [C + 1] (ptr[0] = 0, non-decreasing) and idx [ptr[C]] with entries in [0, n),
+ * honoured as given (any order, repeats allowed, any length) -> device fp64 sum_out [C], sum_out[c] = T(length) of list c; a list shorter
+ * than 2 gives 0.0.  One workgroup per list.  C = 0 is a no-op.  Refuses (GSS_EINVAL, by name): n < 1, a null d, ptr, sum_out or (with an
+ * entry to read) idx, ld < n, C < 0, a ptr that is no CSR row pointer, and an idx entry outside [0, n) (by position and value: one check
+ * launch, before anything reads d through the list); sum_out is then untouched.  Reads ptr back and synchronises the stream. */
+int gss_pair_sums_lists(int32_t n, const double *d, int64_t ld, int32_t C, const int32_t *ptr, const int32_t *idx, double *sum_out, void *stream);
+/* gss_pair_sums_random: the same sums over random sets.  For sample s = s0 .. s0 + P - 1: key_i = rng_key(seed, kRngClassPerm = 9, s, i, 0)
+ * (csrc/counter_rng.h) for i in [0, n), pi_s = 0 .. n - 1 sorted by (key, i) ascending -- a pure function of (seed, s, n), replayable in numpy
+ * (tests/class_cohesion_mirror.py) -- and sums_out[s - s0][k] = T(sizes[k]) of pi_s: the first m places of a uniformly random permutation are
+ * a uniformly random m-subset for every m, so one permutation serves every size.  sizes: device int32 [n_sizes], strictly ascending in
+ * [2, n]; sums_out: device fp64 [P][n_sizes]; perm_out: null, or device int32 [P][sizes[n_sizes - 1]], the prefix of pi_s.  One workgroup per
+ * sample; the permutation is sorted in LDS, hence n <= 4096.  Samples are numbered, not drawn: a call over [s0, s0 + P) equals the same
+ * samples in any split.  Refuses (GSS_EINVAL, by name): n outside [2, 4096], a null d, sizes or sums_out, ld < n, P < 1, s0 < 0 or
+ * s0 + P > 2^31, n_sizes outside [1, n - 1], a size outside [2, n] or not above its predecessor; the outputs are then untouched.  Reads
+ * sizes back and synchronises the stream. */
+int gss_pair_sums_random(int32_t n, const double *d, int64_t ld, uint64_t seed, int64_t s0, int32_t P, int32_t n_sizes, const int32_t *sizes,
+                         double *sums_out, int32_t *perm_out, void *stream);
 
 /* ---- inner-product scores between listed embedding rows (predict_drug.py:52-66: sklearn.preprocessing.normalize, then np.matmul)
  * gss_embedding_scores: device fp32 emb [n][ld], ld >= d (a plan's embedding tensor with its zero padding); device int32 index lists rows
