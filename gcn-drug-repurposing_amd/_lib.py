@@ -9,7 +9,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgssgcn.so")
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 _lib = None
 
@@ -186,6 +186,7 @@ SIGNATURES = {
     "gss_topk_overlap": (C.c_int, [_I32, _I32, _I32, _P, _P, _I32, _P, _P, _P, _P]),
     "gss_pair_sums_lists": (C.c_int, [_I32, _P, _I64, _I32, _P, _P, _P, _P]),
     "gss_pair_sums_random": (C.c_int, [_I32, _P, _I64, C.c_uint64, _I64, _I32, _I32, _P, _P, _P, _P]),
+    "gss_resample_stats": (C.c_int, [_P, _I64, _I32, _I32, _I32, C.c_uint64, _I64, _I64, _P, _P]),
     "gss_embedding_scores": (C.c_int, [_I32, _I32, _P, _I64, _I32, _P, _I32, _P, _I32, _P, _I64, _P]),
     # for tests: the row-sparse SpMM modes and their bitmap builders (tests/test_gpu_sparse_ops.py)
     "gss_spmm_bwd1_sparse_ex": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _P]),

@@ -11,6 +11,9 @@ section 9.4 has the contract decisions and the measurements.
 
 --metrics adds average precision and recall@K beside the AUC (csrc/rank_metrics.hip: all three in one launch in place of auc.hip's;
 DESIGN.md section 9.8).  Without it nothing here launches or prints anything it did not before.
+
+--bootstrap B adds, behind those lines, one line per reported metric with the percentile intervals of its median and mean over B bootstrap
+resamples of the indications (csrc/resample.hip through resample.bootstrap_summary).  The same holds without it.
 """
 from __future__ import annotations
 
@@ -49,6 +52,10 @@ def parse_args(argv=None):
     p.add_argument("--metrics", default=None, type=str,
                    help="comma-separated ranking statistics to report after the AUC line, one line each: ap (average precision), "
                         f"recall@K (K >= 1, at most {MAX_CUTS} distinct K), auc; --per-indication gains one column per metric")
+    p.add_argument("--bootstrap", default=None, type=int,
+                   help="also print, per reported metric, the percentile intervals of the median and the mean over this many bootstrap "
+                        "resamples of the indications (seeded by --seed)")
+    p.add_argument("--level", default=0.95, type=float, help="coverage of the --bootstrap intervals (default: 0.95)")
     return p.parse_args(argv)
 
 
@@ -162,6 +169,22 @@ def format_metric_line(name, values):
     """the AUC line's f-string with the metric's name"""
     a = np.asarray(values, dtype=np.float64)
     return f"median {name}: {np.median(a)}, mean {name}: {a.mean()}"
+
+
+def format_bootstrap_line(name, s, B, seed):
+    """one line of --bootstrap from resample.bootstrap_summary's record of the metric"""
+    return (f"bootstrap {name}: median [{s['median']['lo']}, {s['median']['hi']}], mean [{s['mean']['lo']}, {s['mean']['hi']}] "
+            f"({B} resamples, seed {seed})")
+
+
+def bootstrap_lines(res, B, level, seed, summary=None):
+    """the lines of --bootstrap for Result res: the AUC and then every requested metric, over the AUC line's indications, all resampled
+    together (csrc/resample.hip through resample.bootstrap_summary, or `summary` in its place)"""
+    if summary is None:
+        from .resample import bootstrap_summary as summary
+    series = {"auc": res.auc[res.kept]}
+    series.update({name: v[res.kept] for name, v in res.metrics.items()})
+    return [format_bootstrap_line(name, s, B, seed) for name, s in summary(series, B, seed, level).items()]
 
 
 def _device_inputs(who, scores, pos_ptr, pos_col):
@@ -525,15 +548,22 @@ def main(argv=None, auc_source=device_aucs, metric_source=device_metrics):
     args = parse_args(argv)
     try:
         metrics = parse_metrics(args.metrics) if args.metrics is not None else []
+        if args.bootstrap is not None and args.bootstrap < 2:
+            raise PredictError(f"--bootstrap {args.bootstrap} must be at least 2")
+        if not 0.0 < args.level < 1.0:
+            raise PredictError(f"--level {args.level} must lie strictly between 0 and 1")
         s = Settings(load_config(args.config))
     except (PredictError, OSError, json.JSONDecodeError) as e:
         print(f"evaluate_auc: {e}", file=sys.stderr)
         sys.exit(2)
     try:
         res = run(s, args.seed, args.per_indication, auc_source=auc_source, metrics=metrics, metric_source=metric_source)
+        extra = bootstrap_lines(res, args.bootstrap, args.level, args.seed) if args.bootstrap is not None else []
     except (PredictError, OSError) as e:
         print(f"evaluate_auc: {e}", file=sys.stderr)
         sys.exit(2)
     print(res.line)
     for line in res.metric_lines:
+        print(line)
+    for line in extra:
         print(line)
