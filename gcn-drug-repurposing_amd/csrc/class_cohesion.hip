@@ -138,20 +138,18 @@ int gss_pair_sums_lists(int32_t n, const double *d, int64_t ld, int32_t C, const
   GSS_REQUIRE(ptr != nullptr, "pair_sums_lists: ptr is null");
   GSS_REQUIRE(sum_out != nullptr, "pair_sums_lists: sum_out is null");
   hipStream_t st = as_stream(stream);
-  std::unique_ptr<int32_t[]> h(new (std::nothrow) int32_t[(size_t)C + 1]);
-  if (!h) return fail(GSS_ENOMEM, "pair_sums_lists: host copy of ptr, %d lists", C);
-  GSS_HIP(hipMemcpyAsync(h.get(), ptr, ((size_t)C + 1) * 4, hipMemcpyDeviceToHost, st));
-  GSS_HIP(hipStreamSynchronize(st));
+  std::unique_ptr<int32_t[]> h;
+  if (int rc = host_copy(h, ptr, (size_t)C + 1, st, "pair_sums_lists: host copy of ptr, %d lists", C)) return rc;
   GSS_REQUIRE(h[0] == 0, "pair_sums_lists: ptr[0] = %d must be 0", h[0]);
   for (int32_t c = 0; c < C; ++c)
     GSS_REQUIRE(h[c + 1] >= h[c], "pair_sums_lists: ptr[%d] = %d is below ptr[%d] = %d", c + 1, h[c + 1], c, h[c]);
   const int32_t total = h[C];
   if (total > 0) {   // nothing reads d through a list before every entry of it is known to be a row; the status words are freed before the launch
     GSS_REQUIRE(idx != nullptr, "pair_sums_lists: idx is null");
-    DeviceScratch status;
-    GSS_HIP(hipMalloc(&status.p, 8));
+    DeviceBuf<uint32_t> status;
+    if (int rc = status.alloc("pair_sums_lists", 8)) return rc;
     const CheckedList la{idx, total, 0, n, "idx", "n"}, none{nullptr, 0, 0, 0, "", ""};
-    if (int rc = check_lists("pair_sums_lists", la, none, static_cast<uint32_t *>(status.p), st)) return rc;
+    if (int rc = check_lists("pair_sums_lists", la, none, status.p, st)) return rc;
   }
   hipLaunchKernelGGL(cc_lists_kernel, dim3(C), dim3(kCcThreads), 0, st, d, ld, ptr, idx, sum_out);
   GSS_LAUNCH_CHECK("cc_lists_kernel");
@@ -169,10 +167,8 @@ int gss_pair_sums_random(int32_t n, const double *d, int64_t ld, uint64_t seed, 
   GSS_REQUIRE(sizes != nullptr, "pair_sums_random: sizes is null");
   GSS_REQUIRE(sums_out != nullptr, "pair_sums_random: sums_out is null");
   hipStream_t st = as_stream(stream);
-  std::unique_ptr<int32_t[]> h(new (std::nothrow) int32_t[(size_t)n_sizes]);
-  if (!h) return fail(GSS_ENOMEM, "pair_sums_random: host copy of %d sizes", n_sizes);
-  GSS_HIP(hipMemcpyAsync(h.get(), sizes, (size_t)n_sizes * 4, hipMemcpyDeviceToHost, st));
-  GSS_HIP(hipStreamSynchronize(st));
+  std::unique_ptr<int32_t[]> h;
+  if (int rc = host_copy(h, sizes, (size_t)n_sizes, st, "pair_sums_random: host copy of %d sizes", n_sizes)) return rc;
   for (int32_t k = 0; k < n_sizes; ++k) {
     GSS_REQUIRE(h[k] >= 2 && h[k] <= n, "pair_sums_random: sizes[%d] = %d is outside [2, n=%d]", k, h[k], n);
     GSS_REQUIRE(k == 0 || h[k] > h[k - 1], "pair_sums_random: sizes[%d] = %d is not above sizes[%d] = %d (strictly ascending)", k, h[k], k - 1,

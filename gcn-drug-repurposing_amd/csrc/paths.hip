@@ -12,20 +12,24 @@
 // on results: bitwise deterministic); the only atomic is the per-level "something changed" flag the host reads.
 #include <algorithm>
 
-#include "common.h"
+#include "device_scope.h"
 #include "ops.h"
 
-struct gss_paths {
+struct PathsWords {            // what the kernels report through, on the device and as a pinned host copy
+  int32_t flag;                // a level's word: 1 changed, 2 a node 255+ hops away, 4 a bad column
+  unsigned long long status;   // the status of a count pass (trace.hip)
+};
+
+struct __attribute__((visibility("hidden"))) gss_paths {
   int32_t n;
   int64_t nnz;
   int64_t max_bytes;
   const int32_t *rowptr, *col;   // device CSR (owned when uploaded)
-  int32_t *own_rowptr, *own_col;
-  uint64_t *seen, *front[2];     // [n] each: 24 n bytes of state
-  int32_t *flag;                 // device word: 1 changed, 2 a node 255+ hops away, 4 a bad column; the 64-bit word behind it (flag + 2) is
-                                 // the status of a count pass (trace.hip)
-  int32_t *h_flag;               // pinned host copy (4 words as well)
-  int32_t *targets;              // [kMaxTargets] device
+  gss::DeviceBuf<int32_t> own_rowptr, own_col;
+  gss::DeviceBuf<uint64_t> seen, front[2];   // [n] each: 24 n bytes of state
+  gss::DeviceBuf<PathsWords> words;
+  gss::DeviceBuf<PathsWords, true> h_words;
+  gss::DeviceBuf<int32_t> targets;   // [kMaxTargets] device
 };
 
 namespace gss {
@@ -172,13 +176,6 @@ __global__ __launch_bounds__(kLevelThreads) void paths_level_kernel(LevelArgs a)
   if (lane == 0 && (any_changed || any_bad)) atomicOr(a.flag, (any_changed ? (probe ? 2 : 1) : 0) | (any_bad ? 4 : 0));
 }
 
-int read_flag(gss_paths *p, hipStream_t st, int32_t *out) {
-  GSS_HIP(hipMemcpyAsync(p->h_flag, p->flag, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  GSS_HIP(hipStreamSynchronize(st));
-  *out = *p->h_flag;
-  return GSS_OK;
-}
-
 }  // namespace
 
 // what a count pass (trace.hip) needs of a handle
@@ -188,9 +185,9 @@ int paths_view(const gss_paths *p, PathsView *out) {
   out->max_bytes = p->max_bytes;
   out->rowptr = p->rowptr;
   out->col = p->col;
-  out->targets = p->targets;
-  out->status = reinterpret_cast<unsigned long long *>(p->flag + 2);
-  out->h_status = reinterpret_cast<unsigned long long *>(p->h_flag + 2);
+  out->targets = p->targets.p;
+  out->status = &p->words.p->status;
+  out->h_status = &p->h_words.p->status;
   return GSS_OK;
 }
 
@@ -212,63 +209,37 @@ int gss_paths_create(gss_paths **out, int32_t n, int64_t nnz, const int32_t *row
               "paths_create: one target needs %lld bytes (24 N of state + 5 N of output, N=%d), above the budget max_bytes=%lld",
               (long long)(state + (int64_t)5 * n), n, (long long)max_bytes);
   hipStream_t st = as_stream(stream);
-  gss_paths *p = new gss_paths();
+  std::unique_ptr<gss_paths> p(new gss_paths());
   p->n = n;
   p->nnz = nnz;
   p->max_bytes = max_bytes;
-  bool ok = hipMalloc((void **)&p->seen, (size_t)n * 8) == hipSuccess && hipMalloc((void **)&p->front[0], (size_t)n * 8) == hipSuccess &&
-            hipMalloc((void **)&p->front[1], (size_t)n * 8) == hipSuccess && hipMalloc((void **)&p->flag, 4 * sizeof(int32_t)) == hipSuccess &&
-            hipMalloc((void **)&p->targets, kMaxTargets * sizeof(int32_t)) == hipSuccess &&
-            hipHostMalloc((void **)&p->h_flag, 4 * sizeof(int32_t)) == hipSuccess;
-  if (ok && !on_device) {
-    ok = hipMalloc((void **)&p->own_rowptr, (size_t)(n + 1) * 4) == hipSuccess &&
-         hipMalloc((void **)&p->own_col, (size_t)std::max<int64_t>(nnz, 1) * 4) == hipSuccess;
-  }
-  if (!ok) {
-    gss_paths_destroy(p);
+  const char *who = "paths_create";
+  if (p->seen.alloc(who, (size_t)n * 8) || p->front[0].alloc(who, (size_t)n * 8) || p->front[1].alloc(who, (size_t)n * 8) ||
+      p->words.alloc(who, sizeof(PathsWords)) || p->targets.alloc(who, kMaxTargets * sizeof(int32_t)) || p->h_words.alloc(who, sizeof(PathsWords)) ||
+      (!on_device && (p->own_rowptr.alloc(who, (size_t)(n + 1) * 4) || p->own_col.alloc(who, (size_t)std::max<int64_t>(nnz, 1) * 4))))
     return fail(GSS_ENOMEM, "paths_create: device allocation failed (N=%d, nnz=%lld)", n, (long long)nnz);
-  }
-  int rc = GSS_OK;
   if (!on_device) {
-    if (hipMemcpyAsync(p->own_rowptr, rowptr, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
-        (nnz && hipMemcpyAsync(p->own_col, col, (size_t)nnz * 4, hipMemcpyHostToDevice, st) != hipSuccess))
-      rc = fail(GSS_EHIP, "paths_create: graph upload failed");
-    p->rowptr = p->own_rowptr;
-    p->col = p->own_col;
+    GSS_HIP(hipMemcpyAsync(p->own_rowptr.p, rowptr, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, st));
+    if (nnz) GSS_HIP(hipMemcpyAsync(p->own_col.p, col, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
+    p->rowptr = p->own_rowptr.p;
+    p->col = p->own_col.p;
   } else {
     p->rowptr = rowptr;
     p->col = col;
   }
-  int32_t flag = 0;
-  if (rc == GSS_OK && hipMemsetAsync(p->flag, 0, sizeof(int32_t), st) != hipSuccess) rc = fail(GSS_EHIP, "paths_create: memset failed");
-  if (rc == GSS_OK) {
-    paths_check_kernel<<<ceil_div(n, 256), 256, 0, st>>>(n, nnz, p->rowptr, p->col, p->flag);
-    if (hipGetLastError() != hipSuccess) rc = fail(GSS_EHIP, "paths_create: launch paths_check_kernel failed");
-  }
-  if (rc == GSS_OK) rc = read_flag(p, st, &flag);
-  if (rc == GSS_OK && (flag & 1)) rc = fail(GSS_EINVAL, "paths_create: rowptr is not a CSR row pointer (0 first, non-decreasing, <= nnz=%lld)", (long long)nnz);
-  if (rc == GSS_OK && (flag & 2)) rc = fail(GSS_EINVAL, "paths_create: a column index is outside [0, %d)", n);
-  if (rc == GSS_OK && (flag & 4)) rc = fail(GSS_EINVAL, "paths_create: the columns of a row are not ascending (the tie rule needs row order = index order)");
-  if (rc != GSS_OK) {
-    gss_paths_destroy(p);
-    return rc;
-  }
-  *out = p;
+  int32_t *flag = &p->words.p->flag, *h_flag = &p->h_words.p->flag;
+  GSS_HIP(hipMemsetAsync(flag, 0, sizeof(int32_t), st));
+  paths_check_kernel<<<ceil_div(n, 256), 256, 0, st>>>(n, nnz, p->rowptr, p->col, flag);
+  GSS_LAUNCH_CHECK("paths_check_kernel");
+  if (int rc = read_back(h_flag, flag, sizeof(int32_t), st)) return rc;
+  GSS_REQUIRE(!(*h_flag & 1), "paths_create: rowptr is not a CSR row pointer (0 first, non-decreasing, <= nnz=%lld)", (long long)nnz);
+  GSS_REQUIRE(!(*h_flag & 2), "paths_create: a column index is outside [0, %d)", n);
+  GSS_REQUIRE(!(*h_flag & 4), "paths_create: the columns of a row are not ascending (the tie rule needs row order = index order)");
+  *out = p.release();
   return GSS_OK;
 }
 
-void gss_paths_destroy(gss_paths *p) {
-  if (!p) return;
-  (void)hipFree(p->seen);
-  (void)hipFree(p->front[0]);
-  (void)hipFree(p->front[1]);
-  (void)hipFree(p->flag);
-  (void)hipFree(p->targets);
-  (void)hipFree(p->own_rowptr);
-  (void)hipFree(p->own_col);
-  if (p->h_flag) (void)hipHostFree(p->h_flag);
-  delete p;
-}
+void gss_paths_destroy(gss_paths *p) { delete p; }
 
 int gss_paths_run(gss_paths *p, int32_t q, const int32_t *targets, uint8_t *dist, int32_t *next, int32_t *levels, void *stream) {
   GSS_REQUIRE(p && targets && dist && next, "paths_run: null argument");
@@ -279,28 +250,29 @@ int gss_paths_run(gss_paths *p, int32_t q, const int32_t *targets, uint8_t *dist
   GSS_REQUIRE(need <= p->max_bytes, "paths_run: the pass needs %lld bytes (5 Q N of output + 24 N of state, Q=%d N=%d), above the budget max_bytes=%lld",
               (long long)need, q, p->n, (long long)p->max_bytes);
   hipStream_t st = as_stream(stream);
-  GSS_HIP(hipMemcpyAsync(p->targets, targets, (size_t)q * 4, hipMemcpyHostToDevice, st));
-  paths_init_kernel<<<ceil_div(p->n, 256), 256, 0, st>>>(p->n, q, p->targets, p->seen, p->front[0], dist, next);
+  GSS_HIP(hipMemcpyAsync(p->targets.p, targets, (size_t)q * 4, hipMemcpyHostToDevice, st));
+  paths_init_kernel<<<ceil_div(p->n, 256), 256, 0, st>>>(p->n, q, p->targets.p, p->seen.p, p->front[0].p, dist, next);
   GSS_LAUNCH_CHECK("paths_init_kernel");
   LevelArgs a;
   a.n = p->n;
   a.valid = q == 64 ? ~0ull : ((1ull << q) - 1);
   a.rowptr = p->rowptr;
   a.col = p->col;
-  a.seen = p->seen;
+  a.seen = p->seen.p;
   a.dist = dist;
   a.next = next;
-  a.flag = p->flag;
+  a.flag = &p->words.p->flag;
+  int32_t *h_flag = &p->h_words.p->flag;
   int32_t level = 0;
   for (int32_t L = 1;; ++L) {
     a.level = L;
-    a.front_cur = p->front[(L - 1) & 1];
-    a.front_next = p->front[L & 1];
-    GSS_HIP(hipMemsetAsync(p->flag, 0, sizeof(int32_t), st));
+    a.front_cur = p->front[(L - 1) & 1].p;
+    a.front_next = p->front[L & 1].p;
+    GSS_HIP(hipMemsetAsync(a.flag, 0, sizeof(int32_t), st));
     paths_level_kernel<<<ceil_div(p->n, kLevelThreads), kLevelThreads, 0, st>>>(a);
     GSS_LAUNCH_CHECK("paths_level_kernel");
-    int32_t flag = 0;
-    if (int rc = read_flag(p, st, &flag)) return rc;
+    if (int rc = read_back(h_flag, a.flag, sizeof(int32_t), st)) return rc;
+    const int32_t flag = *h_flag;
     GSS_REQUIRE(!(flag & 4), "paths_run: a column index is outside [0, %d)", p->n);
     GSS_REQUIRE(!(flag & 2), "paths_run: a node lies 255 or more hops from a target; hop counts are stored in one byte (depth <= %d)",
                 kMaxLevel);

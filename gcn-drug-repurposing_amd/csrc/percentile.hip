@@ -8,6 +8,7 @@
 // One-time setup work; MFMA-bound (2 N^2 d / 2 flops per pass).
 #include <vector>
 
+#include "device_scope.h"
 #include "ops.h"
 
 namespace gss {
@@ -123,31 +124,22 @@ extern "C" int gss_percentile(int32_t n, int32_t d, const float *e, double q, fl
   const double frac = pos - (double)lo;
   const unsigned long long hi = lo + 1 < M ? lo + 1 : M - 1;
 
-  unsigned long long *d_hist = nullptr;
-  uint32_t *d_min = nullptr;
-  GSS_HIP(hipMalloc((void **)&d_hist, sizeof(unsigned long long) * 2048 + 16));
-  d_min = reinterpret_cast<uint32_t *>(d_hist + 2048);
+  DeviceBuf<unsigned long long> hist;   // 2048 bins, then the min pass's word
+  if (int rc = hist.alloc("percentile", sizeof(unsigned long long) * 2048 + 16)) return rc;
+  uint32_t *d_min = reinterpret_cast<uint32_t *>(hist.p + 2048);
   std::vector<unsigned long long> h_hist(2048);
   const int nt = ceil_div(n, 64);
   dim3 grid(nt, nt), block(256);
-  PctArgs g{n, d, e, 0u, 0u, 0, 0, d_hist, 0u, d_min};
+  PctArgs g{n, d, e, 0u, 0u, 0, 0, hist.p, 0u, d_min};
   const int shifts[3] = {21, 10, 0}, bits[3] = {11, 11, 10};
   unsigned long long rank = lo, eq_count = 0;
-  int rc = GSS_OK;
-  for (int pass = 0; pass < 3 && rc == GSS_OK; ++pass) {
+  for (int pass = 0; pass < 3; ++pass) {
     g.shift = shifts[pass];
     g.nbits = bits[pass];
-    hipError_t err = hipMemsetAsync(d_hist, 0, sizeof(unsigned long long) * 2048, st);
-    if (err == hipSuccess) {
-      hipLaunchKernelGGL((pct_kernel<0>), grid, block, 0, st, g);
-      err = hipGetLastError();
-    }
-    if (err == hipSuccess) err = hipMemcpyAsync(h_hist.data(), d_hist, sizeof(unsigned long long) * (1u << g.nbits), hipMemcpyDeviceToHost, st);
-    if (err == hipSuccess) err = hipStreamSynchronize(st);
-    if (err != hipSuccess) {
-      rc = fail(GSS_EHIP, "percentile pass %d: %s", pass, hipGetErrorString(err));
-      break;
-    }
+    GSS_HIP(hipMemsetAsync(hist.p, 0, sizeof(unsigned long long) * 2048, st));
+    hipLaunchKernelGGL((pct_kernel<0>), grid, block, 0, st, g);
+    GSS_LAUNCH_CHECK("pct_kernel<0>");
+    if (int rc = read_back(h_hist.data(), hist.p, sizeof(unsigned long long) * (1u << g.nbits), st)) return rc;
     unsigned long long cum = 0;
     int chosen = -1;
     for (int b = 0; b < (1 << g.nbits); ++b) {
@@ -157,40 +149,26 @@ extern "C" int gss_percentile(int32_t n, int32_t d, const float *e, double q, fl
       }
       cum += h_hist[b];
     }
-    if (chosen < 0) {
-      rc = fail(GSS_EHIP, "percentile: rank %llu not found in pass %d (NaN in the embeddings?)", rank, pass);
-      break;
-    }
+    if (chosen < 0) return fail(GSS_EHIP, "percentile: rank %llu not found in pass %d (NaN in the embeddings?)", rank, pass);
     rank -= cum;
     eq_count = h_hist[chosen];
     g.prefix |= (uint32_t)chosen << g.shift;
     g.mask |= ((1u << g.nbits) - 1u) << g.shift;
   }
-  if (rc == GSS_OK) {
-    const uint32_t key_lo = g.prefix;
-    uint32_t key_hi = key_lo;
-    // `rank` is now the 0-based position of the wanted element inside its final (single-value) bin
-    if (hi != lo && rank + 1 >= eq_count) {
-      const uint32_t init = 0xffffffffu;
-      hipError_t err = hipMemcpyAsync(d_min, &init, 4, hipMemcpyHostToDevice, st);
-      g.floor_key = key_lo;
-      if (err == hipSuccess) {
-        hipLaunchKernelGGL((pct_kernel<1>), grid, block, 0, st, g);
-        err = hipGetLastError();
-      }
-      uint32_t got = init;
-      if (err == hipSuccess) err = hipMemcpyAsync(&got, d_min, 4, hipMemcpyDeviceToHost, st);
-      if (err == hipSuccess) err = hipStreamSynchronize(st);
-      if (err != hipSuccess)
-        rc = fail(GSS_EHIP, "percentile min pass: %s", hipGetErrorString(err));
-      else if (got != init)
-        key_hi = got;
-    }
-    if (rc == GSS_OK) {
-      const float a = key_to_float(key_lo), b = key_to_float(key_hi);
-      *h_out = (float)((double)a + ((double)b - (double)a) * frac);  // numpy 'linear' interpolation
-    }
+  const uint32_t key_lo = g.prefix;
+  uint32_t key_hi = key_lo;
+  // `rank` is now the 0-based position of the wanted element inside its final (single-value) bin
+  if (hi != lo && rank + 1 >= eq_count) {
+    const uint32_t init = 0xffffffffu;
+    GSS_HIP(hipMemcpyAsync(d_min, &init, 4, hipMemcpyHostToDevice, st));
+    g.floor_key = key_lo;
+    hipLaunchKernelGGL((pct_kernel<1>), grid, block, 0, st, g);
+    GSS_LAUNCH_CHECK("pct_kernel<1>");
+    uint32_t got = init;
+    if (int rc = read_back(&got, d_min, 4, st)) return rc;
+    if (got != init) key_hi = got;
   }
-  (void)hipFree(d_hist);
-  return rc;
+  const float a = key_to_float(key_lo), b = key_to_float(key_hi);
+  *h_out = (float)((double)a + ((double)b - (double)a) * frac);  // numpy 'linear' interpolation
+  return GSS_OK;
 }

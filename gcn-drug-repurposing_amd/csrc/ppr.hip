@@ -18,13 +18,16 @@
 #include <utility>
 #include <vector>
 
+#include "device_scope.h"
 #include "ops.h"
 
-struct gss_ppr {
+struct __attribute__((visibility("hidden"))) gss_ppr {
   gss_ppr_desc d;
-  gss_csr *csr;       // structure handle for the segment schedule
-  char *slab;
-  size_t slab_bytes;
+  gss_csr *csr = nullptr;   // structure handle for the segment schedule (owned)
+  ~gss_ppr() {
+    if (csr) gss_csr_destroy(csr);
+  }
+  gss::DeviceBuf<char> slab;
   std::vector<size_t> guard_off;   // slab offsets of the guards behind the carved buffers
   double *y;          // [n][kpad]
   double *stash_o;    // [n_ovr]
@@ -525,19 +528,14 @@ int gss_ppr_create(gss_ppr **out, const gss_ppr_desc *desc) {
                   D.n_sel >= 0 && (D.n_sel == 0 || (D.sel_col && D.sel_row && D.sel_val)),
               "ppr_create: empty-row / override / start-row lists missing");
   GSS_REQUIRE((double)D.n * D.kpad < 9.0e18 / 8, "ppr_create: matrix too large");
-  gss_ppr *p = new gss_ppr();
+  std::unique_ptr<gss_ppr> p(new gss_ppr());
   p->d = D;
-  p->csr = nullptr;
-  p->slab = nullptr;
   p->has_ko = false;
   p->dead = p->corr_ptr = p->corr_grp_row = p->corr_grp_col = p->corr_src = nullptr;
   p->corr_val = nullptr;
   p->n_grp = p->n_corr = 0;
   // structure-only CSR handle for the segment schedule (its value pointer is never read as float)
-  if (int rc = gss_csr_create(&p->csr, D.n, D.n, D.nnz, D.h_rowptr, D.t_rowptr, D.t_col, reinterpret_cast<const float *>(D.t_val))) {
-    delete p;
-    return rc;
-  }
+  if (int rc = gss_csr_create(&p->csr, D.n, D.n, D.nnz, D.h_rowptr, D.t_rowptr, D.t_col, reinterpret_cast<const float *>(D.t_val))) return rc;
   p->n_rowblocks = ceil_div(D.n, kPprRows);
   p->n_zchunks = ceil_div(D.n_z, kPprRows);
   // fused update: needs the overrides grouped by column (ovr_ptr); knob "ppr_fused" = 0 keeps the separate update pass (A/B)
@@ -547,11 +545,7 @@ int gss_ppr_create(gss_ppr **out, const gss_ppr_desc *desc) {
   p->rowflag = nullptr;
   if (p->fused) {
     const int4 *segs = nullptr;
-    if (int rc = csr_segments(p->csr, 2, &segs, &p->n_segblocks)) {
-      gss_csr_destroy(p->csr);
-      delete p;
-      return rc;
-    }
+    if (int rc = csr_segments(p->csr, 2, &segs, &p->n_segblocks)) return rc;
   }
   const size_t row = (size_t)D.kpad * sizeof(double);
   auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
@@ -561,18 +555,13 @@ int gss_ppr_create(gss_ppr **out, const gss_ppr_desc *desc) {
   const size_t b_flag = al(((size_t)D.n / 32 + 1) * sizeof(uint32_t)), b_pe = al((size_t)std::max(p->n_segblocks, 1) * row);
   // every carved buffer is followed by a 256-byte guard (as in plan.hip): gss_ppr_check_guards verifies that no kernel wrote one
   constexpr size_t kGuard = 256;
-  p->slab_bytes = b_y + b_so + b_part + 2 * b_col + 2 * b_int + 256 + 8 * kGuard + (p->fused ? b_y + b_flag + b_pe + b_col + 4 * kGuard : 0);
-  if (hipMalloc((void **)&p->slab, p->slab_bytes) != hipSuccess) {
-    gss_csr_destroy(p->csr);
-    const size_t want = p->slab_bytes;
-    delete p;
-    return fail(GSS_ENOMEM, "ppr_create: hipMalloc of %zu bytes failed", want);
-  }
-  char *q = p->slab;
+  const size_t want = b_y + b_so + b_part + 2 * b_col + 2 * b_int + 256 + 8 * kGuard + (p->fused ? b_y + b_flag + b_pe + b_col + 4 * kGuard : 0);
+  if (int rc = p->slab.alloc("ppr_create", want)) return rc;
+  char *q = p->slab.p;
   auto take = [&](size_t b) {
     char *r = q;
     q += b;
-    p->guard_off.push_back((size_t)(q - p->slab));
+    p->guard_off.push_back((size_t)(q - p->slab.p));
     q += kGuard;
     return r;
   };
@@ -584,49 +573,36 @@ int gss_ppr_create(gss_ppr **out, const gss_ppr_desc *desc) {
   p->done = (int32_t *)take(b_int);
   p->iters = (int32_t *)take(b_int);
   p->n_active = (int32_t *)take(256);
-  hipError_t ge = hipSuccess;
   if (p->fused) {
     p->ysel = (double *)take(b_y);
     p->rowflag = (uint32_t *)take(b_flag);
     p->part_e = (double *)take(b_pe);
     p->err_corr = (double *)take(b_col);
-    ge = hipMemset(p->ysel, 0, b_y);
-    if (ge == hipSuccess) ge = hipMemset(p->rowflag, 0, b_flag);
-    if (ge == hipSuccess) ge = hipMemset(p->part_e, 0, b_pe);
-    if (ge == hipSuccess) ge = hipMemset(p->err_corr, 0, b_col);
-    if (ge == hipSuccess && D.n_sel > 0) {
+    GSS_HIP(hipMemset(p->ysel, 0, b_y));
+    GSS_HIP(hipMemset(p->rowflag, 0, b_flag));
+    GSS_HIP(hipMemset(p->part_e, 0, b_pe));
+    GSS_HIP(hipMemset(p->err_corr, 0, b_col));
+    if (D.n_sel > 0) {
       hipLaunchKernelGGL(ppr_rowflag_kernel, dim3(ceil_div(D.n_sel, 256)), dim3(256), 0, nullptr, p->rowflag, D.sel_row, (long)D.n_sel);
-      ge = hipGetLastError();
+      GSS_LAUNCH_CHECK("ppr_rowflag_kernel");
     }
   }
-  for (size_t g : p->guard_off)
-    if (ge == hipSuccess) ge = hipMemset(p->slab + g, 0xA5, kGuard);
-  if (ge == hipSuccess) ge = hipDeviceSynchronize();
-  if (ge != hipSuccess) {
-    gss_csr_destroy(p->csr);
-    (void)hipFree(p->slab);
-    delete p;
-    return fail(GSS_EHIP, "ppr_create: guard fill -> %s", hipGetErrorString(ge));
-  }
-  *out = p;
+  for (size_t g : p->guard_off) GSS_HIP(hipMemset(p->slab.p + g, 0xA5, kGuard));
+  GSS_HIP(hipDeviceSynchronize());
+  *out = p.release();
   return GSS_OK;
 }
 
-void gss_ppr_destroy(gss_ppr *p) {
-  if (!p) return;
-  if (p->csr) gss_csr_destroy(p->csr);
-  if (p->slab) (void)hipFree(p->slab);
-  delete p;
-}
+void gss_ppr_destroy(gss_ppr *p) { delete p; }
 
-size_t gss_ppr_device_bytes(const gss_ppr *p) { return p ? p->slab_bytes : 0; }
+size_t gss_ppr_device_bytes(const gss_ppr *p) { return p ? p->slab.bytes : 0; }
 
 int gss_ppr_check_guards(gss_ppr *p) {
   GSS_REQUIRE(p, "ppr_check_guards: null handle");
   GSS_HIP(hipDeviceSynchronize());
   unsigned char host[256];
   for (size_t k = 0; k < p->guard_off.size(); ++k) {
-    GSS_HIP(hipMemcpy(host, p->slab + p->guard_off[k], sizeof(host), hipMemcpyDeviceToHost));
+    GSS_HIP(hipMemcpy(host, p->slab.p + p->guard_off[k], sizeof(host), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < sizeof(host); ++i)
       if (host[i] != 0xA5)
         return fail(GSS_EINVAL, "ppr_check_guards: the guard behind carved buffer %zu (slab offset %zu) was overwritten at byte %zu", k,

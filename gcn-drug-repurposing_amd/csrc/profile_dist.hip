@@ -346,21 +346,16 @@ int gss_profile_dist(int32_t n, const double *x, int64_t ld, int32_t na, const i
   // scratch: the two status words of the column check (16 bytes), then mean and norm of every listed column (dot class)
   const size_t entries = (size_t)na + (size_t)nb;
   const size_t want = 16 + (dot ? 2 * entries * sizeof(double) : 0);
-  DeviceScratch ws;
-  if (lists || dot) {
-    if (hipMalloc(&ws.p, want) != hipSuccess) {
-      (void)hipGetLastError();
-      ws.p = nullptr;
-      return fail(GSS_ENOMEM, "profile_dist: hipMalloc of %zu bytes failed", want);
-    }
-  }
+  DeviceBuf<char> ws;
+  if (lists || dot)
+    if (int rc = ws.alloc("profile_dist", want)) return rc;
   if (lists) {   // nothing reads x through a list before every entry of it is known to be a column of x
     const CheckedList a{cols_a, na, 0, ld, "cols_a", "ld"}, b{cols_b, nb, 0, ld, "cols_b", "ld"};
-    if (int rc = check_lists("profile_dist", a, b, static_cast<uint32_t *>(ws.p), st)) return rc;
+    if (int rc = check_lists("profile_dist", a, b, reinterpret_cast<uint32_t *>(ws.p), st)) return rc;
   }
   const dim3 grid(ceil_div(nb, kPdTile), ceil_div(na, kPdTile)), block(kPdThreads);
   if (dot) {
-    double *mean = reinterpret_cast<double *>(static_cast<char *>(ws.p) + 16), *norm = mean + entries;
+    double *mean = reinterpret_cast<double *>(ws.p + 16), *norm = mean + entries;
     hipLaunchKernelGGL(pd_stats_kernel, dim3(ceil_div((int64_t)entries, kPdThreads)), block, 0, st, n, x, ld, na, cols_a, nb, cols_b,
                        metric == GSS_DIST_CORRELATION ? 1 : 0, mean, norm);
     GSS_LAUNCH_CHECK("pd_stats_kernel");
@@ -376,7 +371,7 @@ int gss_profile_dist(int32_t n, const double *x, int64_t ld, int32_t na, const i
     hipLaunchKernelGGL(pd_diff_kernel<GSS_DIST_CANBERRA>, grid, block, 0, st, n, x, ld, na, cols_a, nb, cols_b, out, ld_out);
     GSS_LAUNCH_CHECK("pd_diff_kernel<canberra>");
   }
-  if (ws.p) GSS_HIP(hipStreamSynchronize(st));   // the scratch is freed on return: its readers have to be done
+  if (ws.p) GSS_HIP(hipStreamSynchronize(st));   // not for the free (device_scope.h): a call with scratch has always returned with its work done
   return GSS_OK;
 }
 

@@ -19,13 +19,6 @@ constexpr int kKeyTileThreads = 256;
 constexpr int kKeyPanel = 512;                // listed columns per pass through the workspace: two workgroups per CU on 256 CUs
 constexpr int kKeyMaxRows = 1 << 24;          // rows of a key pass; a node index is three 8-bit digits
 
-struct DeviceScratch {   // freed on every way out of its scope
-  void *p = nullptr;
-  ~DeviceScratch() {
-    if (p) (void)hipFree(p);
-  }
-};
-
 // one list of a call: v[0 .. len) must lie in [lo, hi); v null = no list, nothing to check.  `name` and `bound` are the refusal's words
 // for the list and for hi ("cols", "ld")
 struct CheckedList {
@@ -59,8 +52,7 @@ inline int check_lists(const char *who, const CheckedList &a, const CheckedList 
                      a.hi, b.v, b.len, b.lo, b.hi, status);
   GSS_LAUNCH_CHECK("check_lists_kernel");
   uint32_t h[2] = {kListNone, kListNone};
-  GSS_HIP(hipMemcpyAsync(h, status, 8, hipMemcpyDeviceToHost, st));
-  GSS_HIP(hipStreamSynchronize(st));
+  if (int rc = read_back(h, status, 8, st)) return rc;
   for (int s = 0; s < 2; ++s) {
     if (h[s] == kListNone) continue;
     const CheckedList &l = s == 0 ? a : b;

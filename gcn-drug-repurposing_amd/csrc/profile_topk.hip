@@ -320,10 +320,10 @@ int gss_topk_overlap(int32_t S, int32_t G, int32_t k, const int32_t *idx, const 
   GSS_REQUIRE(shared != nullptr, "topk_overlap: shared is null");
   hipStream_t st = as_stream(stream);
   {   // nothing reads idx or cnt through a list before every entry of it is known to be a selection; the status words are freed before the launch
-    DeviceScratch status;
-    GSS_HIP(hipMalloc(&status.p, 8));
+    DeviceBuf<uint32_t> status;
+    if (int rc = status.alloc("topk_overlap", 8)) return rc;
     const CheckedList la{a, T, 0, S, "a", "S"}, lb{b, T, 0, S, "b", "S"};
-    if (int rc = check_lists("topk_overlap", la, lb, static_cast<uint32_t *>(status.p), st)) return rc;
+    if (int rc = check_lists("topk_overlap", la, lb, status.p, st)) return rc;
   }
   const int32_t cp = pow2_at_least(k);
   hipLaunchKernelGGL(to_overlap_kernel, dim3(T, G), dim3(kToThreads), (size_t)cp * 8, st, G, k, cp, idx, cnt, a, b, shared);

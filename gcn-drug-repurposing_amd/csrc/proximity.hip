@@ -14,16 +14,16 @@
 
 #include <algorithm>
 
-#include "common.h"
+#include "device_scope.h"
+
 #include "counter_rng.h"
 
-struct gss_prox {
+struct __attribute__((visibility("hidden"))) gss_prox {
   int32_t n;
-  int32_t diameter;   // max finite eccentricity
-  uint8_t *dist;      // [n][n]
-  double *vals;       // scoring scratch: [batch pairs][kProxMeasures][n_samples]
-  size_t vals_bytes;
-  int32_t *flag;      // device word for error reports
+  int32_t diameter;                 // max finite eccentricity
+  gss::DeviceBuf<uint8_t> dist;     // [n][n]
+  gss::DeviceBuf<double> vals;      // scoring scratch: [batch pairs][kProxMeasures][n_samples]
+  gss::DeviceBuf<int32_t> flag;     // two device words for error reports
 };
 
 namespace gss {
@@ -291,12 +291,6 @@ __global__ __launch_bounds__(256) void stats_kernel(int64_t n_items, int32_t n_s
   o[4] = 0.5 * erfc(-z * M_SQRT1_2);
 }
 
-int read_flag(gss_prox *p, hipStream_t st, int32_t *out) {
-  GSS_HIP(hipMemcpyAsync(out, p->flag, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  GSS_HIP(hipStreamSynchronize(st));
-  return GSS_OK;
-}
-
 int check_sets(const char *what, const gss_prox_sets *s, int32_t n_samples) {
   GSS_REQUIRE(s, "prox_score: %s sets missing", what);
   GSS_REQUIRE(s->n_sets >= 1 && s->max_size >= 1, "prox_score: %s: n_sets=%d max_size=%d must be >= 1", what, s->n_sets, s->max_size);
@@ -317,45 +311,24 @@ int gss_prox_create(gss_prox **out, int32_t n, const int32_t *rowptr, const int3
   GSS_REQUIRE(bytes <= max_bytes, "prox_create: the distance matrix needs %lld bytes (N=%d), above the budget max_bytes=%lld",
               (long long)bytes, n, (long long)max_bytes);
   hipStream_t st = as_stream(stream);
-  gss_prox *p = new gss_prox();
+  std::unique_ptr<gss_prox> p(new gss_prox());
   p->n = n;
-  int32_t *dev = nullptr;
-  if (hipMalloc((void **)&p->dist, (size_t)bytes) != hipSuccess || hipMalloc((void **)&dev, 2 * sizeof(int32_t)) != hipSuccess) {
-    hipFree(p->dist);
-    delete p;
+  if (p->dist.alloc("prox_create", (size_t)bytes) || p->flag.alloc("prox_create", 2 * sizeof(int32_t)))
     return fail(GSS_ENOMEM, "prox_create: hipMalloc of %lld bytes failed", (long long)bytes);
-  }
-  p->flag = dev;
-  int rc = GSS_OK;
-  int32_t h[2] = {0, 0};
-  if (hipMemsetAsync(dev, 0, 2 * sizeof(int32_t), st) != hipSuccess) rc = fail(GSS_EHIP, "prox_create: memset failed");
-  if (rc == GSS_OK) {
-    apsp_kernel<<<n, kApspThreads, (size_t)n, st>>>(n, rowptr, col, p->dist, dev, dev + 1);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(h, dev, sizeof(h), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) rc = fail(GSS_EHIP, "prox_create: apsp_kernel -> %s", hipGetErrorString(e));
-  }
-  if (rc == GSS_OK && h[1])
-    rc = fail(GSS_EINVAL, "prox_create: a node lies 255 or more hops from another; distances are stored in one byte (eccentricity <= 254)");
-  if (rc != GSS_OK) {
-    gss_prox_destroy(p);
-    return rc;
-  }
+  int32_t *dev = p->flag.p, h[2] = {0, 0};
+  GSS_HIP(hipMemsetAsync(dev, 0, 2 * sizeof(int32_t), st));
+  apsp_kernel<<<n, kApspThreads, (size_t)n, st>>>(n, rowptr, col, p->dist.p, dev, dev + 1);
+  GSS_LAUNCH_CHECK("apsp_kernel");
+  if (int rc = read_back(h, dev, sizeof(h), st)) return rc;
+  GSS_REQUIRE(!h[1], "prox_create: a node lies 255 or more hops from another; distances are stored in one byte (eccentricity <= 254)");
   p->diameter = h[0];
-  *out = p;
+  *out = p.release();
   return GSS_OK;
 }
 
-void gss_prox_destroy(gss_prox *p) {
-  if (!p) return;
-  hipFree(p->dist);
-  hipFree(p->vals);
-  hipFree(p->flag);
-  delete p;
-}
+void gss_prox_destroy(gss_prox *p) { delete p; }
 
-const uint8_t *gss_prox_distances(const gss_prox *p) { return p ? p->dist : nullptr; }
+const uint8_t *gss_prox_distances(const gss_prox *p) { return p ? p->dist.p : nullptr; }
 
 int32_t gss_prox_diameter(const gss_prox *p) { return p ? p->diameter : -1; }
 
@@ -382,13 +355,13 @@ int gss_prox_random_sets(gss_prox *p, int32_t side, int32_t n_sets, const int32_
   a.tag = side == 0 ? kRngProxFrom : kRngProxTo;
   a.out_nodes = out_nodes;
   a.out_size = out_size;
-  a.flag = p->flag;
-  GSS_HIP(hipMemsetAsync(p->flag, 0, sizeof(int32_t), st));
+  a.flag = p->flag.p;
+  GSS_HIP(hipMemsetAsync(a.flag, 0, sizeof(int32_t), st));
   const int64_t units = (int64_t)n_sets * a.n_samples;
   random_sets_kernel<<<ceil_div(units, 256), 256, 0, st>>>(a);
   GSS_LAUNCH_CHECK("random_sets_kernel");
   int32_t flag = 0;
-  if (int rc = read_flag(p, st, &flag)) return rc;
+  if (int rc = read_back(&flag, a.flag, sizeof(int32_t), st)) return rc;
   GSS_REQUIRE(!(flag & 1), "prox_random_sets: a set member is not a node index in [0, %d)", p->n);
   GSS_REQUIRE(!(flag & 2), "prox_random_sets: a set has more than max_size=%d members", max_size);
   return GSS_OK;
@@ -405,7 +378,7 @@ int gss_prox_set_stats(gss_prox *p, int32_t n_sets, int32_t n_samples, int32_t m
   a.n_units = (int64_t)n_sets * n_samples;
   a.n_samples = n_samples;
   a.max_size = max_size;
-  a.dist = p->dist;
+  a.dist = p->dist.p;
   a.nodes = nodes;
   a.sizes = sizes;
   a.inner = inner;
@@ -435,31 +408,26 @@ int gss_prox_score(gss_prox *p, const gss_prox_sets *from, const gss_prox_sets *
   int64_t batch = std::max<int64_t>(1, (int64_t)(kScratchBytes / per_pair));
   batch = std::min(batch, n_pairs);
   const size_t want = (size_t)batch * per_pair;
-  if (p->vals_bytes < want) {
-    hipFree(p->vals);
-    p->vals = nullptr;
-    p->vals_bytes = 0;
-    if (hipMalloc((void **)&p->vals, want) != hipSuccess) return fail(GSS_ENOMEM, "prox_score: hipMalloc of %zu bytes failed", want);
-    p->vals_bytes = want;
-  }
+  if (p->vals.bytes < want)
+    if (int rc = p->vals.alloc("prox_score", want)) return rc;
   ScoreArgs a;
   a.n = p->n;
   a.n_samples = n_samples;
   a.measures = measures;
   a.n_to_all = to->n_sets;
-  a.dist = p->dist;
+  a.dist = p->dist.p;
   a.from = *from;
   a.to = *to;
   a.pair_from = pair_from;
   a.pair_to = pair_to;
-  a.vals = p->vals;
+  a.vals = p->vals.p;
   for (int64_t p0 = 0; p0 < n_pairs; p0 += batch) {
     const int64_t nb = std::min(batch, n_pairs - p0);
     a.p0 = p0;
     a.n_units = nb * n_samples;
     score_kernel<<<ceil_div(a.n_units, kScoreWaves), 64 * kScoreWaves, 0, st>>>(a);
     GSS_LAUNCH_CHECK("score_kernel");
-    stats_kernel<<<ceil_div(nb * kMeasures, 256), 256, 0, st>>>(nb * kMeasures, n_samples, p0, p->vals, out);
+    stats_kernel<<<ceil_div(nb * kMeasures, 256), 256, 0, st>>>(nb * kMeasures, n_samples, p0, p->vals.p, out);
     GSS_LAUNCH_CHECK("stats_kernel");
   }
   return GSS_OK;

@@ -4,9 +4,7 @@
 // rule of the three files depends on those integer counts alone.  The two row kernels also share what they refuse: the positives' list
 // of a row, checked while its bitmap is built, and the refusals' way back to the host.  Inline device and host code only.
 #pragma once
-#include <new>
-
-#include "common.h"
+#include "device_scope.h"
 
 namespace gss {
 
@@ -141,26 +139,18 @@ __device__ __forceinline__ bool mark_and_fill(int32_t C, int32_t cpad, const dou
 // The refusals come back in the count words: -code in n_pos, the column in n_neg.  Reads both arrays of R words back on the stream,
 // waits for it, and names the first refused row in the words of entry point `who` ("auc_rows", "rank_metrics_rows")
 inline int read_refusals(const char *who, int32_t R, int32_t C, const int32_t *n_pos, const int32_t *n_neg, hipStream_t st) {
-  int32_t *h = new (std::nothrow) int32_t[(size_t)2 * R];
+  std::unique_ptr<int32_t[]> h(new (std::nothrow) int32_t[(size_t)2 * R]);
   if (!h) return fail(GSS_ENOMEM, "%s: host status buffer of %d rows", who, R);
-  hipError_t e1 = hipMemcpyAsync(h, n_pos, (size_t)R * 4, hipMemcpyDeviceToHost, st);
-  hipError_t e2 = e1 == hipSuccess ? hipMemcpyAsync(h + R, n_neg, (size_t)R * 4, hipMemcpyDeviceToHost, st) : e1;
-  hipError_t e3 = e2 == hipSuccess ? hipStreamSynchronize(st) : e2;
-  int rc = GSS_OK;
-  if (e3 != hipSuccess) rc = fail(GSS_EHIP, "%s: reading the row status failed: %s", who, hipGetErrorString(e3));
-  for (int32_t r = 0; rc == GSS_OK && r < R; ++r) {
+  GSS_HIP(hipMemcpyAsync(h.get(), n_pos, (size_t)R * 4, hipMemcpyDeviceToHost, st));   // no wait of its own: the stream orders it before n_neg's
+  if (int rc = read_back(h.get() + R, n_neg, (size_t)R * 4, st)) return rc;
+  for (int32_t r = 0; r < R; ++r) {
     const int32_t code = -h[r], col = h[R + r];
-    if (code == kBadPtr)
-      rc = fail(GSS_EINVAL, "%s: row %d: pos_ptr is not a CSR row pointer (0 first, non-decreasing, at most C=%d per row; %d here)", who, r, C, col);
-    else if (code == kColRange)
-      rc = fail(GSS_EINVAL, "%s: row %d: pos_col %d is outside [0, %d)", who, r, col, C);
-    else if (code == kColRepeat)
-      rc = fail(GSS_EINVAL, "%s: row %d: pos_col %d is repeated", who, r, col);
-    else if (code == kNonFinite)
-      rc = fail(GSS_EINVAL, "%s: row %d, column %d: the score is NaN or infinite (roc_auc_score refuses it)", who, r, col);
+    GSS_REQUIRE(code != kBadPtr, "%s: row %d: pos_ptr is not a CSR row pointer (0 first, non-decreasing, at most C=%d per row; %d here)", who, r, C, col);
+    GSS_REQUIRE(code != kColRange, "%s: row %d: pos_col %d is outside [0, %d)", who, r, col, C);
+    GSS_REQUIRE(code != kColRepeat, "%s: row %d: pos_col %d is repeated", who, r, col);
+    GSS_REQUIRE(code != kNonFinite, "%s: row %d, column %d: the score is NaN or infinite (roc_auc_score refuses it)", who, r, col);
   }
-  delete[] h;
-  return rc;
+  return GSS_OK;
 }
 
 }  // namespace gss

@@ -121,22 +121,16 @@ int gss_resample_stats(const double *v, int64_t ld, int32_t S, int32_t n, int32_
   GSS_REQUIRE(out != nullptr, "resample_stats: out is null");
   hipStream_t st = as_stream(stream);
   {   // nothing is resampled, and nothing written, before every value is known to be finite
-    struct Status {
-      unsigned long long *p = nullptr;
-      ~Status() {
-        if (p) (void)hipFree(p);
-      }
-    } status;
+    DeviceBuf<unsigned long long> status;
     unsigned long long h = 0;
     const int64_t total = (int64_t)S * n;
     const int64_t blocks = (total + kRsCheckThreads - 1) / kRsCheckThreads;
-    GSS_HIP(hipMalloc(&status.p, 8));
+    if (int rc = status.alloc("resample_stats", 8)) return rc;
     GSS_HIP(hipMemsetAsync(status.p, 0xff, 8, st));
     hipLaunchKernelGGL(rs_check_kernel, dim3((unsigned)(blocks < kRsCheckBlocks ? blocks : kRsCheckBlocks)), dim3(kRsCheckThreads), 0, st, v, ld,
                        total, n, status.p);
     GSS_LAUNCH_CHECK("rs_check_kernel");
-    GSS_HIP(hipMemcpyAsync(&h, status.p, 8, hipMemcpyDeviceToHost, st));
-    GSS_HIP(hipStreamSynchronize(st));
+    if (int rc = read_back(&h, status.p, 8, st)) return rc;
     GSS_REQUIRE(h == ~0ull, "resample_stats: series %lld, position %lld: the value is NaN or infinite", (long long)(h / (uint64_t)n),
                 (long long)(h % (uint64_t)n));
   }

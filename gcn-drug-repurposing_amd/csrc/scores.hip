@@ -22,7 +22,7 @@
 // owns it; the only atomic is the status word.
 #include <math.h>
 
-#include "common.h"
+#include "device_scope.h"
 
 #pragma clang fp contract(off)
 
@@ -170,13 +170,6 @@ __global__ __launch_bounds__(kScThreads) void scores_dot_kernel(int32_t d, const
   }
 }
 
-struct ScoresScratch {   // freed on every way out of the call
-  void *p = nullptr;
-  ~ScoresScratch() {
-    if (p) (void)hipFree(p);
-  }
-};
-
 }  // namespace
 }  // namespace gss
 
@@ -202,45 +195,28 @@ int gss_embedding_scores(int32_t n, int32_t d, const float *emb, int64_t ld, int
   // scratch: the status word (16 bytes), then the listed rows as fp64, normalised
   const size_t entries = (size_t)nr + (size_t)nc;
   const size_t want = 16 + entries * (size_t)d * sizeof(double);
-  ScoresScratch ws;
-  if (hipMalloc(&ws.p, want) != hipSuccess) {
-    (void)hipGetLastError();
-    ws.p = nullptr;
-    return fail(GSS_ENOMEM, "embedding_scores: hipMalloc of %zu bytes failed", want);
-  }
-  unsigned long long *status = static_cast<unsigned long long *>(ws.p);
-  double *xn = reinterpret_cast<double *>(static_cast<char *>(ws.p) + 16);
-  int rc = GSS_OK;
+  DeviceBuf<char> ws;
+  if (int rc = ws.alloc("embedding_scores", want)) return rc;
+  unsigned long long *status = reinterpret_cast<unsigned long long *>(ws.p);
+  double *xn = reinterpret_cast<double *>(ws.p + 16);
   unsigned long long h = kScClean;
-  // after the first launch every way out drains the stream first: the scratch is freed on return and its readers have to be done
-  hipError_t e = hipMemsetAsync(status, 0xff, sizeof(unsigned long long), st);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(scores_prepare_kernel, dim3(ceil_div((int64_t)entries, kScThreads / kWave)), dim3(kScThreads), 0, st, n, d, emb, ld, nr, rows,
-                       nc, cols, (int)normalize, xn, status);
-    e = hipGetLastError();
+  GSS_HIP(hipMemsetAsync(status, 0xff, sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(scores_prepare_kernel, dim3(ceil_div((int64_t)entries, kScThreads / kWave)), dim3(kScThreads), 0, st, n, d, emb, ld, nr, rows, nc,
+                     cols, (int)normalize, xn, status);
+  GSS_LAUNCH_CHECK("scores_prepare_kernel");
+  hipLaunchKernelGGL(scores_dot_kernel, dim3(ceil_div(nc, kScTile), ceil_div(nr, kScTile)), dim3(kScThreads), 0, st, d, xn, nr, nc, out, ld_out);
+  GSS_LAUNCH_CHECK("scores_dot_kernel");
+  if (int rc = read_back(&h, status, sizeof(h), st)) return rc;
+  if (h == kScClean) return GSS_OK;
+  const int code = (int)(h >> 56), list = (int)((h >> 48) & 0xff);
+  const int32_t at = (int32_t)(h & 0xffffffffu);
+  if (code == kScErrIndex) {
+    int32_t v = 0;
+    GSS_HIP(hipMemcpy(&v, (list ? cols : rows) + at, 4, hipMemcpyDeviceToHost));
+    return fail(GSS_EINVAL, "embedding_scores: %s[%d] = %d is not a row index in [0, %d)", list ? "cols" : "rows", at, v, n);
   }
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(scores_dot_kernel, dim3(ceil_div(nc, kScTile), ceil_div(nr, kScTile)), dim3(kScThreads), 0, st, d, xn, nr, nc, out, ld_out);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(&h, status, sizeof(h), hipMemcpyDeviceToHost, st);
-  const hipError_t es = hipStreamSynchronize(st);
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) return fail(GSS_EHIP, "embedding_scores: %s", hipGetErrorString(e));
-  if (h != kScClean) {
-    const int code = (int)(h >> 56), list = (int)((h >> 48) & 0xff);
-    const int32_t at = (int32_t)(h & 0xffffffffu);
-    if (code == kScErrIndex) {
-      int32_t v = 0;
-      GSS_HIP(hipMemcpy(&v, (list ? cols : rows) + at, 4, hipMemcpyDeviceToHost));
-      rc = fail(GSS_EINVAL, "embedding_scores: %s[%d] = %d is not a row index in [0, %d)", list ? "cols" : "rows", at, v, n);
-    } else if (code == kScErrValue) {
-      rc = fail(GSS_EINVAL, "embedding_scores: row %d of emb holds a NaN or infinite value", at);
-    } else {
-      rc = fail(GSS_EHIP, "embedding_scores: unknown status word %llx", h);
-    }
-  }
-  return rc;
+  if (code == kScErrValue) return fail(GSS_EINVAL, "embedding_scores: row %d of emb holds a NaN or infinite value", at);
+  return fail(GSS_EHIP, "embedding_scores: unknown status word %llx", h);
 }
 
 }  // extern "C"

@@ -15,7 +15,7 @@
 // that compacts in node order (ballot + prefix over the workgroup's waves).
 #include <math.h>
 
-#include "common.h"
+#include "device_scope.h"
 #include "ops.h"
 
 namespace gss {
@@ -369,8 +369,7 @@ int gss_paths_count(gss_paths *p, int32_t q, const int32_t *targets, const uint8
     trace_level_kernel<<<grid, kThreads, 0, st>>>(a);
     GSS_LAUNCH_CHECK("trace_level_kernel");
   }
-  GSS_HIP(hipMemcpyAsync(g.h_status, g.status, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  GSS_HIP(hipStreamSynchronize(st));
+  if (int rc = read_back(g.h_status, g.status, sizeof(unsigned long long), st)) return rc;
   const unsigned long long status = *g.h_status;
   if (status) {
     const int code = (int)(status >> 56), tq = (int)((status >> 32) & 0xff);

@@ -14,7 +14,8 @@
 // statement of the same steps (tests/node2vec_mirror.py) reproduces the walks bit for bit.
 #include <float.h>
 
-#include "common.h"
+#include "device_scope.h"
+
 #include "counter_rng.h"
 
 namespace gss {
@@ -133,22 +134,15 @@ int gss_walk_prefix(int32_t n, const int32_t *rowptr, const double *val, double 
   GSS_REQUIRE(n >= 1, "walk_prefix: n=%d must be >= 1", n);
   GSS_REQUIRE(rowptr && val && cum, "walk_prefix: null pointer");
   hipStream_t st = as_stream(stream);
-  unsigned long long *d_bad = nullptr;
-  GSS_HIP(hipMalloc((void **)&d_bad, sizeof(unsigned long long)));
+  DeviceBuf<unsigned long long> bad;
+  if (int rc = bad.alloc("walk_prefix", sizeof(unsigned long long))) return rc;
   unsigned long long h_bad = ~0ull;
-  int rc = GSS_OK;
-  if (hipMemcpyAsync(d_bad, &h_bad, sizeof(h_bad), hipMemcpyHostToDevice, st) != hipSuccess) rc = fail(GSS_EHIP, "walk_prefix: upload failed");
-  if (rc == GSS_OK) {
-    row_prefix_kernel<<<ceil_div(n, 256), 256, 0, st>>>(n, rowptr, val, cum, d_bad);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(&h_bad, d_bad, sizeof(h_bad), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) rc = fail(GSS_EHIP, "walk_prefix: %s", hipGetErrorString(e));
-  }
-  (void)hipFree(d_bad);
-  if (rc == GSS_OK && h_bad != ~0ull)
-    rc = fail(GSS_EINVAL, "walk_prefix: edge weight of CSR entry %llu is not positive and finite (node2vec needs weights > 0)", h_bad);
-  return rc;
+  GSS_HIP(hipMemcpyAsync(bad.p, &h_bad, sizeof(h_bad), hipMemcpyHostToDevice, st));
+  row_prefix_kernel<<<ceil_div(n, 256), 256, 0, st>>>(n, rowptr, val, cum, bad.p);
+  GSS_LAUNCH_CHECK("row_prefix_kernel");
+  if (int rc = read_back(&h_bad, bad.p, sizeof(h_bad), st)) return rc;
+  GSS_REQUIRE(h_bad == ~0ull, "walk_prefix: edge weight of CSR entry %llu is not positive and finite (node2vec needs weights > 0)", h_bad);
+  return GSS_OK;
 }
 
 int gss_node2vec_walks(int32_t n, const int32_t *rowptr, const int32_t *col, const double *val, const double *cum, int64_t n_walks,
