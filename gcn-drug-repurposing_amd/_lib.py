@@ -186,6 +186,7 @@ SIGNATURES = {
     "gss_topk_overlap": (C.c_int, [_I32, _I32, _I32, _P, _P, _I32, _P, _P, _P, _P]),
     "gss_pair_sums_lists": (C.c_int, [_I32, _P, _I64, _I32, _P, _P, _P, _P]),
     "gss_pair_sums_random": (C.c_int, [_I32, _P, _I64, C.c_uint64, _I64, _I32, _I32, _P, _P, _P, _P]),
+    "gss_matrix_cross_sums": (C.c_int, [_I32, _P, _I64, _P, _I64, _I32, C.c_uint64, _I64, _I64, _P, _P, _P]),
     "gss_resample_stats": (C.c_int, [_P, _I64, _I32, _I32, _I32, C.c_uint64, _I64, _I64, _P, _P]),
     "gss_embedding_scores": (C.c_int, [_I32, _I32, _P, _I64, _I32, _P, _I32, _P, _I32, _P, _I64, _P]),
     # for tests: the row-sparse SpMM modes and their bitmap builders (tests/test_gpu_sparse_ops.py)

@@ -10,7 +10,7 @@
 // other sizes asked for, or on the chunks the rows are taken in.  Nothing is accumulated with atomics.
 //   cc_lists_kernel    one workgroup per list; the list is read from global memory, r_j goes through an LDS buffer of kCcRowChunk rows;
 //   cc_random_kernel   one workgroup per sample s: the keys rng_key(seed, kRngClassPerm, s, i, 0) of i = 0 .. n - 1 (counter_rng.h) are sorted
-//                      in LDS by (key, i) ascending -- rank_keys.h's bitonic network with the index as the second word of the comparison, so
+//                      in LDS by (key, i) ascending -- rank_keys.h's sort_pairs, the bitonic network with the index as the second word of the comparison, so
 //                      that the permutation is a total order and equal keys cannot make it depend on the network -- and the first
 //                      sizes[n_sizes - 1] places are the list; r_j reuses the keys' LDS.
 // The first m places of a uniformly random permutation are a uniformly random m-subset for every m: one permutation per sample serves every size.
@@ -75,27 +75,6 @@ __global__ __launch_bounds__(kCcThreads) void cc_lists_kernel(const double *__re
   pair_prefix_sums(d, ld, idx + b, m, &len, 1, sum_out + c, r, kCcRowChunk, tid);
 }
 
-// sort_keys (rank_keys.h) over the pairs (key[i], idx[i]), ascending by key, then by index
-__device__ __forceinline__ void sort_pairs(uint64_t *key, int32_t *idx, int32_t cpad, int32_t tid) {
-  for (int32_t k = 2; k <= cpad; k <<= 1) {
-    for (int32_t j = k >> 1; j > 0; j >>= 1) {
-      for (int32_t i = tid; i < cpad / 2; i += kCcThreads) {
-        const int32_t lo = ((i & ~(j - 1)) << 1) | (i & (j - 1)), hi = lo + j;
-        const uint64_t x = key[lo], y = key[hi];
-        const int32_t ix = idx[lo], iy = idx[hi];
-        const bool above = x > y || (x == y && ix > iy);
-        if (above == ((lo & k) == 0)) {
-          key[lo] = y;
-          key[hi] = x;
-          idx[lo] = iy;
-          idx[hi] = ix;
-        }
-      }
-      __syncthreads();
-    }
-  }
-}
-
 // sample s0 + blockIdx.x.  LDS: key [cpad] then idx [cpad]; the padding (kBehind, i >= n) sorts behind every (key, i < n)
 __global__ __launch_bounds__(kCcThreads) void cc_random_kernel(int32_t n, const double *__restrict__ d, int64_t ld, uint64_t seed, int64_t s0,
                                                                 int32_t cpad, int32_t n_sizes, const int32_t *__restrict__ sizes, int32_t m_max,
@@ -110,7 +89,7 @@ __global__ __launch_bounds__(kCcThreads) void cc_random_kernel(int32_t n, const 
     idx[i] = i;
   }
   __syncthreads();
-  sort_pairs(key, idx, cpad, tid);
+  sort_pairs<kCcThreads>(key, idx, cpad, tid);
   if (perm_out)
     for (int32_t i = tid; i < m_max; i += kCcThreads) perm_out[(int64_t)blockIdx.x * m_max + i] = idx[i];
   // the keys have done their work: their LDS holds the row sums (m_max - 1 <= cpad of them, one chunk)

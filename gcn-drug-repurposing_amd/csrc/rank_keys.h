@@ -58,6 +58,30 @@ __device__ __forceinline__ void sort_keys(uint64_t *key, int32_t cpad, int32_t t
   }
 }
 
+// sort_keys over the pairs (key[i], idx[i]), ascending by key, then by index: with distinct indices the order is total, so equal keys cannot
+// make it depend on the network.  The seeded permutations of class_cohesion.hip and matrix_mantel.hip are idx after this sort of
+// counter-based keys.  Made of barriers, as sort_keys is
+template <int THREADS>
+__device__ __forceinline__ void sort_pairs(uint64_t *key, int32_t *idx, int32_t cpad, int32_t tid) {
+  for (int32_t k = 2; k <= cpad; k <<= 1) {
+    for (int32_t j = k >> 1; j > 0; j >>= 1) {
+      for (int32_t i = tid; i < cpad / 2; i += THREADS) {
+        const int32_t lo = ((i & ~(j - 1)) << 1) | (i & (j - 1)), hi = lo + j;
+        const uint64_t x = key[lo], y = key[hi];
+        const int32_t ix = idx[lo], iy = idx[hi];
+        const bool above = x > y || (x == y && ix > iy);
+        if (above == ((lo & k) == 0)) {
+          key[lo] = y;
+          key[hi] = x;
+          idx[lo] = iy;
+          idx[hi] = ix;
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
 // ---- the positives of a row: what the two row kernels check before they sort ------------------------------------------------------------
 // per-row refusal, written to n_pos[r] as -code with the offending column (kBadPtr: the row's length) in n_neg[r]
 enum RowRefusal { kBadPtr = 1, kColRange = 2, kColRepeat = 3, kNonFinite = 4 };

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define GSS_ABI_VERSION 25  /* 25: the mean and the median of bootstrap resamples and sign flips of series, behind intervals and paired tests of the per-indication metrics -- gss_resample_stats; 24: sums of a distance matrix over the pairs of listed sets and of the prefixes of seeded random permutations, the statistic and the null of ATC class coherence -- gss_pair_sums_lists, gss_pair_sums_random; 23: entry points for tests of the halo bookkeeping and the batch preparation of a sharded plan -- gss_pack_rows, gss_unpack_rows, gss_halo_need_mark, gss_send_slot_bits, gss_bits_clear, gss_bits_set_list, gss_bits_compact, gss_bits_compact_scratch_bytes, gss_batch_prepare, gss_scatter_add_rows_ex, gss_spmm_prep_side; 22: two forward products in one launch and layer 1 one pass ahead -- gss_spmm_fwd_pair, gss_plan_l1_ahead, plan option "l1_ahead"; 21: entry points for tests of the dense half of a plan's step -- gss_dense_fwd_rows, gss_dense_fwd_first, gss_dense_fwd_split_available, gss_dense_fwd_norm, gss_rownorm_fwd_rows, gss_wgrad_slices, gss_wgrad_slices_max, gss_wgrad_partial, gss_wgrad_partial_pair, gss_wgrad_reduce, gss_wgrad_reduce_adam, gss_adam_step4, gss_transpose2; 20: entry points for tests of the loss stages of a plan's step -- gss_loss_step, gss_loss_slab_sweep, gss_loss_workspace_bytes_parts, gss_loss_gather_rows, gss_loss_gather_rows_mapped, gss_loss_gather_batch; loss_step refuses input-gradient weights at widths outside {64, 128, 256}; 19: exact typed top-k selection of listed profile columns and set overlap between selections -- gss_profile_topk, gss_profile_topk_workspace_bytes, gss_topk_overlap; 18: exact average-tie ranks of listed profile columns, the transform behind the spearman distance -- gss_profile_rank, gss_profile_rank_workspace_bytes; 17: gene knock-outs per column of the diffusion profiles -- gss_ppr_set_knockout; distances of listed column pairs of the profile matrix -- gss_profile_dist_pairs, gss_profile_dist_pairs_workspace_bytes; 16: ROC-AUC, average precision and hits@k per row in one launch -- gss_rank_metrics_rows, gss_rank_metrics_workspace_bytes; 15: entry points for tests of the row-sparse SpMM modes -- gss_spmm_bwd1_sparse_ex, gss_spmm_bwd2_sparse_res, gss_spmm_filtered, gss_mark_rows_and_neighbours, gss_batch_bits, gss_bits_fill; 14:indication x drug scores from the embedding tensor -- gss_embedding_scores; 13: pairwise distances between diffusion profiles -- gss_profile_dist; 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows */
+#define GSS_ABI_VERSION 25  /* 25: the mean and the median of bootstrap resamples and sign flips of series, behind intervals and paired tests of the per-indication metrics -- gss_resample_stats; 24: sums of a distance matrix over the pairs of listed sets and of the prefixes of seeded random permutations, the statistic and the null of ATC class coherence -- gss_pair_sums_lists, gss_pair_sums_random; 23: entry points for tests of the halo bookkeeping and the batch preparation of a sharded plan -- gss_pack_rows, gss_unpack_rows, gss_halo_need_mark, gss_send_slot_bits, gss_bits_clear, gss_bits_set_list, gss_bits_compact, gss_bits_compact_scratch_bytes, gss_batch_prepare, gss_scatter_add_rows_ex, gss_spmm_prep_side; 22: two forward products in one launch and layer 1 one pass ahead -- gss_spmm_fwd_pair, gss_plan_l1_ahead, plan option "l1_ahead"; 21: entry points for tests of the dense half of a plan's step -- gss_dense_fwd_rows, gss_dense_fwd_first, gss_dense_fwd_split_available, gss_dense_fwd_norm, gss_rownorm_fwd_rows, gss_wgrad_slices, gss_wgrad_slices_max, gss_wgrad_partial, gss_wgrad_partial_pair, gss_wgrad_reduce, gss_wgrad_reduce_adam, gss_adam_step4, gss_transpose2; 20: entry points for tests of the loss stages of a plan's step -- gss_loss_step, gss_loss_slab_sweep, gss_loss_workspace_bytes_parts, gss_loss_gather_rows, gss_loss_gather_rows_mapped, gss_loss_gather_batch; loss_step refuses input-gradient weights at widths outside {64, 128, 256}; 19: exact typed top-k selection of listed profile columns and set overlap between selections -- gss_profile_topk, gss_profile_topk_workspace_bytes, gss_topk_overlap; 18: exact average-tie ranks of listed profile columns, the transform behind the spearman distance -- gss_profile_rank, gss_profile_rank_workspace_bytes; 17: gene knock-outs per column of the diffusion profiles -- gss_ppr_set_knockout; distances of listed column pairs of the profile matrix -- gss_profile_dist_pairs, gss_profile_dist_pairs_workspace_bytes; 16: ROC-AUC, average precision and hits@k per row in one launch -- gss_rank_metrics_rows, gss_rank_metrics_workspace_bytes; 15: entry points for tests of the row-sparse SpMM modes -- gss_spmm_bwd1_sparse_ex, gss_spmm_bwd2_sparse_res, gss_spmm_filtered, gss_mark_rows_and_neighbours, gss_batch_bits, gss_bits_fill; 14:indication x drug scores from the embedding tensor -- gss_embedding_scores; 13: pairwise distances between diffusion profiles -- gss_profile_dist; 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows.  gss_matrix_cross_sums, the permuted cross-product sum of two matrices behind Mantel's test, joined under 25 without a new number: an added export breaks no caller */
 
 #define GSS_OK 0
 #define GSS_EINVAL (-22)   /* bad argument (shape, null pointer, unsupported d) */
@@ -629,6 +629,29 @@ int gss_pair_sums_lists(int32_t n, const double *d, int64_t ld, int32_t C, const
  * sizes back and synchronises the stream. */
 int gss_pair_sums_random(int32_t n, const double *d, int64_t ld, uint64_t seed, int64_t s0, int32_t P, int32_t n_sizes, const int32_t *sizes,
                          double *sums_out, int32_t *perm_out, void *stream);
+
+/* ---- the cross-product sum of two symmetric matrices under seeded relabellings of one: the statistic and the null of Mantel's test between
+ * two drug x drug matrices (mantel.py, drug_signatures.py; the reference ships data/bcm_df.tsv, multiscale/README.md dataset 8, and has no
+ * code that reads it)
+ * gss_matrix_cross_sums: a, b: device fp64 [n][lda], [n][ldb], lda, ldb >= n -> device fp64 out [count],
+ *   out[s - first] = sum over 0 <= i < j < n of a[j][i] * b[pi_s(j)][pi_s(i)]      for the replicates s = first .. first + count - 1.
+ *   mode 0 (plain)     pi = the identity: the observed statistic with the arithmetic of the null; only first = 0, count = 1;
+ *   mode 1 (permuted)  key_i = rng_key(seed, kRngMantelPerm = 12, s, i, 0) (csrc/counter_rng.h) for i in [0, n), pi_s = 0 .. n - 1 sorted by
+ *                      (key, i) ascending -- a pure function of (seed, s, n), replayable in numpy (tests/mantel_mirror.py).
+ * a is read below its diagonal only; of b both triangles are read (pi_s(j) may be below pi_s(i)), so the sum is the one over unordered pairs
+ * only when b is symmetric.  The order of the additions is fixed:
+ *   r_j = the row sum over i < j: the 64 partial sums p[l] = the terms i = l, l + 64, l + 128 ... (ascending, from +0.0; a lane without a term
+ *         keeps +0.0), every product rounded to fp64 on its own (no fused multiply-add), combined by the butterfly p[l] = p[l] + p[l ^ o] for
+ *         o = 32, 16, 8, 4, 2, 1;
+ *   T   = r_1 + r_2 + ... + r_{n-1}, added in that order (n = 2: T = r_1).
+ * A replicate's bits are a function of (n, a, b, seed, s): the same run to run, in any split of the replicates through first / count, under
+ * any grid, alone or among other replicates.  Nothing is accumulated with atomics.  perm_out: null, or device int32 [count][n], pi_s (mode 0:
+ * the identity).  One workgroup per replicate; pi_s is sorted in LDS, hence n <= 4096.  count = 0 succeeds and reads nothing.  Neither
+ * allocates nor synchronises.  Refuses (GSS_EINVAL, by name): n outside [2, 4096], lda or ldb < n, a mode outside 0..1, count < 0, mode 0
+ * with anything but first = 0 and count = 1, first < 0 or first + count > 2^31, a null a, b or out; out is then untouched.  Values are not
+ * inspected: a NaN or an infinity propagates into the sums it is a term of (mantel.py refuses NaN before the call). */
+int gss_matrix_cross_sums(int32_t n, const double *a, int64_t lda, const double *b, int64_t ldb, int32_t mode, uint64_t seed, int64_t first,
+                          int64_t count, double *out, int32_t *perm_out, void *stream);
 
 /* ---- the mean and the median of resampled series: bootstrap intervals and sign-flip tests of the per-indication metrics (resample.py,
  * compare_methods.py, evaluate_auc.py --bootstrap; the reference prints point estimates only, evaluate_auc.py:170)
