@@ -205,7 +205,7 @@ def test_gpu_ppr_workspace_guards_over_a_size_sweep():
         x, it = eng.run(*[hp[0], hp[2], hp[1]])
         eng.check_guards()
         got = x[:, :n_start].t().contiguous().cpu().numpy()
-        for c in (0, n_start - 1):
+        for c in range(n_start):   # every column: those beside the 32- and 64-column boundaries too
             ref, ref_it = O.diffusion_profile(m0, int(starts[c]), prot, *hp)
             assert np.abs(got[c] - ref).max() < 1e-13 and it[c] == ref_it, (n, n_start, c)
 
