@@ -176,6 +176,8 @@ SIGNATURES = {
     "gss_auc_rows": (C.c_int, [_I32, _I32, _P, _I64, _P, _P, _P, _P, _P, _P]),
     "gss_rank_metrics_workspace_bytes": (_SZ, [_I32, _I32]),
     "gss_rank_metrics_rows": (C.c_int, [_I32, _I32, _P, _I64, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "gss_rank_strata_workspace_bytes": (_SZ, [_I64]),
+    "gss_rank_metrics_strata": (C.c_int, [_I32, _I32, _P, _I64, _P, _P, _I32, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "gss_profile_dist": (C.c_int, [_I32, _P, _I64, _I32, _P, _I32, _P, _I32, _P, _I64, _P]),
     "gss_profile_dist_pairs_workspace_bytes": (_SZ, [_I32, _I32]),
     "gss_profile_dist_pairs": (C.c_int, [_I32, _P, _I64, _I32, _P, _P, _I32, _P, _P, _SZ, _P]),

@@ -187,16 +187,17 @@ def parse_args(argv=None):
     return p.parse_args(argv)
 
 
-def parse_levels(text):
+def parse_levels(text, flag="--levels"):
+    """flag: the option the refusals name (evaluate_auc.py calls it --class-levels)"""
     try:
         levels = [int(t) for t in str(text).split(",")]
     except ValueError:
-        raise PredictError(f"--levels {text!r} must be comma-separated integers out of 1,2,3,4") from None
+        raise PredictError(f"{flag} {text!r} must be comma-separated integers out of 1,2,3,4") from None
     for k in levels:
         if k not in LEVELS:
-            raise PredictError(f"--levels: level {k} is unknown; the ATC levels are 1, 2, 3 and 4")
+            raise PredictError(f"{flag}: level {k} is unknown; the ATC levels are 1, 2, 3 and 4")
     if len(set(levels)) != len(levels):
-        raise PredictError(f"--levels {text!r} repeats a level")
+        raise PredictError(f"{flag} {text!r} repeats a level")
     return sorted(levels)
 
 
@@ -212,17 +213,18 @@ def check_args(levels, metric, min_size, samples):
     return levels
 
 
-def read_classes(path, levels):
+def read_classes(path, levels, flag="--classes"):
     """the table -> (the drug ids in order of first appearance, {level: {class code: [name, [drug ids, each once, in file order]]}}).  A drug
-    carries one row per ATC code, so it can be in several classes of a level; an empty or NA code names no class"""
+    carries one row per ATC code, so it can be in several classes of a level; an empty or NA code names no class.  flag: the option the
+    refusals name (evaluate_auc.py calls it --by-class)"""
     with open(path, newline="") as f:
         rows = list(csv.reader(f, delimiter="\t"))
     if not rows:
-        raise PredictError(f"--classes {path}: the table is empty")
+        raise PredictError(f"{flag} {path}: the table is empty")
     head = {h: i for i, h in enumerate(rows[0])}
     for col in ["db_id"] + [c for k in levels for c in (f"level_{k}", f"level_{k}_name")]:
         if col not in head:
-            raise PredictError(f"--classes {path}: column {col!r} is missing")
+            raise PredictError(f"{flag} {path}: column {col!r} is missing")
     drugs, table = {}, {k: {} for k in levels}
     for r in rows[1:]:
         if not any(r):

@@ -2,7 +2,8 @@
 // (rank_metrics.hip) and gss_profile_rank (profile_rank.hip).  A score becomes an order-preserving uint64 key (-0.0 folded into +0.0), a
 // power-of-two block of keys is bitonic-sorted in LDS, and "below" and "tied" are a lower-bound and an upper-bound binary search: every
 // rule of the three files depends on those integer counts alone.  The two row kernels also share what they refuse: the positives' list
-// of a row, checked while its bitmap is built, and the refusals' way back to the host.  Inline device and host code only.
+// of a row, checked while its bitmap is built, and the refusals' way back to the host.  gss_rank_metrics_strata (rank_strata.hip) uses
+// all of it once more, per stratum of a row.  Inline device and host code only.
 #pragma once
 #include "device_scope.h"
 

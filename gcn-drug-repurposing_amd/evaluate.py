@@ -14,6 +14,10 @@ DESIGN.md section 9.8).  Without it nothing here launches or prints anything it 
 
 --bootstrap B adds, behind those lines, one line per reported metric with the percentile intervals of its median and mean over B bootstrap
 resamples of the indications (csrc/resample.hip through resample.bootstrap_summary).  The same holds without it.
+
+--by-class TABLE adds the AUC and the --metrics per ATC drug class: one stratum per (indication, class) pair with a listed drug in common,
+the class's listed drugs ranked against all the indication's unlisted drugs, every stratum in one launch (csrc/rank_strata.hip through
+device_metrics_strata), a table per class, optionally one per pair, and one more line.  The same holds without it.
 """
 from __future__ import annotations
 
@@ -56,6 +60,13 @@ def parse_args(argv=None):
                    help="also print, per reported metric, the percentile intervals of the median and the mean over this many bootstrap "
                         "resamples of the indications (seeded by --seed)")
     p.add_argument("--level", default=0.95, type=float, help="coverage of the --bootstrap intervals (default: 0.95)")
+    p.add_argument("--by-class", default=None, type=str,
+                   help="the drug-class table (data/drug_classification_df.tsv): also report the AUC and the --metrics per ATC class, over "
+                        "the (indication, class) pairs with a listed drug in common, each ranked against all the indication's unlisted drugs")
+    p.add_argument("--class-levels", default=None, type=str, help="ATC levels of --by-class, comma-separated (default: 1,2,3,4)")
+    p.add_argument("--min-indications", default=1, type=int, help="drop classes with fewer (indication, class) pairs from --per-class (default: 1)")
+    p.add_argument("--per-class", default=None, type=str, help="the table of --by-class, one row per class (default: class_metrics.tsv)")
+    p.add_argument("--per-stratum", default=None, type=str, help="with --by-class, also write one row per (indication, class) pair")
     return p.parse_args(argv)
 
 
@@ -290,6 +301,161 @@ def device_aucs(scores, pos_ptr, pos_col, timings=None):
     return auc, n_pos, n_neg
 
 
+def device_metrics_strata(scores, pos_ptr, pos_col, str_ptr, sub_ptr, sub_col, ks, timings=None):
+    """device_metrics per stratum of a row (csrc/rank_strata.hip, one launch): row r owns strata str_ptr[r] .. str_ptr[r + 1], stratum s
+    has the positives sub_col[sub_ptr[s] .. sub_ptr[s + 1]), a subset of its row's, and is ranked against all of the row's negatives; the
+    row's other positives are left out of it -> host (auc [S], ap [S], hits [S, len(ks)], s_pos [S], n_pos [R], n_neg [R]); NaN in auc, ap
+    and hits where a stratum is empty or its row has no negative.  Every word is what device_metrics returns for the stratum gathered into
+    a row of its own.  Shape checks on the host first; no CPU fallback; scores and timings as device_metrics takes them."""
+    import torch
+
+    from . import _lib
+    who = "device_metrics_strata"
+    s, ptr, col = _device_inputs(who, scores, pos_ptr, pos_col)
+    h_ks = check_cuts(who, ks)
+    sp, qp, qc = (np.ascontiguousarray(a, dtype=np.int32) for a in (str_ptr, sub_ptr, sub_col))
+    (R, C), nk = s.shape, len(h_ks)
+    if sp.shape != (R + 1,) or sp[0] != 0 or np.any(np.diff(sp) < 0):
+        raise PredictError(f"{who}: the strata's row pointer ({len(sp)} entries) is not one over {R} rows")
+    S = int(sp[-1])
+    if qp.shape != (S + 1,) or qp[0] != 0 or np.any(np.diff(qp) < 0) or qp[-1] != len(qc):
+        raise PredictError(f"{who}: the strata's pointer ({len(qp)} entries over {len(qc)} columns) is not one over {S} strata")
+    if R == 0 or S == 0:
+        n_pos = np.diff(ptr).astype(np.int32)
+        return np.zeros(0), np.zeros(0), np.zeros((0, nk)), np.zeros(0, np.int32), n_pos, (C - n_pos).astype(np.int32)
+    t = {} if timings is None else timings
+    lib = _lib.load()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    dev = torch.device("cuda")
+    b = _row_buffers(dev, s, ptr, col)
+    d_sp, d_qp = torch.from_numpy(sp).to(dev), torch.from_numpy(qp).to(dev)
+    d_qc = torch.from_numpy(qc if len(qc) else np.zeros(1, np.int32)).to(dev)
+    d_out = torch.empty(S * (2 + max(nk, 1)), dtype=torch.float64, device=dev)       # auc [S], ap [S], hits [S][nk]
+    d_cnt = torch.empty(2 * S, dtype=torch.int32, device=dev)                        # s_pos [S], s_neg [S]
+    d_work = torch.empty(max(len(qc), 1), dtype=torch.int64, device=dev)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    _lib.check(lib.gss_rank_metrics_strata(R, C, _lib.ptr(b.d_scores), C, _lib.ptr(b.d_ptr), _lib.ptr(b.d_col), S, _lib.ptr(d_sp), _lib.ptr(d_qp),
+                                           _lib.ptr(d_qc), nk, h_ks.ctypes.data if nk else None, _lib.ptr(d_out), _lib.ptr(d_out[S:]),
+                                           _lib.ptr(d_out[2 * S:]), _lib.ptr(d_cnt), _lib.ptr(d_cnt[S:]), _lib.ptr(b.d_pos), _lib.ptr(b.d_neg),
+                                           _lib.ptr(d_work), d_work.numel() * 8, _lib.current_stream()), "gss_rank_metrics_strata")
+    t["upload_s"], t["kernel_s"] = t1 - t0, time.perf_counter() - t1
+    out = d_out.cpu().numpy()
+    return (out[:S], out[S:2 * S], out[2 * S:2 * S + S * nk].reshape(S, nk), d_cnt[:S].cpu().numpy(), b.d_pos.cpu().numpy(),
+            b.d_neg.cpu().numpy())
+
+
+# ---- drug classes: the metrics per (indication, class) ----------------------------------------------------------------------------------
+
+CLASS_HEADER = ["level", "class", "class_name", "drugs", "indications", "positives"]
+PER_STRATUM_HEADER = ["level", "class", "indication", "name", "positives", "negatives", "auc"]
+
+
+def class_columns(drugs, table_drugs, table):
+    """classes.read_classes' table on the evaluation's drug columns -> ([(level, code, name, [columns, ascending])] by level, then code,
+    of the classes with a member among `drugs`; how many of the table's drugs are no drug column)"""
+    col_of = {d: k for k, d in enumerate(drugs)}
+    out = []
+    for level in sorted(table):
+        for code in sorted(table[level]):
+            name, members = table[level][code]
+            cols = sorted(col_of[d] for d in members if d in col_of)
+            if cols:
+                out.append((level, code, name, cols))
+    return out, sum(1 for d in table_drugs if d not in col_of)
+
+
+def class_strata(pos_ptr, pos_col, classes, rows=None):
+    """classes: [(level, code, name, [drug columns])] -> (str_ptr [R + 1], sub_ptr [S + 1], sub_col, owner [S] = (row, class index)): one
+    stratum per (row, class) with a positive of the row among the class's columns, in row order, then class order; its columns in the
+    order of the row's pos_col.  A drug in several classes is in several strata.  rows: the rows that get strata (default: every row)."""
+    ptr, col = np.asarray(pos_ptr, np.int64), np.asarray(pos_col, np.int64)
+    of_col = {}
+    for k, cl in enumerate(classes):
+        for c in dict.fromkeys(int(c) for c in cl[3]):
+            of_col.setdefault(c, []).append(k)
+    wanted = None if rows is None else {int(r) for r in rows}
+    str_ptr, sub_ptr, sub_col, owner = [0], [0], [], []
+    for r in range(len(ptr) - 1):
+        if wanted is None or r in wanted:
+            members = {}
+            for c in col[ptr[r]:ptr[r + 1]]:
+                for k in of_col.get(int(c), ()):
+                    members.setdefault(k, []).append(int(c))
+            for k in sorted(members):
+                sub_col += members[k]
+                sub_ptr.append(len(sub_col))
+                owner.append((r, k))
+        str_ptr.append(len(owner))
+    return np.asarray(str_ptr, np.int32), np.asarray(sub_ptr, np.int32), np.asarray(sub_col, np.int32), owner
+
+
+def class_metric_names(metrics):
+    """the columns of the class tables: auc, then the requested metrics in order"""
+    return ["auc"] + [n for n in metrics if n != "auc"]
+
+
+class Strata:
+    """the per-(indication, class) half of a Result: the classes [(level, code, name, [columns])], owner [S] = (row, class index), the
+    strata's CSR, |Q_s| per stratum and {name: fp64 [S]} for auc and the requested metrics"""
+
+    def __init__(self, levels, classes, unknown_drugs, str_ptr, sub_ptr, sub_col, owner, s_pos, values):
+        self.levels, self.classes, self.unknown_drugs = list(levels), classes, unknown_drugs
+        self.str_ptr, self.sub_ptr, self.sub_col, self.owner = str_ptr, sub_ptr, sub_col, owner
+        self.s_pos, self.metrics = np.asarray(s_pos), values
+        self.of_class = {}                        # class index -> its strata, in indication order
+        for s, (_, k) in enumerate(owner):
+            self.of_class.setdefault(k, []).append(s)
+        self.line = None
+
+    def class_rows(self, min_indications=1):
+        """the per-class table: one row per class with at least min_indications strata, by level, then code"""
+        rows = []
+        for k, (level, code, name, cols) in enumerate(self.classes):
+            idx = self.of_class.get(k, [])
+            if len(idx) < max(min_indications, 1):
+                continue
+            row = [level, code, name, len(cols), len(idx), int(self.s_pos[idx].sum())]
+            for v in self.metrics.values():
+                row += [repr(float(np.median(v[idx]))), repr(float(v[idx].mean()))]
+            rows.append(row)
+        return rows
+
+
+def stratify(res, classes, metrics, pos_ptr, pos_col, strata_source, err):
+    """run()'s --by-class half: classes = classes.read_classes' (drugs, table) -> Strata of Result res, over the rows of res.kept alone"""
+    table_drugs, table = classes
+    cls, unknown = class_columns(res.drugs, table_drugs, table)
+    if unknown:
+        print(f"evaluate_auc: {unknown} drugs of the class table are not drug nodes of the graph; they are left out", file=err)
+    str_ptr, sub_ptr, sub_col, owner = class_strata(pos_ptr, pos_col, cls, rows=res.kept)
+    ks = metric_cuts(metrics)
+    auc, ap, hits, s_pos, _, _ = strata_source(res.scores, pos_ptr, pos_col, str_ptr, sub_ptr, sub_col, ks)
+    names = class_metric_names(metrics)
+    values = metric_arrays(names, ks, auc, ap, hits, s_pos)
+    return Strata(sorted(table), cls, unknown, str_ptr, sub_ptr, sub_col, owner, s_pos, values)
+
+
+def write_class_tables(g, res, per_class, per_stratum, min_indications):
+    """the two tables of --by-class -> the number of classes written to per_class"""
+    st = res.strata
+    rows = st.class_rows(min_indications)
+    with open(per_class, "w", newline="") as f:
+        w = csv.writer(f, delimiter="\t", lineterminator="\n")
+        w.writerow(CLASS_HEADER + [f"{stat}_{n}" for n in st.metrics for stat in ("median", "mean")])
+        w.writerows(rows)
+    if per_stratum:
+        with open(per_stratum, "w", newline="") as f:
+            w = csv.writer(f, delimiter="\t", lineterminator="\n")
+            w.writerow(PER_STRATUM_HEADER + list(st.metrics)[1:])
+            for s, (r, k) in enumerate(st.owner):
+                i = res.indications[r]
+                w.writerow([st.classes[k][0], st.classes[k][1], i, display(g, i), int(st.s_pos[s]), int(res.n_neg[r])]
+                           + [repr(float(v[s])) for v in st.metrics.values()])
+    return len(rows)
+
+
 # ---- scores and labels ---------------------------------------------------------------------------------------------------------------
 
 def score_rows(s, g, seed):
@@ -351,6 +517,7 @@ class Result:
         self.drugs, self.scores = drugs, scores    # what was ranked: scores [indications][drugs] (a device tensor under diffusion.compare = a metric)
         self.skipped, self.unknown_pairs = skipped, unknown
         self.kept = [k for k in range(len(inds)) if n_pos[k] > 0 and n_neg[k] > 0]
+        self.strata = None                         # the Strata of run(classes=...)
         self.line = format_line(auc[self.kept])
         self.metric_lines = [format_metric_line(name, v[self.kept]) for name, v in self.metrics.items()]   # over the AUC line's indications
 
@@ -391,11 +558,14 @@ def write_per_indication(path, g, res):
                        + [repr(float(v[k])) for v in res.metrics.values()])
 
 
-def run(s, seed=0, per_indication=None, auc_source=device_aucs, timings=None, err=None, metrics=(), metric_source=device_metrics):
+def run(s, seed=0, per_indication=None, auc_source=device_aucs, timings=None, err=None, metrics=(), metric_source=device_metrics, classes=None,
+        strata_source=device_metrics_strata, per_class="class_metrics.tsv", per_stratum=None, min_indications=1):
     """evaluate_auc.main on Settings s -> Result (per-indication AUCs, counts, skipped indications by reason, the stdout line).
     auc_source(scores, pos_ptr, pos_col) -> (auc, n_pos, n_neg), NaN where a row has one class.  With metrics (names parse_metrics
     accepts) the one call is metric_source(scores, pos_ptr, pos_col, ks) -> (auc, ap, hits [R, len(ks)], n_pos, n_neg) instead, and the
-    Result carries ap, the metrics' arrays and one line per metric."""
+    Result carries ap, the metrics' arrays and one line per metric.  With classes (classes.read_classes' pair: the table's drugs and
+    {level: {code: [name, drugs]}}) the Result also carries .strata, the AUC and the metrics of every (indication, class) pair with a listed
+    drug in common, out of one call of strata_source (device_metrics_strata's arguments and results), and the two tables are written."""
     metrics = parse_metrics(metrics) if metrics else []
     err = sys.stderr if err is None else err
     t = {} if timings is None else timings
@@ -432,6 +602,13 @@ def run(s, seed=0, per_indication=None, auc_source=device_aucs, timings=None, er
         raise PredictError(f"no indication has both a listed drug and an unlisted one in {s.labels!r}; there is no AUC to report")
     if per_indication:
         write_per_indication(per_indication, g, res)
+    if classes is not None:
+        t3 = time.perf_counter()
+        res.strata = stratify(res, classes, metrics, pos_ptr, pos_col, strata_source, err)
+        t["strata_s"] = time.perf_counter() - t3
+        n = write_class_tables(g, res, per_class, per_stratum, min_indications)
+        res.strata.line = (f"classes: {n} classes of levels {','.join(str(k) for k in res.strata.levels)} over {len(res.strata.owner)} "
+                           f"(indication, class) pairs: {per_class}")
     t["total_s"] = time.perf_counter() - t0
     return res
 
@@ -543,8 +720,24 @@ class DeviceEvaluator:
         return res
 
 
-def main(argv=None, auc_source=device_aucs, metric_source=device_metrics):
-    """the command line; the two sources are run()'s (the host tests put their mirrors there)"""
+def read_class_table(args):
+    """--by-class and its companions, checked before anything touches the GPU -> classes.read_classes' pair, or None without --by-class"""
+    from . import classes
+    if args.min_indications < 1:
+        raise PredictError(f"--min-indications {args.min_indications} must be at least 1")
+    if args.by_class is None:
+        for flag, value in (("--class-levels", args.class_levels), ("--per-class", args.per_class), ("--per-stratum", args.per_stratum)):
+            if value is not None:
+                raise PredictError(f"{flag} needs --by-class, the drug-class table")
+        return None
+    levels = classes.parse_levels("1,2,3,4" if args.class_levels is None else args.class_levels, flag="--class-levels")
+    if not os.path.exists(args.by_class):
+        raise PredictError(f"--by-class {args.by_class!r} does not exist")
+    return classes.read_classes(args.by_class, levels, flag="--by-class")
+
+
+def main(argv=None, auc_source=device_aucs, metric_source=device_metrics, strata_source=device_metrics_strata):
+    """the command line; the three sources are run()'s (the host tests put their mirrors there)"""
     args = parse_args(argv)
     try:
         metrics = parse_metrics(args.metrics) if args.metrics is not None else []
@@ -552,12 +745,15 @@ def main(argv=None, auc_source=device_aucs, metric_source=device_metrics):
             raise PredictError(f"--bootstrap {args.bootstrap} must be at least 2")
         if not 0.0 < args.level < 1.0:
             raise PredictError(f"--level {args.level} must lie strictly between 0 and 1")
+        by_class = read_class_table(args)
         s = Settings(load_config(args.config))
     except (PredictError, OSError, json.JSONDecodeError) as e:
         print(f"evaluate_auc: {e}", file=sys.stderr)
         sys.exit(2)
     try:
-        res = run(s, args.seed, args.per_indication, auc_source=auc_source, metrics=metrics, metric_source=metric_source)
+        res = run(s, args.seed, args.per_indication, auc_source=auc_source, metrics=metrics, metric_source=metric_source, classes=by_class,
+                  strata_source=strata_source, per_class=args.per_class or "class_metrics.tsv", per_stratum=args.per_stratum,
+                  min_indications=args.min_indications)
         extra = bootstrap_lines(res, args.bootstrap, args.level, args.seed) if args.bootstrap is not None else []
     except (PredictError, OSError) as e:
         print(f"evaluate_auc: {e}", file=sys.stderr)
@@ -567,3 +763,5 @@ def main(argv=None, auc_source=device_aucs, metric_source=device_metrics):
         print(line)
     for line in extra:
         print(line)
+    if res.strata is not None:
+        print(res.strata.line)

@@ -500,6 +500,31 @@ int gss_rank_metrics_rows(int32_t R, int32_t C, const double *scores, int64_t ld
                           const int32_t *h_ks, double *auc, double *ap, double *hits, int32_t *n_pos, int32_t *n_neg, void *workspace,
                           size_t workspace_bytes, void *stream);
 
+/* ---- the same three statistics per stratum of a row: which kinds of drugs a method ranks well (evaluate_auc.py --by-class: AUROC, AP and
+ * recall@50 by ATC drug class, as the multiscale-interactome work breaks them down)
+ * gss_rank_metrics_strata: scores, pos_ptr, pos_col, h_ks as gss_rank_metrics_rows takes them; S strata, row r owning strata
+ * str_ptr[r] .. str_ptr[r + 1] (device int32 [R + 1], a row pointer over [0, S]); stratum s has the positives Q_s =
+ * sub_col[sub_ptr[s] .. sub_ptr[s + 1]) (device int32 [S + 1] and [sub_ptr[S]]: columns, any order), a subset of its row's positives P_r;
+ * strata of a row may overlap -> device auc [S], ap [S], hits [S][nk] fp64, s_pos [S], s_neg [S], n_pos [R], n_neg [R] int32.
+ * Stratum s is the sub-problem whose candidates are the row's N negatives and Q_s, C_s = N + |Q_s| columns: the row's other positives are
+ * neither positive nor negative.  Its auc, ap and hits (at k' = min(k, C_s)) are what gss_rank_metrics_rows defines on those candidates,
+ * and every output word is bit for bit the word gss_rank_metrics_rows writes for that sub-problem gathered into a row of its own; a
+ * stratum with all of the row's positives has the row's words.  |Q_s| = 0 or N = 0 gives NaN in auc, ap and every hits word.
+ * s_pos[s] = |Q_s|, s_neg[s] = N; n_pos and n_neg as gss_rank_metrics_rows writes them.  Permuting a stratum's sub_col entries, a row's
+ * strata or the columns changes no bit of any stratum, and no result goes through an atomic.
+ * One workgroup per row checks and sorts each stratum's keys in LDS, parks them at workspace[sub_ptr[s] ..) (device, 8-byte aligned, at
+ * least gss_rank_strata_workspace_bytes(sub_ptr[S]) = 8 sub_ptr[S] bytes; nothing is allocated inside), sorts the row's negatives once in
+ * the same LDS and serves every stratum by binary search, so 1 <= C <= 16384 with any |Q_s|.  Synchronises the stream and refuses
+ * (GSS_EINVAL, by name behind "rank_metrics_strata:") what gss_rank_metrics_rows refuses, S < 0, a str_ptr that is not a row pointer over
+ * [0, S] (0 first, non-decreasing, S last), a sub_ptr that is not one over the strata (0 first, non-decreasing, at most P_r per stratum;
+ * row and stratum named), a sub_col that is not a positive of its row or is repeated within its stratum (row, stratum and column named),
+ * and a workspace that is too small or misaligned; the outputs are then unspecified.  R = 0 or S = 0 succeeds and reads nothing. */
+size_t gss_rank_strata_workspace_bytes(int64_t n_sub);
+int gss_rank_metrics_strata(int32_t R, int32_t C, const double *scores, int64_t ld, const int32_t *pos_ptr, const int32_t *pos_col, int32_t S,
+                            const int32_t *str_ptr, const int32_t *sub_ptr, const int32_t *sub_col, int32_t nk, const int32_t *h_ks, double *auc,
+                            double *ap, double *hits, int32_t *s_pos, int32_t *s_neg, int32_t *n_pos, int32_t *n_neg, void *workspace,
+                            size_t workspace_bytes, void *stream);
+
 /* ---- pairwise distances between diffusion profiles (multiscale/README.md, overview (c): "by comparing the diffusion profiles of a drug and
  * a disease ...")
  * gss_profile_dist: device fp64 x [n][ld], profile c = column c (the layout gss_ppr_run writes, so profiles go from the power iteration into
