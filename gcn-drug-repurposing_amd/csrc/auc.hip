@@ -7,35 +7,34 @@
 //   2 U = sum over positives of (lower_bound + upper_bound) = sum of (2 * below + tied),   AUC = 2 U / (2 P N)
 // which is the average-rank (Mann-Whitney) form of roc_auc_score.  The counts are integers, so the result depends only on the multiset
 // of (score, label) pairs; every output word is written by the one thread that owns it (no atomics on results: bitwise deterministic).
-#include "rank_keys.h"
+// The limits, the argument checks and the refusals' way back are rank_score.h's, shared with rank_metrics.hip and rank_strata.hip.  Their
+// scoring body is not used here: this kernel sorts once and has no workspace to park its positives in, so it keeps its own loop.
+#include "rank_score.h"
 
 namespace gss {
 namespace {
 
-constexpr int kAucThreads = 256;
-constexpr int kMaxCols = 16384;                 // the sort buffer: pow2ceil(C) keys of 8 bytes in LDS (128 KiB at the limit)
-
-__global__ __launch_bounds__(kAucThreads) void auc_rows_kernel(int32_t C, int32_t cpad, const double *__restrict__ scores, int64_t ld,
-                                                               const int32_t *__restrict__ pos_ptr, const int32_t *__restrict__ pos_col,
-                                                               double *__restrict__ auc, int32_t *__restrict__ n_pos,
-                                                               int32_t *__restrict__ n_neg) {
+__global__ __launch_bounds__(kRankThreads) void auc_rows_kernel(int32_t C, int32_t cpad, const double *__restrict__ scores, int64_t ld,
+                                                                const int32_t *__restrict__ pos_ptr, const int32_t *__restrict__ pos_col,
+                                                                double *__restrict__ auc, int32_t *__restrict__ n_pos,
+                                                                int32_t *__restrict__ n_neg) {
   extern __shared__ __align__(16) unsigned char lds[];
   uint64_t *key = reinterpret_cast<uint64_t *>(lds);                     // [cpad]
   uint32_t *is_pos = reinterpret_cast<uint32_t *>(lds + (size_t)cpad * 8);  // [cpad / 32] bitmap
-  __shared__ unsigned long long partial[kAucThreads / kWave];
+  __shared__ unsigned long long partial[kRankThreads / kWave];
   const int32_t r = blockIdx.x, tid = threadIdx.x;
   const double *row = scores + (int64_t)r * ld;
   int32_t b, P;
   // the negatives' keys: the positives get the all-ones key and sort behind them
   if (!row_positives(pos_ptr, r, C, tid, n_pos, n_neg, b, P) ||
-      !mark_and_fill<kAucThreads, false>(C, cpad, row, pos_col + b, P, tid, key, is_pos, &n_pos[r], &n_neg[r])) {
+      !mark_and_fill<kRankThreads, false>(C, cpad, row, pos_col + b, P, tid, key, is_pos, &n_pos[r], &n_neg[r])) {
     if (tid == 0) auc[r] = __longlong_as_double(0x7ff8000000000000ll);   // refused, or one class
     return;                                                               // uniform: both answers are the workgroup's
   }
   const int32_t N = C - P;
-  sort_keys<kAucThreads>(key, cpad, tid);   // ascending: the N negatives' keys come first
+  sort_keys<kRankThreads>(key, cpad, tid);   // ascending: the N negatives' keys come first
   unsigned long long twice_u = 0;
-  for (int32_t k = tid; k < P; k += kAucThreads) {
+  for (int32_t k = tid; k < P; k += kRankThreads) {
     const uint64_t kp = order_key(row[pos_col[b + k]]);
     twice_u += (unsigned long long)search(key, 0, N, kp, false) + (unsigned long long)search(key, 0, N, kp, true);
   }
@@ -45,7 +44,7 @@ __global__ __launch_bounds__(kAucThreads) void auc_rows_kernel(int32_t C, int32_
   __syncthreads();
   if (tid == 0) {
     unsigned long long s = 0;
-    for (int w = 0; w < kAucThreads / kWave; ++w) s += partial[w];
+    for (int w = 0; w < kRankThreads / kWave; ++w) s += partial[w];
     auc[r] = (double)s / (2.0 * (double)P * (double)N);   // s < 2^53 and 2 P N < 2^53: exact operands, one rounding
     n_pos[r] = P;
     n_neg[r] = N;
@@ -61,16 +60,14 @@ extern "C" {
 
 int gss_auc_rows(int32_t R, int32_t C, const double *scores, int64_t ld, const int32_t *pos_ptr, const int32_t *pos_col, double *auc,
                  int32_t *n_pos, int32_t *n_neg, void *stream) {
-  GSS_REQUIRE(R >= 0, "auc_rows: R=%d rows must be >= 0", R);
-  GSS_REQUIRE(C >= 1, "auc_rows: C=%d candidates must be >= 1", C);
-  GSS_REQUIRE(C <= kMaxCols, "auc_rows: C=%d candidates is above the limit of %d per row (one workgroup sorts a row in LDS)", C, kMaxCols);
-  GSS_REQUIRE(ld >= C, "auc_rows: ld=%lld is below C=%d", (long long)ld, C);
+  RankCuts none;
+  if (int rc = check_rank_args("auc_rows", R, C, ld, 0, nullptr, none)) return rc;
   if (R == 0) return GSS_OK;
   GSS_REQUIRE(scores && pos_ptr && pos_col && auc && n_pos && n_neg, "auc_rows: null argument");
   hipStream_t st = as_stream(stream);
   const int32_t cpad = pow2_at_least(C);
   const size_t lds = (size_t)cpad * 8 + (size_t)cpad / 8;
-  hipLaunchKernelGGL(auc_rows_kernel, dim3(R), dim3(kAucThreads), lds_request(auc_rows_kernel, lds), st, C, cpad, scores, ld, pos_ptr,
+  hipLaunchKernelGGL(auc_rows_kernel, dim3(R), dim3(kRankThreads), lds_request(auc_rows_kernel, lds), st, C, cpad, scores, ld, pos_ptr,
                      pos_col, auc, n_pos, n_neg);
   GSS_LAUNCH_CHECK("auc_rows_kernel");
   return read_refusals("auc_rows", R, C, n_pos, n_neg, st);

@@ -1,9 +1,10 @@
 // rank_keys.h -- how a double becomes a key and how ties are counted: the one statement behind gss_auc_rows (auc.hip), gss_rank_metrics_rows
 // (rank_metrics.hip) and gss_profile_rank (profile_rank.hip).  A score becomes an order-preserving uint64 key (-0.0 folded into +0.0), a
 // power-of-two block of keys is bitonic-sorted in LDS, and "below" and "tied" are a lower-bound and an upper-bound binary search: every
-// rule of the three files depends on those integer counts alone.  The two row kernels also share what they refuse: the positives' list
-// of a row, checked while its bitmap is built, and the refusals' way back to the host.  gss_rank_metrics_strata (rank_strata.hip) uses
-// all of it once more, per stratum of a row.  Inline device and host code only.
+// rule of the three files depends on those integer counts alone.  The row kernels (auc.hip, rank_metrics.hip, rank_strata.hip) also
+// share what they refuse on the device: the positives' list of a row, checked while its bitmap is built.  What those three share above
+// this -- the limits, the scoring body of the two that rank with cut-offs, the argument checks and the refusals' way back to the host --
+// is rank_score.h, which includes this file.  Inline code only.
 #pragma once
 #include "device_scope.h"
 
@@ -159,23 +160,6 @@ __device__ __forceinline__ bool mark_and_fill(int32_t C, int32_t cpad, const dou
     }
   }
   return false;
-}
-
-// The refusals come back in the count words: -code in n_pos, the column in n_neg.  Reads both arrays of R words back on the stream,
-// waits for it, and names the first refused row in the words of entry point `who` ("auc_rows", "rank_metrics_rows")
-inline int read_refusals(const char *who, int32_t R, int32_t C, const int32_t *n_pos, const int32_t *n_neg, hipStream_t st) {
-  std::unique_ptr<int32_t[]> h(new (std::nothrow) int32_t[(size_t)2 * R]);
-  if (!h) return fail(GSS_ENOMEM, "%s: host status buffer of %d rows", who, R);
-  GSS_HIP(hipMemcpyAsync(h.get(), n_pos, (size_t)R * 4, hipMemcpyDeviceToHost, st));   // no wait of its own: the stream orders it before n_neg's
-  if (int rc = read_back(h.get() + R, n_neg, (size_t)R * 4, st)) return rc;
-  for (int32_t r = 0; r < R; ++r) {
-    const int32_t code = -h[r], col = h[R + r];
-    GSS_REQUIRE(code != kBadPtr, "%s: row %d: pos_ptr is not a CSR row pointer (0 first, non-decreasing, at most C=%d per row; %d here)", who, r, C, col);
-    GSS_REQUIRE(code != kColRange, "%s: row %d: pos_col %d is outside [0, %d)", who, r, col, C);
-    GSS_REQUIRE(code != kColRepeat, "%s: row %d: pos_col %d is repeated", who, r, col);
-    GSS_REQUIRE(code != kNonFinite, "%s: row %d, column %d: the score is NaN or infinite (roc_auc_score refuses it)", who, r, col);
-  }
-  return GSS_OK;
 }
 
 }  // namespace gss

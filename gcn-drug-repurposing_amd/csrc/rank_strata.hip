@@ -9,48 +9,33 @@
 //   2. each of the row's strata in turn: its list is checked against that bitmap and, through a second bitmap, for a repeated column;
 //      its |Q| keys are sorted in the LDS key buffer at pow2_at_least(|Q|) and parked at ws[sub_ptr[s] ..);
 //   3. the row's negatives are sorted ONCE and stay in LDS;
-//   4. each stratum in turn runs rank_metrics_kernel's loop over its parked keys: the same thread-to-positive assignment, the same wave
-//      butterfly, the same order of the four waves and the same integer expressions with P = |Q| and m = C_s - min(k, C_s).  A positive's
-//      counts among the negatives do not depend on which other positives are in play, so the integers, and with them the bits, are those
-//      of the gathered sub-problem.
+//   4. each stratum in turn hands its parked keys and the negatives to rank_score.h's score_positives, the scoring body
+//      rank_metrics_kernel calls for its row, with P = |Q|.  A positive's counts among the negatives do not depend on which other
+//      positives are in play, so the integers, and with them the bits, are those of the gathered sub-problem.
 // Trip counts of every loop that holds a barrier depend on str_ptr, sub_ptr and refusals found behind a barrier alone: the whole workgroup
 // reaches each barrier.  Every output word has one writer and no result goes through an atomic.
-#include "rank_keys.h"
+#include "rank_score.h"
 
 namespace gss {
 namespace {
-
-constexpr int kRsThreads = 256;
-constexpr int kRsWaves = kRsThreads / kWave;
-constexpr int kRsMaxCols = 16384;               // as rank_metrics.hip: pow2ceil(C) keys of 8 bytes in LDS (128 KiB at the limit)
-constexpr int kRsMaxCuts = 8;
 
 // what a row can be refused for beside rank_keys.h's RowRefusal (-code in n_pos[r], the offending word in n_neg[r]) ...
 enum StrataRowRefusal { kBadStrPtr = 5, kWorkspaceShort = 6 };
 // ... and a stratum (-code in s_pos[s], the offending word in s_neg[s])
 enum StratumRefusal { kBadSubPtr = 1, kSubNotPositive = 2, kSubRepeat = 3 };
 
-struct StrataCuts {
-  int32_t nk;
-  int32_t k[kRsMaxCuts];
-};
-
-__global__ __launch_bounds__(kRsThreads) void rank_strata_kernel(int32_t R, int32_t C, int32_t cpad, const double *__restrict__ scores, int64_t ld,
-                                                                 const int32_t *__restrict__ pos_ptr, const int32_t *__restrict__ pos_col,
-                                                                 int32_t S, const int32_t *__restrict__ str_ptr,
-                                                                 const int32_t *__restrict__ sub_ptr, const int32_t *__restrict__ sub_col,
-                                                                 StrataCuts cuts, double *__restrict__ auc, double *__restrict__ ap,
-                                                                 double *__restrict__ hits, int32_t *s_pos, int32_t *s_neg,
-                                                                 int32_t *__restrict__ n_pos, int32_t *__restrict__ n_neg, uint64_t *ws,
-                                                                 int64_t ws_words) {
+__global__ __launch_bounds__(kRankThreads) void rank_strata_kernel(int32_t R, int32_t C, int32_t cpad, const double *__restrict__ scores, int64_t ld,
+                                                                   const int32_t *__restrict__ pos_ptr, const int32_t *__restrict__ pos_col,
+                                                                   int32_t S, const int32_t *__restrict__ str_ptr,
+                                                                   const int32_t *__restrict__ sub_ptr, const int32_t *__restrict__ sub_col,
+                                                                   RankCuts cuts, double *__restrict__ auc, double *__restrict__ ap,
+                                                                   double *__restrict__ hits, int32_t *s_pos, int32_t *s_neg,
+                                                                   int32_t *__restrict__ n_pos, int32_t *__restrict__ n_neg, uint64_t *ws,
+                                                                   int64_t ws_words) {
   extern __shared__ __align__(16) unsigned char lds[];
   uint64_t *key = reinterpret_cast<uint64_t *>(lds);                                        // [cpad]
   uint32_t *is_pos = reinterpret_cast<uint32_t *>(lds + (size_t)cpad * 8);                  // [cpad / 32] the row's positives
   uint32_t *in_sub = reinterpret_cast<uint32_t *>(lds + (size_t)cpad * 8 + (size_t)cpad / 8);   // [cpad / 32] the stratum in hand
-  __shared__ unsigned long long part_u[kRsWaves];
-  __shared__ double part_ap[kRsWaves];
-  __shared__ int32_t part_above[kRsWaves][kRsMaxCuts];
-  __shared__ int32_t grp[kRsMaxCuts][4];   // the tie group that holds cut j's item, if it has a positive: posL, posU, negL, negU
   __shared__ int32_t bad_member, bad_again;
   const int32_t r = blockIdx.x, tid = threadIdx.x;
   const double qnan = __longlong_as_double(0x7ff8000000000000ll);
@@ -76,7 +61,7 @@ __global__ __launch_bounds__(kRsThreads) void rank_strata_kernel(int32_t R, int3
   int32_t b, P;
   if (!row_positives(pos_ptr, r, C, tid, n_pos, n_neg, b, P)) return;
   // with its counts or its refusal written where the row does not go on.  A row of one class still has its strata's lists checked
-  const bool ranked = mark_and_fill<kRsThreads, true>(C, cpad, row, pos_col + b, P, tid, key, is_pos, &n_pos[r], &n_neg[r]);
+  const bool ranked = mark_and_fill<kRankThreads, true>(C, cpad, row, pos_col + b, P, tid, key, is_pos, &n_pos[r], &n_neg[r]);
   const int32_t N = C - P;
 
   // every stratum: its list checked, its keys sorted and parked
@@ -93,9 +78,9 @@ __global__ __launch_bounds__(kRsThreads) void rank_strata_kernel(int32_t R, int3
       bad_member = INT32_MAX;
       bad_again = INT32_MAX;
     }
-    for (int32_t w = tid; w < cpad / 32; w += kRsThreads) in_sub[w] = 0u;
+    for (int32_t w = tid; w < cpad / 32; w += kRankThreads) in_sub[w] = 0u;
     __syncthreads();
-    for (int32_t k = tid; k < Q; k += kRsThreads) {
+    for (int32_t k = tid; k < Q; k += kRankThreads) {
       const int32_t c = sub_col[q0 + k];
       if (c < 0 || c >= C || !((is_pos[c >> 5] >> (c & 31)) & 1u)) {
         atomicMin(&bad_member, k);      // the first offending entry in list order
@@ -109,7 +94,7 @@ __global__ __launch_bounds__(kRsThreads) void rank_strata_kernel(int32_t R, int3
     const bool sorted = ranked && Q != 0 && member == INT32_MAX && again == INT32_MAX;   // uniform
     if (sorted) {
       const int32_t qpad = pow2_at_least(Q);                                             // <= cpad: Q <= P <= C
-      for (int32_t k = tid; k < qpad; k += kRsThreads) key[k] = k < Q ? order_key(row[sub_col[q0 + k]]) : kBehind;
+      for (int32_t k = tid; k < qpad; k += kRankThreads) key[k] = k < Q ? order_key(row[sub_col[q0 + k]]) : kBehind;
     }
     if (tid == 0) {
       if (member != INT32_MAX) {
@@ -131,8 +116,8 @@ __global__ __launch_bounds__(kRsThreads) void rank_strata_kernel(int32_t R, int3
     __syncthreads();                    // the two words are read before the next stratum resets them; the keys are filled
     if (sorted) {
       const int32_t qpad = pow2_at_least(Q);
-      sort_keys<kRsThreads>(key, qpad, tid);
-      for (int32_t i = tid; i < Q; i += kRsThreads) ws[q0 + i] = key[i];
+      sort_keys<kRankThreads>(key, qpad, tid);
+      for (int32_t i = tid; i < Q; i += kRankThreads) ws[q0 + i] = key[i];
       __syncthreads();                  // read out of LDS before the next fill overwrites them
     }
   }
@@ -145,95 +130,20 @@ __global__ __launch_bounds__(kRsThreads) void rank_strata_kernel(int32_t R, int3
   }
 
   // the negatives' keys, sorted once; they stay in LDS
-  for (int32_t c = tid; c < cpad; c += kRsThreads) {
-    uint64_t k = kBehind;
-    if (c < C && !((is_pos[c >> 5] >> (c & 31)) & 1u)) k = order_key(row[c]);
-    key[c] = k;
-  }
-  __syncthreads();
-  sort_keys<kRsThreads>(key, cpad, tid);          // its barriers also make the parked keys and the s_pos words visible to the whole workgroup
+  fill_negatives<kRankThreads>(C, cpad, row, is_pos, key, tid);
+  sort_keys<kRankThreads>(key, cpad, tid);          // its barriers also make the parked keys and the s_pos words visible to the whole workgroup
 
+  // The cut-offs are read out of the kernel's argument here, word by word.  Handing `cuts` itself to score_positives takes its address,
+  // and the compiler then copies all nine words into SGPRs at the kernel's entry, where they stay live through every loop above: 102
+  // SGPRs and 7 waves per SIMD instead of 96 and 8
+  RankCuts late;
+  late.nk = cuts.nk;
+#pragma unroll
+  for (int j = 0; j < kRankMaxCuts; ++j) late.k[j] = cuts.k[j];
   for (int32_t s = s0; s < s1; ++s) {
     const int32_t Q = s_pos[s];                   // |Q_s|, or a refusal: written above by this workgroup, uniform
     if (Q <= 0) continue;
-    const uint64_t *park = ws + sub_ptr[s];
-    const int32_t Cs = N + Q;
-    if (tid < kRsMaxCuts) grp[tid][0] = -1;
-    __syncthreads();                              // also: the last stratum's partial sums have been read
-    unsigned long long twice_u = 0;
-    double ap_sum = 0.0;
-    int32_t above[kRsMaxCuts], cut[kRsMaxCuts];
-#pragma unroll
-    for (int j = 0; j < kRsMaxCuts; ++j) {
-      above[j] = 0;
-      cut[j] = j < cuts.nk ? Cs - (cuts.k[j] < Cs ? cuts.k[j] : Cs) : 0;   // ascending index of the item of rank min(k, C_s)
-    }
-    for (int32_t i = Q - 1 - tid; i >= 0; i -= kRsThreads) {   // descending threshold
-      const uint64_t kp = park[i];
-      const int32_t negL = search(key, 0, N, kp, false), negU = search(key, negL, N, kp, true);
-      const int32_t posL = (i == 0 || park[i - 1] < kp) ? i : search(park, 0, i - 1, kp, false);
-      const int32_t posU = (i == Q - 1 || park[i + 1] > kp) ? i + 1 : search(park, i + 2, Q, kp, true);
-      twice_u += (unsigned long long)negL + (unsigned long long)negU;
-      const bool first = i == posL;
-      if (first) {
-        const long long tp = Q - posL, fp = N - negL;
-        ap_sum += (double)((long long)(posU - posL) * tp) / (double)(tp + fp);   // exact operands (< 2^53), one rounding
-      }
-      const int32_t lt = posL + negL, le = posU + negU;
-#pragma unroll
-      for (int j = 0; j < kRsMaxCuts; ++j) {
-        if (j < cuts.nk) {
-          const int32_t m = cut[j];
-          if (lt > m) above[j] += 1;
-          else if (le > m && first) {       // one group holds the item and it has one first positive: one writer
-            grp[j][1] = posU;
-            grp[j][2] = negL;
-            grp[j][3] = negU;
-            grp[j][0] = posL;
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      twice_u += __shfl_xor(twice_u, o, kWave);
-      ap_sum += __shfl_xor(ap_sum, o, kWave);
-#pragma unroll
-      for (int j = 0; j < kRsMaxCuts; ++j) above[j] += __shfl_xor(above[j], o, kWave);
-    }
-    if ((tid & (kWave - 1)) == 0) {
-      part_u[tid / kWave] = twice_u;
-      part_ap[tid / kWave] = ap_sum;
-#pragma unroll
-      for (int j = 0; j < kRsMaxCuts; ++j) part_above[tid / kWave][j] = above[j];
-    }
-    __syncthreads();
-    if (tid == 0) {
-      unsigned long long u = 0;
-      double a = 0.0;
-      for (int w = 0; w < kRsWaves; ++w) {
-        u += part_u[w];
-        a += part_ap[w];
-      }
-      auc[s] = (double)u / (2.0 * (double)Q * (double)N);   // u < 2^53 and 2 Q N < 2^53: exact operands, one rounding
-      ap[s] = a / (double)Q;
-    }
-    if (tid < cuts.nk) {
-      const int32_t m = cut[tid];
-      double h;
-      if (grp[tid][0] >= 0) {
-        const int32_t posL = grp[tid][0], posU = grp[tid][1], negL = grp[tid][2], negU = grp[tid][3];
-        const long long g = (long long)(posU - posL) + (negU - negL), pos_g = posU - posL;
-        const long long slots = (long long)(posU + negU) - m;   // k' - (C_s - le): 1 .. g
-        const double A = (double)(Q - posU);
-        h = slots == g ? A + (double)pos_g : A + (double)(pos_g * slots) / (double)g;
-      } else {
-        int32_t n = 0;
-        for (int w = 0; w < kRsWaves; ++w) n += part_above[w][tid];
-        h = (double)n;                                          // the item's group holds no positive
-      }
-      hits[(int64_t)s * cuts.nk + tid] = h;
-    }
+    score_positives<kRankThreads>(ws + sub_ptr[s], Q, key, N, late, tid, &auc[s], &ap[s], hits + (int64_t)s * late.nk);
   }
   if (tid == 0) {
     n_pos[r] = P;
@@ -260,10 +170,7 @@ int read_strata_refusals(int32_t R, int32_t C, int32_t S, const int32_t *str_ptr
                 (size_t)col * 8);
     GSS_REQUIRE(code != kBadStrPtr, "%s: row %d: str_ptr is not a row pointer over [0, %d] (0 first, non-decreasing, %d last; %d here)", who, r, S, S,
                 col);
-    GSS_REQUIRE(code != kBadPtr, "%s: row %d: pos_ptr is not a CSR row pointer (0 first, non-decreasing, at most C=%d per row; %d here)", who, r, C, col);
-    GSS_REQUIRE(code != kColRange, "%s: row %d: pos_col %d is outside [0, %d)", who, r, col, C);
-    GSS_REQUIRE(code != kColRepeat, "%s: row %d: pos_col %d is repeated", who, r, col);
-    GSS_REQUIRE(code != kNonFinite, "%s: row %d, column %d: the score is NaN or infinite (roc_auc_score refuses it)", who, r, col);
+    if (int rc = row_refusal(who, r, C, code, col)) return rc;
   }
   for (int32_t s = 0; s < S; ++s) {
     if (hs_pos[s] >= 0) continue;
@@ -295,21 +202,9 @@ int gss_rank_metrics_strata(int32_t R, int32_t C, const double *scores, int64_t 
                             const int32_t *str_ptr, const int32_t *sub_ptr, const int32_t *sub_col, int32_t nk, const int32_t *ks, double *auc,
                             double *ap, double *hits, int32_t *s_pos, int32_t *s_neg, int32_t *n_pos, int32_t *n_neg, void *workspace,
                             size_t workspace_bytes, void *stream) {
-  GSS_REQUIRE(R >= 0, "rank_metrics_strata: R=%d rows must be >= 0", R);
-  GSS_REQUIRE(C >= 1, "rank_metrics_strata: C=%d candidates must be >= 1", C);
-  GSS_REQUIRE(C <= kRsMaxCols, "rank_metrics_strata: C=%d candidates is above the limit of %d per row (one workgroup sorts a row in LDS)", C,
-              kRsMaxCols);
-  GSS_REQUIRE(ld >= C, "rank_metrics_strata: ld=%lld is below C=%d", (long long)ld, C);
+  RankCuts cuts;
+  if (int rc = check_rank_args("rank_metrics_strata", R, C, ld, nk, ks, cuts)) return rc;
   GSS_REQUIRE(S >= 0, "rank_metrics_strata: S=%d strata must be >= 0", S);
-  GSS_REQUIRE(nk >= 0 && nk <= kRsMaxCuts, "rank_metrics_strata: nk=%d cut-offs is outside 0..%d", nk, kRsMaxCuts);
-  GSS_REQUIRE(nk == 0 || ks, "rank_metrics_strata: null argument");
-  StrataCuts cuts;
-  cuts.nk = nk;
-  for (int j = 0; j < kRsMaxCuts; ++j) cuts.k[j] = 1;
-  for (int j = 0; j < nk; ++j) {
-    GSS_REQUIRE(ks[j] >= 1, "rank_metrics_strata: cut-off %d is k=%d; a cut-off must be >= 1", j, ks[j]);
-    cuts.k[j] = ks[j];
-  }
   if (R == 0 || S == 0) return GSS_OK;
   GSS_REQUIRE(scores && pos_ptr && pos_col && str_ptr && sub_ptr && sub_col && auc && ap && (nk == 0 || hits) && s_pos && s_neg && n_pos && n_neg &&
                   workspace,
@@ -318,7 +213,7 @@ int gss_rank_metrics_strata(int32_t R, int32_t C, const double *scores, int64_t 
   hipStream_t st = as_stream(stream);
   const int32_t cpad = pow2_at_least(C);
   const size_t lds = (size_t)cpad * 8 + 2 * ((size_t)cpad / 8);
-  hipLaunchKernelGGL(rank_strata_kernel, dim3(R), dim3(kRsThreads), lds_request(rank_strata_kernel, lds), st, R, C, cpad, scores, ld, pos_ptr, pos_col,
+  hipLaunchKernelGGL(rank_strata_kernel, dim3(R), dim3(kRankThreads), lds_request(rank_strata_kernel, lds), st, R, C, cpad, scores, ld, pos_ptr, pos_col,
                      S, str_ptr, sub_ptr, sub_col, cuts, auc, ap, hits, s_pos, s_neg, n_pos, n_neg, reinterpret_cast<uint64_t *>(workspace),
                      (int64_t)(workspace_bytes / 8));
   GSS_LAUNCH_CHECK("rank_strata_kernel");

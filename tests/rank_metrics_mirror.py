@@ -2,7 +2,8 @@
 test_rank_metrics.py (CPU) and the GPU tests.  Scores compare as the kernel compares them (-0.0 folded into +0.0); a tie group is a
 maximal set of equal scores.
   auc   evaluate_fixture.mirror_aucs: the kernel's own integer counts and its one division.
-  ap    (1 / P) sum over the tie groups that hold a positive of pos_g TP_g / (TP_g + FP_g), in exact rationals, rounded once.
+  ap    (1 / P) sum over the tie groups that hold a positive of pos_g TP_g / (TP_g + FP_g), in exact rationals, rounded once (ap_exact);
+        and the same sum in the kernel's order of fp64 additions (ap_ordered), which fixes the bits the device writes.
   hits  at k' = min(k, C): the group that holds rank k' has `above` items strictly before it (A positive), g items, pos_g positives;
         slots = k' - above; hits = A + pos_g if slots == g, else fl(A + fl((pos_g slots) / g)) -- the two fp64 operations spelled out."""
 import math
@@ -40,6 +41,46 @@ def ap_exact(s, mask):
         common = common * n // math.gcd(common, n)
     num = sum(int(pos[g]) * int(tp[g]) * (common // n) for g, n in zip(hold, dens))
     return Fraction(num, common * P)
+
+
+AP_THREADS, AP_WAVE = 256, 64
+
+
+def ap_ordered(pos, neg, P):
+    """the kernel's average precision, addition by addition (csrc/rank_score.h, DESIGN.md section 9.8 "Order of summation"): pos [P] and
+    neg [N] are one class's scores each, sorted ascending with -0.0 folded into +0.0.  Sorted positive i has posL / posU positives and
+    negL negatives below / not above its score; the first positive of a tie group (i == posL) speaks for it with the term
+    float64(pos_g TP_g) / float64(TP_g + FP_g), pos_g = posU - posL, TP_g = P - posL, FP_g = N - negL.
+      1. thread t of 256 starts from +0.0 and adds the terms of i = P-1-t, P-1-t-256, ... in that order;
+      2. each wave of 64 runs the xor butterfly at offsets 32, 16, 8, 4, 2, 1: v = v + v[lane ^ o];
+      3. the four lane-0 values are added in wave order from 0.0, and the sum is divided by P.
+    The operands are exact integers below 2^53 and every operation is one IEEE rounding, so numpy gives the kernel's bits."""
+    pos, neg = np.asarray(pos, np.float64), np.asarray(neg, np.float64)
+    assert len(pos) == P >= 1 and np.all(pos[1:] >= pos[:-1]) and np.all(neg[1:] >= neg[:-1])
+    posL, posU = np.searchsorted(pos, pos, "left").astype(np.int64), np.searchsorted(pos, pos, "right").astype(np.int64)
+    negL = np.searchsorted(neg, pos, "left").astype(np.int64)
+    tp, fp = P - posL, len(neg) - negL
+    term = ((posU - posL) * tp).astype(np.float64) / (tp + fp).astype(np.float64)
+    first = posL == np.arange(P)
+    acc = np.zeros(AP_THREADS, np.float64)
+    for top in range(P - 1, -1, -AP_THREADS):                # one trip of the threads' loop: thread t holds i = top - t
+        i = top - np.arange(AP_THREADS)
+        live = i >= 0
+        i = np.where(live, i, 0)
+        acc = np.where(live & first[i], acc + term[i], acc)
+    total = 0.0
+    for w in range(AP_THREADS // AP_WAVE):
+        v = acc[w * AP_WAVE:(w + 1) * AP_WAVE].copy()
+        for o in (32, 16, 8, 4, 2, 1):
+            v = v + v[np.arange(AP_WAVE) ^ o]
+        total = total + float(v[0])
+    return float(np.float64(total) / np.float64(P))
+
+
+def ap_ordered_row(s, mask):
+    """ap_ordered of one row: scores [C] and the positives' mask"""
+    s, mask = np.asarray(s, np.float64) + 0.0, np.asarray(mask, bool)
+    return ap_ordered(np.sort(s[mask]), np.sort(s[~mask]), int(mask.sum()))
 
 
 def hits_parts(s, mask, k):

@@ -1,6 +1,7 @@
 """GPU: csrc/rank_metrics.hip (gss_rank_metrics_rows) against its host mirror (rank_metrics_mirror.py), gss_auc_rows and sklearn.
-For every case: auc bit-equal to gss_auc_rows on the same inputs; hits bit-equal to the mirror; ap within (P + 3) 2^-53 relative of the
-mirror's exactly rounded value (any order of summing P positive, correctly rounded terms, plus the final division); ap within 1e-12
+For every case: auc bit-equal to gss_auc_rows on the same inputs; hits bit-equal to the mirror; ap bit-equal to the mirror's statement of
+the kernel's order of additions (M.ap_ordered) and within (P + 3) 2^-53 relative of the mirror's exactly rounded value (any order of
+summing P positive, correctly rounded terms, plus the final division); ap within 1e-12
 absolute of sklearn.metrics.average_precision_score where C <= 1,661 (test_gpu_auc.py's tolerance for the same library; the derived
 4 C 2^-53 is 7.4e-13 at that width).  Then order independence, one-class rows, nk = 0 and the refusals by name."""
 import os
@@ -72,7 +73,7 @@ def seeded_rows(rng, R, Cn, max_pos):
 
 
 def check(scores, rows, ks):
-    """the four comparisons of the module docstring -> the device outputs"""
+    """the comparisons of the module docstring -> the device outputs"""
     scores = np.asarray(scores, np.float64)
     rc, auc, ap, hits, n_pos, n_neg, msg = device_metrics(scores, rows, ks)
     assert rc == 0, msg
@@ -89,6 +90,10 @@ def check(scores, rows, ks):
         bound = (P + 3) * 2.0 ** -53 * m_ap[r]
         worst = max(worst, abs(ap[r] - m_ap[r]) / bound)
         assert abs(ap[r] - m_ap[r]) <= bound, (r, P, ap[r], m_ap[r])
+        mask = np.zeros(C, bool)
+        mask[cols] = True
+        ordered = M.ap_ordered_row(scores[r], mask)
+        assert _bits(ap[r:r + 1])[0] == _bits([ordered])[0], (r, P, ap[r], ordered)
         if C <= 1661:
             y = np.zeros(C, int)
             y[cols] = 1

@@ -1,5 +1,6 @@
 """GPU: csrc/rank_strata.hip (gss_rank_metrics_strata) against gss_rank_metrics_rows on each stratum gathered into a row of its own, and
-against the host mirror (rank_strata_mirror.py).  For every stratum: auc, hits and the counts bit-equal to the mirror; ap within
+against the host mirror (rank_strata_mirror.py).  For every stratum: auc, hits and the counts bit-equal to the mirror; ap bit-equal to
+the mirror's statement of the kernel's order of additions (M.ap_ordered on the gathered sub-problem) and within
 (|Q| + 3) 2^-53 relative of the mirror's exactly rounded value (test_gpu_rank_metrics.py's derived bound: any order of summing |Q| positive,
 correctly rounded terms, plus the final division); and for up to 24 strata per test every output word bit-equal to what
 gss_rank_metrics_rows writes for the gathered sub-problem (R = 1).  A stratum with all of its row's positives has the row's words.  Then
@@ -85,6 +86,11 @@ def check(scores, rows, strata, ks, gather=24, **kw):
         print(f"stratum {s}: |Q| = {s_pos[s]}, N = {s_neg[s]}, ap = {ap[s]!r}, mirror {m_ap[s]!r}, bound {bound:.3e}")
         worst = max(worst, abs(ap[s] - m_ap[s]) / bound)
         assert abs(ap[s] - m_ap[s]) <= bound, (s, s_pos[s], ap[s], m_ap[s])
+        x, cols = RS.gathered(scores[owner[s]], rows[owner[s]], qc[qp[s]:qp[s + 1]])
+        mask = np.zeros(len(x), bool)
+        mask[cols] = True
+        ordered = M.ap_ordered_row(x, mask)
+        assert _bits(ap[s:s + 1])[0] == _bits([ordered])[0], (s, s_pos[s], ap[s], ordered)
     print(f"C={scores.shape[1]}: worst |ap - mirror| / ((|Q| + 3) 2^-53 ap) = {worst:.3f}")
     # the gathered sub-problems through the rows' kernel: the ranked strata, spread evenly when there are more than `gather`
     ranked = [s for s in range(len(owner)) if s_pos[s] > 0 and s_neg[s] > 0]

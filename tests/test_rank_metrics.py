@@ -1,5 +1,6 @@
 """CPU: the host mirror of csrc/rank_metrics.hip (rank_metrics_mirror.py) against sklearn's average precision, against a stable argsort
-and against every tie-breaking order of a small group; the metric-name parser; evaluate_auc.py --metrics end to end on the
+and against every tie-breaking order of a small group; the mirror's AP in the kernel's order of additions against its exact value;
+the metric-name parser; evaluate_auc.py --metrics end to end on the
 evaluate_msi_small fixture with the mirror in place of the device; and the trainer's --eval-metric / --eval-stat checks that need no GPU.
 The device side is in test_gpu_rank_metrics.py and test_gpu_evaluate_metrics.py."""
 import io
@@ -42,6 +43,53 @@ def test_mirror_ap_against_sklearn_on_heavily_tied_rows():
         worst = max(worst, abs(got - want) / (4 * C * 2.0 ** -53))
         assert abs(got - want) <= 4 * C * 2.0 ** -53, (C, got, want)
     print(f"worst |mirror - sklearn| / bound: {worst:.3f}")
+
+
+def _ordered_against_exact(s, mask):
+    """-> |ap_ordered - ap_exact| over the bound (P + 3) 2^-53 ap: P - 1 additions of positive, correctly rounded terms in any order (each
+    term one rounding, each addition one), and the final division"""
+    P = int(mask.sum())
+    exact = M.ap_exact(s, mask)
+    got = M.ap_ordered_row(s, mask)
+    bound = (P + 3) * 2.0 ** -53 * float(exact)
+    assert abs(Fraction(got) - exact) <= Fraction(bound), (P, got, float(exact))
+    return float(abs(Fraction(got) - exact)) / bound
+
+
+@pytest.mark.parametrize("P", [1, 2, 63, 64, 65, 255, 256, 257, 513])
+def test_mirror_ap_in_the_kernels_order_against_the_exact_value(P):
+    """the ordered statement of AP (thread-serial, wave butterfly, four waves) across the wave's and the workgroup's thread counts, on
+    heavily tied rows with both signed zeros and on a row without ties"""
+    rng = np.random.RandomState(200 + P)
+    worst = 0.0
+    for levels in (1, 3, 12, 0):
+        C = P + rng.randint(1, 2 * P + 40)
+        s = rng.randint(-levels, levels + 1, C) * 0.5 if levels else rng.permutation(C) * 0.25 - 7.0
+        zero = s == 0
+        s[zero] = np.where(rng.rand(int(zero.sum())) < 0.5, -0.0, 0.0)
+        mask = np.zeros(C, bool)
+        mask[rng.choice(C, P, replace=False)] = True
+        worst = max(worst, _ordered_against_exact(s, mask))
+    print(f"P={P}: worst |ordered - exact| / ((P + 3) 2^-53 ap) = {worst:.3f}")
+
+
+def test_mirror_ap_in_the_kernels_order_at_the_column_limit_with_mostly_positives():
+    rng = np.random.RandomState(3)
+    s = np.round(rng.randn(16384), 2)
+    s[s == 0] = np.where(rng.rand(int((s == 0).sum())) < 0.5, -0.0, 0.0)
+    assert np.any(np.signbit(s) & (s == 0)) and np.any(~np.signbit(s) & (s == 0))
+    mask = np.zeros(16384, bool)
+    mask[rng.choice(16384, 12000, replace=False)] = True
+    print(f"C=16384, P=12000: |ordered - exact| / ((P + 3) 2^-53 ap) = {_ordered_against_exact(s, mask):.3f}")
+
+
+def test_mirror_ap_in_the_kernels_order_by_hand():
+    """P = 2 over three tie groups: thread 0 holds the upper positive, thread 1 the lower; the butterfly's last step adds lane 1 to lane 0"""
+    s = np.array([1.0, 0.5, 0.25, 0.25])
+    mask = np.array([True, False, True, False])
+    assert M.ap_ordered_row(s, mask) == (1.0 / 1.0 + 2.0 / 4.0) / 2.0 == float(M.ap_exact(s, mask))
+    tied = np.array([0.0, -0.0, 0.0, -1.0])                              # one group of two positives and a negative: one term, 2 * 2 / 3
+    assert M.ap_ordered_row(tied, np.array([True, True, False, False])) == (4.0 / 3.0) / 2.0
 
 
 def test_mirror_hits_on_tie_free_rows_is_the_argsort_count():

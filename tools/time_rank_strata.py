@@ -133,7 +133,7 @@ def main():
         ms["strata"].append(timed(strata))
         ms["rows"].append(timed(rows))
     assert torch.equal(sn_pos, r_pos) and torch.equal(sn_neg, r_neg) and not bool(torch.isnan(s_auc).any())
-    out = {"device": torch.cuda.get_device_name(0), "source_hash": {k: hashes[k] for k in ("rank_strata.hip", "rank_metrics.hip", "rank_keys.h", "*")},
+    out = {"device": torch.cuda.get_device_name(0), "source_hash": {k: hashes[k] for k in ("rank_strata.hip", "rank_metrics.hip", "rank_score.h", "rank_keys.h", "*")},
            "shape": {"rows": R, "columns": C, "positives": int(len(pos_col)), "max_positives_per_row": int(np.diff(pos_ptr).max()), "strata": S,
                      "strata_from_the_class_assignment": int(given), "stratum_positives": int(n_sub),
                      "max_strata_per_row": int(np.diff(str_ptr).max())},
