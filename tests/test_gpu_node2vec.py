@@ -11,6 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import node2vec_mirror as M  # noqa: E402
 from conftest import record_measured  # noqa: E402
+from node2vec_cases import sinks_graph  # noqa: E402
 
 PQ = [(1.0, 1.0), (0.25, 0.25), (4.0, 0.5)]
 TOY_SIF = "A 1 B\nA 1 C\nA 1 D\nA 1 E\nA 1 F\nA 1 G\nA 1 H\nB 1 C\nB 1 D\nB 1 I\nB 1 J\nC 1 K\nD 1 E\nD 1 I\nE 1 F\n"
@@ -27,22 +28,6 @@ def toy_graph(tmp_path):
     f.write_text(TOY_SIF)
     src, dst, w, names = read_edgelist(str(f))
     return sp.csr_matrix((w, (src, dst)), shape=(len(names), len(names)))
-
-
-def sinks_graph():
-    """random weighted digraph with sink rows (no out-edges), self-loops and isolated nodes"""
-    import scipy.sparse as sp
-    rng = np.random.RandomState(7)
-    n = 300
-    a = sp.random(n, n, density=0.03, random_state=rng, format="lil")
-    for i in range(0, n, 17):
-        a[i, i] = 0.5
-    for i in range(3, n, 23):
-        a[i, :] = 0
-    a = a.tocsr()
-    a.eliminate_zeros()
-    a.data = rng.gamma(2.0, 1.0, a.nnz) + 1e-3
-    return a
 
 
 @pytest.mark.gpu
