@@ -47,6 +47,8 @@ struct Knobs {
   int proj_split = -1;       // one-GPU plans: a layer's forward projection as two launches, the AX half on the plan's side stream beside the layer's
                              // second SpMM (plan.hip plan_forward_impl): -1 = where dense_fwd_split_auto says it pays (nowhere: it measured
                              // 31 us per step SLOWER at config 2), 0 = never, 1 = wherever dense_fwd_split_available.  Same bits either way
+  int prox_batch_pairs = 0;  // gss_prox_score: pairs per trip through its score / stats launches: 0 = as many as the 256 MiB scratch holds, > 0 = at most
+                             // this many (lets a test of a few pairs take several trips).  Same bits either way
 };
 template <typename F>
 inline size_t lds_request(F kernel, size_t need) {

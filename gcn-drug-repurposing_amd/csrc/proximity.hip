@@ -407,6 +407,7 @@ int gss_prox_score(gss_prox *p, const gss_prox_sets *from, const gss_prox_sets *
   const size_t per_pair = (size_t)kMeasures * n_samples * sizeof(double);
   int64_t batch = std::max<int64_t>(1, (int64_t)(kScratchBytes / per_pair));
   batch = std::min(batch, n_pairs);
+  if (K().prox_batch_pairs > 0) batch = std::min<int64_t>(batch, K().prox_batch_pairs);   // knob: a few pairs take several trips
   const size_t want = (size_t)batch * per_pair;
   if (p->vals.bytes < want)
     if (int rc = p->vals.alloc("prox_score", want)) return rc;

@@ -48,7 +48,7 @@ const char *gss_source_hash(const char *file);
  * plan's snapshot, so that one plan -- the same buffers at the same addresses --
  * can be timed under alternating settings; knobs that size a workspace or steer the plan's bookkeeping are refused (GSS_EINVAL).
  * Not thread-safe against gss_debug_set_option on another thread.
- * One name is a PLAN OPTION and exists here only (it is none of the 19 process-wide knobs): "l1_ahead" = -1 (default: automatic) / 0 / 1.
+ * One name is a PLAN OPTION and exists here only (it is none of the 20 process-wide knobs): "l1_ahead" = -1 (default: automatic) / 0 / 1.
  * A one-GPU plan with two or more layers and neither cache_layer1 nor pipeline_layer1 computes layer 1's two SpMMs -- functions of
  * A_hat and X alone -- one pass AHEAD: every full forward pass (gss_plan_step, gss_plan_forward) carries them for the next pass as the
  * second halves of layer 2's two SpMM launches (gss_spmm_fwd_pair), into the layer-1 buffers themselves, and a pass that finds them there
@@ -369,13 +369,17 @@ int gss_sgns_epoch(const gss_sgns_desc *desc, int32_t epoch, float *syn0, float 
 /* ---- network proximity of drug targets to disease genes: Guney et al. 2016 (method/test_proximity.py, toolbox wrappers.calculate_proximity)
  * gss_prox_create: all-pairs hop distances of an undirected graph (symmetric CSR, no self loops, rowptr/col device) into a uint8 [n][n]
  * matrix owned by the handle (255 = unreachable).  Refuses n * n > max_bytes and a graph with a node 255 or more hops from another
- * (GSS_EINVAL, by name).  Synchronises the stream.  gss_prox_distances: the device matrix; gss_prox_diameter: the largest finite hop count.
+ * (GSS_EINVAL, by name).  Synchronises the stream.  gss_prox_distances: the device matrix; gss_prox_diameter: the largest finite hop count
+ * (the diameter is taken over finite distances only: isolated nodes and further components, 255 in the matrix, do not enter it; a
+ * path of 255 nodes -- 254 hops -- is accepted, one of 256 nodes refused).
  * Sets are LCC node indices.  A set table holds n_sets x n_samples compacted sets of at most max_size nodes, ascending: nodes
  * [n_sets][n_samples][max_size], sizes [n_sets][n_samples].  Sample 0 is the set itself, sample r >= 1 the random set k = r - 1.
  * gss_prox_random_sets: from the sets in CSR form (set_ptr [n_sets + 1], set_nodes ascending unique) and the degree bins (node_bin [n],
  * bin_ptr, bin_nodes), writes the table with n_samples = n_random + 1.  Random set k walks the members v_i in order: draw a node of v_i's bin,
  * redraw (at most 20 times) while it is already in the set, add it if it is not; draw a of member i of set s is
  * bin_nodes[lo + (u32 * bin size >> 32)], u32 keyed by (seed, 7 + side, s, k, i * 32 + a) in counter_rng.h.  side: 0 from, 1 to.
+ * A member whose 21 draws (a = 0..20) are all taken already is dropped: that random set is one node smaller than the set, and
+ * sizes says so.  Entries of a row past its size are left as the caller had them.  With n_random = 0 only the sets themselves are written.
  * Synchronises the stream (validates the member indices).
  * gss_prox_set_stats: per (set, sample): inner = mean over members of the hop count to the closest other member (0 for fewer than 2);
  * with centres / n_centres: every member whose summed distance to the set is minimal, ascending (centres laid out like nodes).
@@ -383,7 +387,9 @@ int gss_sgns_epoch(const gss_sgns_desc *desc, int32_t epoch, float *syn0, float 
  * sample r, the five measures of (from sample r, to sample r): closest = mean_t min_s D, shortest = mean D, kernel = -mean_t
  * ln(sum_s e^-(D+1) / |S|), center = mean D(t, c) over t and the tied centres, separation = (sum_t min_s D + sum_s min_t D) / (|T| + |S|)
  * - (inner_from + inner_to) / 2.  out [n_pairs][5 measures][5] = d (sample 0), mean and population sd over samples 1.., z = (d - m) / sd
- * (0 when sd = 0), pval = Phi(z), all fp64 in a fixed order (bitwise reproducible); NaN where a set is empty.  measures: bit mask
+ * (0 when sd = 0, then pval = 0.5), pval = Phi(z), all fp64 in a fixed order (bitwise reproducible): m is summed in sample order
+ * r = 1, 2, ... and divided once, sd is the root of the mean squared deviation from that m, summed in the same order; NaN where a set
+ * is empty.  Pairs are scored in batches of as many as a 256 MiB scratch holds ("prox_batch_pairs" caps the batch; same bits).  measures: bit mask
  * (1 closest, 2 shortest, 4 kernel, 8 center, 16 separation); closest and shortest always come out, unmasked others are 0.  The
  * to-side max_size must be <= 4096. */
 typedef struct gss_prox gss_prox;
@@ -919,7 +925,7 @@ enum {
 };
 int gss_plan_profile(gss_plan *p, int enable);
 int gss_plan_profile_read(gss_plan *p, double *ms_out, int64_t *count_out, void *stream);
-/* tuning/debug knobs (A/B runs inside one process; 19 of them -- round 6 removed the access-shape variants whose sweeps said "default holds" in
+/* tuning/debug knobs (A/B runs inside one process; 20 of them -- round 6 removed the access-shape variants whose sweeps said "default holds" in
  * two or more rounds from the kernels; "spmm_seg_edges" left when "proj_split" came: the segment length is 32 entries): "spmm_list_blocks" = workgroups from which a ROW-FILTERED balanced SpMM (the lazy step's
  * top-layer products, the batch-sparse backward hop) lists the workgroups that hold a passing row and walks the list with persistent
  * workgroups instead of dispatching every workgroup (default 2048; 0 = never; same bits); "spmm_variant" = 1 (whole-row gather, wave per row) or
@@ -933,7 +939,8 @@ int gss_plan_profile_read(gss_plan *p, double *ms_out, int64_t *count_out, void 
  * stream beside the layer's second SpMM and finishes it in a second launch (widths 64 / 128 / 256 below the weight-stationary row count; same bits);
  * "wgrad_wgs", "loss_wgs" = workgroups of a full-size weight-gradient launch / the loss sweep (default 256 = one per CU; set
  * before plans are created); "sparse_bits_rows" = operand rows from which a plan keeps the bitmaps of the sparsity-aware backward hops
- * (default 100000); "ppr_fused" = 1 (default) / 0 (separate update pass of the diffusion profiles);
+ * (default 100000); "ppr_fused" = 1 (default) / 0 (separate update pass of the diffusion profiles); "prox_batch_pairs" = 0 (default: as many
+ * pairs per trip of gss_prox_score as its 256 MiB scratch holds) or a cap on that count (same bits; for tests of the batch loop);
  * "lazy_halo" = -1 (default: graphs of >= 262,144 nodes, but never over RCCL, where it stays opt-in) / 0 / 1: sharded plans fetch subsets of the
  * boundary rows where a hop reads a subset (gss_plan_lazy_halo_rows), "lazy_halo_u" = -1 / 0 / 1 the same for u in the second backward hop (see gss_plan_lazy_halo_rows); "halo_recompute" = -1 (default: on) / 0 / 1: sharded plans recompute layer 2's boundary input rows from layer 1's constant AX / AM (fetched once)
  * instead of exchanging them every step (same bits); "loss_dgrad" = -1 (default: on shards only) / 0 / 1: the

@@ -6,6 +6,13 @@
   * measures(): the five measures of one (T, S) pair from a hop-distance lookup, with the tied centres and the inner closest means;
   * stats(): mean / population sd / z / pval over the random samples, as the toolbox computes them (numpy.mean, numpy.std).
 Distances come from scipy's BFS (bfs_rows), only for the rows a test needs.
+
+The kernels one by one, for tests/test_gpu_proximity_ops.py (inputs: tests/proximity_cases.py):
+  * random_table(): gss_prox_random_sets' whole table, draw by draw as the kernel walks it (a member whose 21 draws are all taken is dropped);
+  * set_stats() / stats_table(): what set_stats_kernel writes -- inner, the tied centres ascending, n_centres -- on inner_closest and centres;
+  * pair_values() / score_values(): score_kernel's five values per (pair, sample) from the set statistics it is handed;
+  * stats_sequential() / score_out(): stats_kernel -- the mean summed in sample order, the population sd from it -- and the batch loop;
+  * ABLATIONS: named wrong rules each of these takes as `ablate`; tests/test_proximity_mirror.py shows that every one changes an output.
 """
 from __future__ import annotations
 
@@ -148,6 +155,156 @@ def proximity(dist, T, S, node_bin, bin_list, seed, i, j, n_random, which=MEASUR
         for m, v in measures(dist, rt, rs, which).items():
             rnd[m].append(v)
     return {m: (d[m],) + stats(d[m], rnd[m]) for m in which}
+
+
+# ---- the kernels one by one, with their wrong rules (tests/proximity_cases.py, test_proximity_mirror.py, test_gpu_proximity_ops.py) ----------
+#
+# A set table is a list (per set) of lists (per sample) of ascending int64 node arrays; sample 0 is the set itself.  `ablate` names ONE
+# wrong rule of ABLATIONS, applied where it belongs; None is the contract.
+
+ABLATIONS = {
+    "first_centre": "set stats: only the first of the tied centres",
+    "inner_self": "set stats: the closest member of a member may be the member itself",
+    "inner_single": "set stats: inner of a one-member set is the minimum over no member (the initial 255), not 0",
+    "stats_first64": "set stats: members past the first 64 dropped",
+    "colmin_first64": "score: separation's column minima summed over the first 64 members of S only",
+    "kernel_max_size": "score: the kernel measure's inner mean divided by the table's max_size, not |S|",
+    "redraws_19": "random sets: 19 redraws",
+    "redraws_21": "random sets: 21 redraws",
+    "add_taken": "random sets: a draw still taken after the last redraw is added anyway",
+    "unsorted": "random sets: the set left in the order of its draws",
+    "pair_sample0": "score: from-sample r paired with to-sample 0",
+    "sample_sd": "stats: the sample standard deviation (k - 1)",
+    "drop_p0": "score: the batch offset p0 dropped from the output index",
+}
+
+
+def random_table(sets, node_bin, bin_list, seed, side, n_random, ablate=None):
+    """the set table of gss_prox_random_sets, draw by draw as random_sets_kernel walks it (random_sets above is its vectorised twin)"""
+    redraws = {"redraws_19": 19, "redraws_21": 21}.get(ablate, REDRAWS)
+    tag = TAG_FROM if side == 0 else TAG_TO
+    lo = np.array([0] + [len(b) for b in bin_list]).cumsum()
+    flat = np.concatenate(bin_list)
+    table = []
+    for s, members in enumerate(sets):
+        members = np.asarray(members, np.int64)
+        rows = [members.copy()]
+        if len(members) and n_random:
+            k = np.arange(n_random, dtype=np.uint64)[:, None, None]
+            c = (np.arange(len(members), dtype=np.uint64) * np.uint64(32))[None, :, None] + np.arange(redraws + 1, dtype=np.uint64)[None, None, :]
+            keys = rng_key(seed, tag, s, k, c)
+            bm = node_bin[members]
+            size = (lo[bm + 1] - lo[bm]).astype(np.uint64)[None, :, None]
+            picks = flat[lo[bm][None, :, None] + ((keys >> np.uint64(32)) * size >> np.uint64(32)).astype(np.int64)].tolist()
+        for kk in range(n_random):
+            chosen = []
+            for row in (picks[kk] if len(members) else []):
+                pick, a = row[0], 0
+                while a < redraws and pick in chosen:
+                    a += 1
+                    pick = row[a]
+                if pick not in chosen or ablate == "add_taken":
+                    chosen.append(pick)
+            rows.append(np.array(chosen if ablate == "unsorted" else sorted(chosen), np.int64))
+        table.append(rows)
+    return table
+
+
+def matrix_dist(D):
+    """dist(rows, cols) over a full distance matrix"""
+    return lambda T, S: D[np.ix_(np.asarray(T, np.int64), np.asarray(S, np.int64))]
+
+
+def set_stats(dist, S, ablate=None):
+    """what set_stats_kernel writes for one set -> (inner, the tied centres ascending, n_centres)"""
+    S = np.asarray(S, np.int64)
+    if ablate == "stats_first64":
+        S = S[:64]
+    if len(S) == 0:
+        return 0.0, np.zeros(0, np.int64), 0
+    Dss = dist(S, S)
+    if ablate == "inner_self" and len(S) > 1:
+        inner = float(Dss.astype(np.int64).min(axis=1).sum()) / len(S)
+    elif ablate == "inner_single" and len(S) == 1:
+        inner = 255.0
+    else:
+        inner = inner_closest(Dss)
+    c = centres(S, Dss)
+    if ablate == "first_centre":
+        c = c[:1]
+    return inner, c, len(c)
+
+
+def stats_table(dist, table, ablate=None):
+    return [[set_stats(dist, x, ablate) for x in rows] for rows in table]
+
+
+def pair_values(dist, T, S, stat_t, stat_s, which=MEASURES, ablate=None, max_size=None):
+    """the five values score_kernel writes for one (T, S), from the set statistics it is handed; 0 for a measure not in `which`"""
+    B = dist(T, S).astype(np.int64)
+    out = dict.fromkeys(MEASURES, 0.0)
+    out["closest"] = float(B.min(axis=1).sum()) / len(T)
+    out["shortest"] = float(B.sum()) / (len(T) * len(S))
+    if "kernel" in which:
+        e = np.exp(-(B + 1.0))
+        out["kernel"] = -float(np.sum(np.log(e.sum(axis=1) / (max_size if ablate == "kernel_max_size" else len(S))))) / len(T)
+    if "center" in which:
+        c = stat_s[1]
+        out["center"] = float(dist(T, c).astype(np.int64).sum()) / (len(T) * len(c))
+    if "separation" in which:
+        cols = B[:, :64] if ablate == "colmin_first64" else B
+        d_ab = float(B.min(axis=1).sum() + cols.min(axis=0).sum()) / (len(T) + len(S))
+        out["separation"] = d_ab - (stat_t[0] + stat_s[0]) / 2.0
+    return out
+
+
+def score_values(dist, ftab, ttab, fstat, tstat, pairs, which=MEASURES, ablate=None, max_size=None):
+    """vals [n_pairs, 5, n_samples]: sample r of the from set against sample r of the to set; NaN where either is empty"""
+    R = len(ftab[0])
+    vals = np.zeros((len(pairs), len(MEASURES), R))
+    for q, (i, j) in enumerate(pairs):
+        for r in range(R):
+            rs = 0 if ablate == "pair_sample0" else r
+            T, S = ftab[i][r], ttab[j][rs]
+            if len(T) == 0 or len(S) == 0:
+                vals[q, :, r] = np.nan
+                continue
+            v = pair_values(dist, T, S, fstat[i][r], tstat[j][rs], which, ablate, max_size)
+            vals[q, :, r] = [v[m] for m in MEASURES]
+    return vals
+
+
+def stats_sequential(vals, ablate=None):
+    """vals [..., n_samples] -> [..., 5] = d, m, s, z, pval as stats_kernel computes them: the mean summed in sample order and divided
+    once, the population sd from that mean in the same order; all NaN where d is"""
+    vals = np.asarray(vals, np.float64)
+    d, k = vals[..., 0], vals.shape[-1] - 1
+    total = np.zeros(d.shape)
+    for i in range(1, k + 1):
+        total = total + vals[..., i]
+    m = total / k
+    ss = np.zeros(d.shape)
+    for i in range(1, k + 1):
+        ss = ss + (vals[..., i] - m) * (vals[..., i] - m)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        s = np.sqrt(ss / (k - 1 if ablate == "sample_sd" else k))
+        z = np.where(s == 0, 0.0, (d - m) / np.where(s == 0, 1.0, s))
+    p = 0.5 * np.vectorize(math.erfc, otypes=[np.float64])(-z / math.sqrt(2.0))
+    out = np.stack([d, m, s, z, p], axis=-1)
+    out[np.isnan(d)] = np.nan
+    return out
+
+
+def score_out(vals, batch=None, ablate=None, fill=np.nan):
+    """out [n_pairs, 5, 5] of gss_prox_score run in batches of `batch` pairs; rows no batch writes keep `fill`"""
+    P = len(vals)
+    batch = P if not batch else min(batch, P)
+    out = np.full((P, len(MEASURES), 5), fill, np.float64)
+    for p0 in range(0, P, batch):
+        nb = min(batch, P - p0)
+        at = 0 if ablate == "drop_p0" else p0
+        out[at:at + nb] = stats_sequential(vals[p0:p0 + nb], ablate)
+    return out
 
 
 def bfs_rows(rowptr, col, sources):

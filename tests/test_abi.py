@@ -139,8 +139,9 @@ def test_build_recovers_from_a_stale_library(tmp_path, monkeypatch):
 
 
 def test_removed_knobs_are_refused_by_name(lib):
-    """round 6 pruned the access-shape knobs: the removed names are errors, not silent no-ops, and 19 remain --
-    one `struct Knobs` field per name gss_debug_set_option accepts"""
+    """round 6 pruned the access-shape knobs: the removed names are errors, not silent no-ops, and 19 remained --
+    20 with "prox_batch_pairs" (the pair batch of gss_prox_score, for tests/test_gpu_proximity_ops.py): one `struct Knobs` field per name
+    gss_debug_set_option accepts"""
     for name in ("gemm_ws_mode", "gemm_ws_stagger", "gemm_ws_wgs", "wgrad_variant", "spmm_fly", "gemm_small_nt", "gemm_nt_cap",
                  "gemm_lines", "gemm_hoist", "gemm_rows_split", "wgrad_deep", "spmm_pair", "xcd_remap"):
         assert lib.gss_debug_set_option(name.encode(), 1) != 0, name
@@ -150,7 +151,10 @@ def test_removed_knobs_are_refused_by_name(lib):
     fields = re.findall(r"^  int \w+ = ", body, flags=re.M)
     api = open(os.path.join(ROOT, "gcn-drug-repurposing_amd", "csrc", "api.hip")).read()
     names = re.findall(r'strcmp\(name, "(\w+)"\) == 0', api)
-    assert len(set(names)) == len(names) == len(fields) == 19, (len(names), len(fields))
+    assert len(set(names)) == len(names) == len(fields) == 20, (len(names), len(fields))
+    assert "prox_batch_pairs" in names
+    assert lib.gss_debug_set_option(b"prox_batch_pairs", -1) != 0 and "prox_batch_pairs must be >= 0" in lib.gss_last_error().decode()
+    assert lib.gss_debug_set_option(b"prox_batch_pairs", 0) == 0
 
 
 def test_stamp_instrumentation_is_not_exported(lib):
