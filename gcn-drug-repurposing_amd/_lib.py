@@ -194,6 +194,8 @@ SIGNATURES = {
     # for tests: the row-sparse SpMM modes and their bitmap builders (tests/test_gpu_sparse_ops.py)
     "gss_spmm_bwd1_sparse_ex": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _P]),
     "gss_spmm_bwd2_sparse_res": (C.c_int, [_P, _I32, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _I32, _P]),
+    "gss_spmm_bwd1_ex": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gss_spmm_bwd2_ex": (C.c_int, [_P, _I32, _P, _P, _P, _F, _P, _P, _P, _P, _I32, _P]),
     "gss_spmm_filtered": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gss_mark_rows_and_neighbours": (C.c_int, [_P, _P, _I32, _P, _P]),
     "gss_spmm_fwd_pair": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P]),

@@ -1404,6 +1404,17 @@ int gss_spmm_filtered(const gss_csr *a, int32_t d, const float *x, float *y, con
   GSS_REQUIRE(a && x && y, "gss_spmm_filtered: null operand");
   return spmm_fwd(a, d, x, y, h, m, stream, row_pos, row_bits, y_in, gather_bits);
 }
+// the dense backward hops with the arguments only a sharded plan passes (tests/test_gpu_dense_hops.py): include/gssgcn.h
+int gss_spmm_bwd1_ex(const gss_csr *at, int32_t d, const float *g_am, const float *g_ax, const float *x_in, const float *ax,
+                     float *u, float *t, const float *y_in, void *stream) {
+  GSS_REQUIRE(at, "gss_spmm_bwd1_ex: null handle");
+  return spmm_bwd1(at, d, g_am, g_ax, x_in, ax, u, t, stream, y_in);
+}
+int gss_spmm_bwd2_ex(const gss_csr *at, int32_t d, const float *u, const float *t, const float *p, float c, const float *res,
+                     float *dp, float *gx_out, const float *y_in, int32_t own_row_limit, void *stream) {
+  GSS_REQUIRE(at, "gss_spmm_bwd2_ex: null handle");
+  return spmm_bwd2(at, d, u, t, p, c, res, dp, gx_out, stream, y_in, own_row_limit);
+}
 // two forward products over one matrix (tests/test_gpu_spmm_pair.py; what the plan's layer-1-ahead launches call): include/gssgcn.h
 int gss_spmm_fwd_pair(const gss_csr *a, int32_t d, const float *x0, float *y0, const float *h0, float *m0, const float *x1, float *y1,
                       const float *h1, float *m1, const int32_t *prep_idx, int32_t prep_b, const int32_t *prep_node_map, int32_t *prep_rloc,

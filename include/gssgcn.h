@@ -971,6 +971,11 @@ int gss_memcpy_d2d(void *dst, const void *src, size_t bytes, void *stream);
  *     nzbits (nullable): a clear bit c says rows c of u AND of t are zero (the neighbour is skipped, t's row is not read).  y_in
  *     (nullable): [n_rows][d] partial sums of a first pass, added before the epilogue.  pos_row_limit > 0: t, pos_row and the residual
  *     exist for output rows below it only; rows behind it get dp = c * (A u) (.) elu'(p).
+ *   gss_spmm_bwd1_ex / gss_spmm_bwd2_ex (tests/test_gpu_dense_hops.py): gss_spmm_bwd1 / gss_spmm_bwd2 with the arguments that only a
+ *     sharded plan's overlapped hops pass.  y_in (nullable): [n_rows][d] partial sums of a first pass, added before the epilogue; it may
+ *     be the buffer the pass writes: t for bwd1, dp for bwd2.  own_row_limit > 0: t and res exist for output rows below it only; rows
+ *     behind it get gx = A u and dp = c * gx (.) elu'(p).  Either argument needs the balanced SpMM; without them the row-per-wave
+ *     variant runs too.
  *   gss_spmm_filtered: gss_spmm with row filters.  row_pos (plain product only): rows with row_pos[r] < 0 are not computed and not
  *     written; row_bits: the same by bitmap; y_in as above; gather_bits (plain product only): columns whose bit is clear are skipped.
  *   gss_mark_rows_and_neighbours: bits |= the listed rows and every column of their entries (negative list entries skipped).
@@ -983,6 +988,10 @@ int gss_spmm_bwd1_sparse_ex(const gss_csr *at, int32_t d, const float *g_am_b, c
 int gss_spmm_bwd2_sparse_res(const gss_csr *at, int32_t d, const float *u, const float *t, const float *p, float c, const float *res_b,
                              const int32_t *pos_row, float *dp, float *gx_out, const uint32_t *nzbits, const float *y_in,
                              int32_t pos_row_limit, void *stream);
+int gss_spmm_bwd1_ex(const gss_csr *at, int32_t d, const float *g_am, const float *g_ax, const float *x_in, const float *ax,
+                     float *u, float *t, const float *y_in, void *stream);
+int gss_spmm_bwd2_ex(const gss_csr *at, int32_t d, const float *u, const float *t, const float *p, float c, const float *res,
+                     float *dp, float *gx_out, const float *y_in, int32_t own_row_limit, void *stream);
 int gss_spmm_filtered(const gss_csr *a, int32_t d, const float *x, float *y, const float *h, float *m, const int32_t *row_pos,
                       const uint32_t *row_bits, const float *y_in, const uint32_t *gather_bits, void *stream);
 int gss_mark_rows_and_neighbours(const gss_csr *a, const int32_t *rows, int32_t b, uint32_t *bits, void *stream);

@@ -2,7 +2,9 @@
 SPMM_FWD1) and of the bitmap builders they consume: what every mode must compute, which rows it must write, which it must leave alone and
 which bits it must set -- stated entry by entry over the stored entries of the CSR, not as a densified product, so that a filter is a
 statement about single entries here as it is in the kernel.  tests/test_sparse_hop_mirror.py checks this file against scipy products of
-the scattered dense operands; tests/test_gpu_sparse_ops.py holds the kernels to it.
+the scattered dense operands; tests/test_gpu_sparse_ops.py holds the kernels to it.  The dense backward modes (SPMM_BWD1, SPMM_BWD2:
+bwd1_dense, bwd2_dense at the end of this file) are stated the same way, with the second pass's y_in and the own-row limit a sharded
+plan passes; tests/test_dense_hop_mirror.py checks them on the CPU, tests/test_gpu_dense_hops.py holds the kernels to them.
 
 Every mode returns, next to its values, per output row the number k of stored entries that contribute and per element the magnitude S:
 the mode's own expression with the absolute value of every term.  A kernel that sums the k products in fp32 in ANY order and runs the
@@ -209,3 +211,67 @@ def spmm_filtered(a, x, h=None, row_pos=None, row_bits=None, y_in=None, gather_b
         m = y * h.astype(dtype)
         s_m = s * np.abs(h.astype(np.float64))
     return Fwd(y, m, s, s_m, k, written)
+
+
+# ---------------------------------------------------------------- the dense backward modes (SPMM_BWD1, SPMM_BWD2)
+def _dense_sum(a, x, y_in, dtype):
+    """acc[r] = (y_in[r] +) sum over the stored entries (r, c) of A[r, c] x[c], entry by entry in entry order; its magnitude; its k"""
+    n_rows = a.shape[0]
+    d = x.shape[1]
+    val = a.data.astype(dtype)
+    xx = x.astype(dtype)
+    acc = np.zeros((n_rows, d), dtype)
+    s = np.zeros((n_rows, d), np.float64)
+    k = np.zeros(n_rows, np.int64)
+    for r in range(n_rows):
+        for e in range(a.indptr[r], a.indptr[r + 1]):
+            col = int(a.indices[e])
+            acc[r] = acc[r] + val[e] * xx[col]
+            s[r] += abs(float(a.data[e])) * np.abs(x[col].astype(np.float64))
+            k[r] += 1
+    if y_in is not None:
+        acc = y_in.astype(dtype) + acc
+        s = s + np.abs(y_in.astype(np.float64))
+        k = k + 1
+    return acc, s, k
+
+
+def bwd1_dense(a, g_am, g_ax, x_in, ax, y_in=None, dtype=np.float64):
+    """SPMM_BWD1.  a: scipy CSR [n_rows][n_cols]; g_am: [n_cols][d]; g_ax, x_in, ax: [n_rows][d]; y_in (the first pass's sums): [n_rows][d].
+        dm[r] = (y_in[r] +) sum over the stored entries (r, c) of A[r, c] g_am[c]
+        u[r]  = g_ax[r] + dm[r] (.) x_in[r]
+        t[r]  = dm[r] (.) ax[r]
+    Every row is written (nz and written are all rows); an empty row gets u = g_ax and t = 0.  k counts the row's stored entries, + 1
+    with y_in.  Epilogue roundings inside the 4 of bound(): the Hadamard product and g_ax's addition for u (one when the two contract
+    into a multiply-add), the Hadamard product for t."""
+    n_rows = a.shape[0]
+    dm, s_dm, k = _dense_sum(a, g_am, y_in, dtype)
+    u = g_ax.astype(dtype) + dm * x_in.astype(dtype)
+    t = dm * ax.astype(dtype)
+    s_u = np.abs(g_ax.astype(np.float64)) + s_dm * np.abs(x_in.astype(np.float64))
+    s_t = s_dm * np.abs(ax.astype(np.float64))
+    every = np.ones(n_rows, bool)
+    return Bwd1(u, t, s_u, s_t, k, every, every.copy())
+
+
+def bwd2_dense(a, u, t, p, c, res=None, y_in=None, own_row_limit=0, dtype=np.float64):
+    """SPMM_BWD2.  u: [n_cols][d]; p: [n_rows][d]; t, res: [n_rows][d] -- or own_row_limit rows of them when that is > 0.
+        gx[r] = t[r] + ((y_in[r] +) sum over the stored entries (r, c) of A[r, c] u[c])
+        dp[r] = c gx[r] (.) elu'(p[r])  (+ res[r])
+    Rows at or behind own_row_limit have neither t nor a residual: gx = A u (+ y_in), dp = c gx (.) elu'(p).  Every row is written; an
+    empty row gets gx = t.  k counts the row's stored entries, + 1 with y_in.  Epilogue roundings inside the 4 of bound(): t's
+    addition, the Hadamard product with elu'(p), the scale by c, the residual's addition."""
+    n_rows = a.shape[0]
+    acc, s, k = _dense_sum(a, u, y_in, dtype)
+    own = n_rows if own_row_limit <= 0 else min(n_rows, int(own_row_limit))
+    gx = acc.copy()
+    gx[:own] = t[:own].astype(dtype) + acc[:own]
+    s_gx = s.copy()
+    s_gx[:own] += np.abs(t[:own].astype(np.float64))
+    eg = elu_grad(p.astype(dtype))
+    dp = dtype(c) * (gx * eg)
+    s_dp = abs(float(c)) * s_gx * eg.astype(np.float64)
+    if res is not None:
+        dp[:own] = dp[:own] + res[:own].astype(dtype)
+        s_dp[:own] += np.abs(res[:own].astype(np.float64))
+    return Bwd2(dp, gx, s_dp, s_gx, k)
