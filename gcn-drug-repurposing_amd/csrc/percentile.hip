@@ -5,6 +5,7 @@
 // 64x64 tiles, off-diagonal tiles weighted twice) and the wanted order statistic is found by a
 // 3-pass most-significant-digit radix select (11 + 11 + 10 bits of the order-preserving integer image
 // of the float), plus one min-reduction pass when the upper neighbour lies outside the final bin.
+// An inf or a NaN among the inner products is refused by name after the first pass (np.percentile would give NaN).
 // One-time setup work; MFMA-bound (2 N^2 d / 2 flops per pass).
 #include <vector>
 
@@ -140,6 +141,17 @@ extern "C" int gss_percentile(int32_t n, int32_t d, const float *e, double q, fl
     hipLaunchKernelGGL((pct_kernel<0>), grid, block, 0, st, g);
     GSS_LAUNCH_CHECK("pct_kernel<0>");
     if (int rc = read_back(h_hist.data(), hist.p, sizeof(unsigned long long) * (1u << g.nbits), st)) return rc;
+    if (pass == 0) {
+      // finite keys lie in [0x00800000, 0xFF7FFFFF]: of the 2048 top digits, 0..3 are reached by -inf and the negative NaNs only and
+      // 0x7FC..0x7FF by +inf and the positive NaNs.  np.percentile of such a matrix is NaN; no beta is returned for it
+      unsigned long long bad = 0;
+      for (int b = 0; b < 4; ++b) bad += h_hist[b] + h_hist[0x7FC + b];
+      if (bad)
+        return fail(GSS_EINVAL,
+                    "percentile: non-finite similarity: %llu of the %llu entries of E E^T are inf or NaN (a NaN or inf in the embeddings, or a "
+                    "product beyond fp32)",
+                    bad, M);
+    }
     unsigned long long cum = 0;
     int chosen = -1;
     for (int b = 0; b < (1 << g.nbits); ++b) {
@@ -149,7 +161,8 @@ extern "C" int gss_percentile(int32_t n, int32_t d, const float *e, double q, fl
       }
       cum += h_hist[b];
     }
-    if (chosen < 0) return fail(GSS_EHIP, "percentile: rank %llu not found in pass %d (NaN in the embeddings?)", rank, pass);
+    // every key is counted in pass 0 and a later pass counts the keys of a non-empty bin, so a bin is always found unless a count was lost
+    if (chosen < 0) return fail(GSS_EHIP, "percentile: rank %llu not found in pass %d: the histogram holds fewer than the %llu entries", rank, pass, M);
     rank -= cum;
     eq_count = h_hist[chosen];
     g.prefix |= (uint32_t)chosen << g.shift;

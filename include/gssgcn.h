@@ -238,7 +238,8 @@ int gss_adam_step(int64_t count, float *param, const float *grad, float *exp_avg
 
 /* ---- K12  np.percentile(E E^T, q), train.py:165-167 -------------------------------------------
  * Exact q-th percentile (linear interpolation) of all n*n inner products of the rows of e, by
- * 3-pass radix select on device.  Result to h_out (host float), synchronises the stream. */
+ * 3-pass radix select on device.  Result to h_out (host float), synchronises the stream.
+ * GSS_EINVAL, h_out untouched, when an inner product is inf or NaN in fp32 ("non-finite similarity"). */
 int gss_percentile(int32_t n, int32_t d, const float *e, double q, float *h_out, void *stream);
 
 /* ---- a1  gen_graph's similarity + top-k, helpers/helper.py:39-44 --------------------------------------

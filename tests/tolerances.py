@@ -61,3 +61,23 @@ DENSE_STEP_BOUND["rows_out"] = DENSE_STEP_BOUND["e"]          # E_B copies E's r
 # = E 5.6e-6, inv_den 3.0e-6.  Observed on an MI355X, the largest over every case of test_gpu_dense_step.py (the tests print each figure
 # before they assert): P 1.9e-6, x_next 1.9e-6, AX W1^T 6.3e-7, E 1.0e-6 of the largest entry, inv_den 2.8e-7 per row, gW1 1.5e-7, gW2
 # 2.0e-7, gb 1.6e-7; Adam from the state each launch reads: parameters 3.3e-8, m 1.2e-7, v 1.1e-7.
+
+
+# ---- the setup ops, op by op (tests/test_gpu_setup_ops.py against tests/setup_ops_mirror.py) ------------------------------------------
+# No new bound: wherever the comparison is not bit equality it is one tests/test_gpu_ops.py has always held these ops to.
+SETUP_OPS_PERCENTILE_ABS = 2e-6    # |beta - np.percentile of the fp64 similarities|, unit rows (test_percentile_exact)
+SETUP_OPS_KNN_RTOL = 1e-12         # kept similarities against numpy's fp64 product, tie-free rows (test_knn_topk_values_and_odd_sizes)
+SETUP_OPS_ROWSUM_RTOL = 1e-13      # row sums and D^-1/2 (test_normalize_adj_matches_reference_fixture)
+SETUP_OPS_AHAT_RTOL = 1.2e-7       # A_hat in fp32 against fp64 (the same test)
+# Observed on an MI355X (the tests print each figure before they assert):
+#   percentile, exact inputs: 35 cases, 721 percentiles at and around level boundaries, 0 differ from the mirror in any bit;
+#   percentile, unit rows: 7.1e-8 (n = 129, d = 16) and 4.5e-7 (n = 1000, d = 128) of the 2e-6; the count of similarities at or below the
+#     returned value off by at most half of its allowance;
+#   kNN, tie-free rows: kept values 1.5e-13 relative (n = 65, d = 8, k = 64) of the 1e-12; integer descriptors: the contract holds on all
+#     46 cases, windows bit-equal to the whole table;
+#   normalisation: row sums 4.0e-16, D^-1/2 3.3e-16 of the 1e-13; A_hat 5.9e-8 of the 1.2e-7 against fp64, and 0 bits from the mirror
+#     evaluated with the device's own D^-1/2; every shard of the asymmetric matrix and of its transpose bit-equal to A_hat.
+# Non-finite similarities (n = 65, d = 16, the lattice case with one entry replaced): before gss_percentile refused them it returned
+# GSS_OK with, at q = 0 / 50 / 98 / 100: one NaN entry -6.75, 0.0, NaN, NaN; one +inf entry NaN, 0.0, 7.63, NaN; two entries of 2e19
+# -2e19, 0.0, 1e19, NaN.  np.percentile of these matrices is NaN at every q.  On every finite case above the results before and after
+# the refusal are the same bits.
