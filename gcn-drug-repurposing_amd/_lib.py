@@ -188,6 +188,10 @@ SIGNATURES = {
     "gss_topk_overlap": (C.c_int, [_I32, _I32, _I32, _P, _P, _I32, _P, _P, _P, _P]),
     "gss_pair_sums_lists": (C.c_int, [_I32, _P, _I64, _I32, _P, _P, _P, _P]),
     "gss_pair_sums_random": (C.c_int, [_I32, _P, _I64, C.c_uint64, _I64, _I32, _I32, _P, _P, _P, _P]),
+    "gss_profile_order_workspace_bytes": (_SZ, [_I32, _I32]),
+    "gss_profile_order": (C.c_int, [_I32, _P, _I64, _I32, _P, _I32, _P, _P, _P, _P, _SZ, _P]),
+    "gss_enrich_lists": (C.c_int, [_I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
+    "gss_enrich_random": (C.c_int, [_I32, _I32, _P, _P, _I32, C.c_uint64, _I64, _I32, _I32, _P, _P, _P, _P]),
     "gss_matrix_cross_sums": (C.c_int, [_I32, _P, _I64, _P, _I64, _I32, C.c_uint64, _I64, _I64, _P, _P, _P]),
     "gss_resample_stats": (C.c_int, [_P, _I64, _I32, _I32, _I32, C.c_uint64, _I64, _I64, _P, _P]),
     "gss_embedding_scores": (C.c_int, [_I32, _I32, _P, _I64, _I32, _P, _I32, _P, _I32, _P, _I64, _P]),

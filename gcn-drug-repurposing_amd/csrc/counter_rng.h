@@ -1,5 +1,5 @@
 // counter_rng.h -- the counter-based generator of the node2vec kernels (walk.hip, sgns.hip), of proximity.hip's random sets, of
-// class_cohesion.hip's and matrix_mantel.hip's random permutations and of resample.hip's bootstrap draws and sign flips.
+// class_cohesion.hip's, matrix_mantel.hip's and enrich.hip's random permutations and of resample.hip's bootstrap draws and sign flips.
 //
 // Every random number is a pure function of (seed, stream tag, three 64-bit counters): no state is carried between draws, so
 // walks and SGNS are bitwise reproducible run to run, independent of the launch shape, and replayable by a numpy statement of
@@ -24,6 +24,7 @@ enum RngTag : uint64_t {
   kRngBootDraw = 10, // bootstrap of the per-indication metrics: (replicate, place, 0): the upper 32 bits pick the place's value out of n
   kRngSignFlip = 11, // sign-flip null of a paired difference: (replicate, place, 0): the top bit negates the place's value
   kRngMantelPerm = 12, // Mantel null: (replicate, row, 0): sort keys of the replicate's relabelling of one matrix's rows and columns
+  kRngEnrichPerm = 13, // enrichment null: (sample, place, 0): sort keys of the sample's permutation of the universe's places
 };
 
 __host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define GSS_ABI_VERSION 25  /* 25: the mean and the median of bootstrap resamples and sign flips of series, behind intervals and paired tests of the per-indication metrics -- gss_resample_stats; 24: sums of a distance matrix over the pairs of listed sets and of the prefixes of seeded random permutations, the statistic and the null of ATC class coherence -- gss_pair_sums_lists, gss_pair_sums_random; 23: entry points for tests of the halo bookkeeping and the batch preparation of a sharded plan -- gss_pack_rows, gss_unpack_rows, gss_halo_need_mark, gss_send_slot_bits, gss_bits_clear, gss_bits_set_list, gss_bits_compact, gss_bits_compact_scratch_bytes, gss_batch_prepare, gss_scatter_add_rows_ex, gss_spmm_prep_side; 22: two forward products in one launch and layer 1 one pass ahead -- gss_spmm_fwd_pair, gss_plan_l1_ahead, plan option "l1_ahead"; 21: entry points for tests of the dense half of a plan's step -- gss_dense_fwd_rows, gss_dense_fwd_first, gss_dense_fwd_split_available, gss_dense_fwd_norm, gss_rownorm_fwd_rows, gss_wgrad_slices, gss_wgrad_slices_max, gss_wgrad_partial, gss_wgrad_partial_pair, gss_wgrad_reduce, gss_wgrad_reduce_adam, gss_adam_step4, gss_transpose2; 20: entry points for tests of the loss stages of a plan's step -- gss_loss_step, gss_loss_slab_sweep, gss_loss_workspace_bytes_parts, gss_loss_gather_rows, gss_loss_gather_rows_mapped, gss_loss_gather_batch; loss_step refuses input-gradient weights at widths outside {64, 128, 256}; 19: exact typed top-k selection of listed profile columns and set overlap between selections -- gss_profile_topk, gss_profile_topk_workspace_bytes, gss_topk_overlap; 18: exact average-tie ranks of listed profile columns, the transform behind the spearman distance -- gss_profile_rank, gss_profile_rank_workspace_bytes; 17: gene knock-outs per column of the diffusion profiles -- gss_ppr_set_knockout; distances of listed column pairs of the profile matrix -- gss_profile_dist_pairs, gss_profile_dist_pairs_workspace_bytes; 16: ROC-AUC, average precision and hits@k per row in one launch -- gss_rank_metrics_rows, gss_rank_metrics_workspace_bytes; 15: entry points for tests of the row-sparse SpMM modes -- gss_spmm_bwd1_sparse_ex, gss_spmm_bwd2_sparse_res, gss_spmm_filtered, gss_mark_rows_and_neighbours, gss_batch_bits, gss_bits_fill; 14:indication x drug scores from the embedding tensor -- gss_embedding_scores; 13: pairwise distances between diffusion profiles -- gss_profile_dist; 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows.  gss_matrix_cross_sums, the permuted cross-product sum of two matrices behind Mantel's test, joined under 25 without a new number: an added export breaks no caller */
+#define GSS_ABI_VERSION 25  /* 25: the mean and the median of bootstrap resamples and sign flips of series, behind intervals and paired tests of the per-indication metrics -- gss_resample_stats; 24: sums of a distance matrix over the pairs of listed sets and of the prefixes of seeded random permutations, the statistic and the null of ATC class coherence -- gss_pair_sums_lists, gss_pair_sums_random; 23: entry points for tests of the halo bookkeeping and the batch preparation of a sharded plan -- gss_pack_rows, gss_unpack_rows, gss_halo_need_mark, gss_send_slot_bits, gss_bits_clear, gss_bits_set_list, gss_bits_compact, gss_bits_compact_scratch_bytes, gss_batch_prepare, gss_scatter_add_rows_ex, gss_spmm_prep_side; 22: two forward products in one launch and layer 1 one pass ahead -- gss_spmm_fwd_pair, gss_plan_l1_ahead, plan option "l1_ahead"; 21: entry points for tests of the dense half of a plan's step -- gss_dense_fwd_rows, gss_dense_fwd_first, gss_dense_fwd_split_available, gss_dense_fwd_norm, gss_rownorm_fwd_rows, gss_wgrad_slices, gss_wgrad_slices_max, gss_wgrad_partial, gss_wgrad_partial_pair, gss_wgrad_reduce, gss_wgrad_reduce_adam, gss_adam_step4, gss_transpose2; 20: entry points for tests of the loss stages of a plan's step -- gss_loss_step, gss_loss_slab_sweep, gss_loss_workspace_bytes_parts, gss_loss_gather_rows, gss_loss_gather_rows_mapped, gss_loss_gather_batch; loss_step refuses input-gradient weights at widths outside {64, 128, 256}; 19: exact typed top-k selection of listed profile columns and set overlap between selections -- gss_profile_topk, gss_profile_topk_workspace_bytes, gss_topk_overlap; 18: exact average-tie ranks of listed profile columns, the transform behind the spearman distance -- gss_profile_rank, gss_profile_rank_workspace_bytes; 17: gene knock-outs per column of the diffusion profiles -- gss_ppr_set_knockout; distances of listed column pairs of the profile matrix -- gss_profile_dist_pairs, gss_profile_dist_pairs_workspace_bytes; 16: ROC-AUC, average precision and hits@k per row in one launch -- gss_rank_metrics_rows, gss_rank_metrics_workspace_bytes; 15: entry points for tests of the row-sparse SpMM modes -- gss_spmm_bwd1_sparse_ex, gss_spmm_bwd2_sparse_res, gss_spmm_filtered, gss_mark_rows_and_neighbours, gss_batch_bits, gss_bits_fill; 14:indication x drug scores from the embedding tensor -- gss_embedding_scores; 13: pairwise distances between diffusion profiles -- gss_profile_dist; 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows.  gss_matrix_cross_sums, the permuted cross-product sum of two matrices behind Mantel's test, joined under 25 without a new number: an added export breaks no caller; so did gss_profile_order, gss_enrich_lists and gss_enrich_random, the preranked gene-set enrichment of profile columns */
 
 #define GSS_OK 0
 #define GSS_EINVAL (-22)   /* bad argument (shape, null pointer, unsupported d) */
@@ -634,6 +634,64 @@ int gss_profile_topk(int32_t n, const double *x, int64_t ld, int32_t nc, const i
  * untouched. */
 int gss_topk_overlap(int32_t S, int32_t G, int32_t k, const int32_t *idx, const int32_t *cnt, int32_t T, const int32_t *a, const int32_t *b,
                      int32_t *shared, void *stream);
+
+/* ---- preranked gene-set enrichment of profile columns: does a set of nodes as a whole sit higher in a profile than random sets of its size
+ * (enrich.py; the running sum of Subramanian et al. 2005 with a gene-set permutation null; the reference ships
+ * data/protein_to_functional_pathway.tsv and no code that scores a set)
+ * universe: device int32 [M], strictly ascending node indices in [0, n), 2 <= M <= 65,536; a "place" u in [0, M) is an index into it.
+ * gss_profile_order: x: device fp64 [n][ld], profile c = column c; cols: device int32 [nc], honoured as given (any order, repeats allowed;
+ * null = columns 0 .. nc - 1) -> pos_out: device int32 [nc][M], w_out: device fp64 [nc][M].  For list position j (column c = cols[j]):
+ *   pos_out[j][u] = the place of u in np.argsort(-x[universe, c], kind="stable"),   w_out[j][u] = |x[universe[u], c]|
+ * EXACTLY: descending value, ties by the smaller place, under IEEE comparison as in gss_profile_topk (-0.0 and +0.0 tie, +-inf are ordinary
+ * extremes, subnormals distinct values).  A NaN at a universe node flags the column: every pos = -1 and every w = NaN; a NaN at a node
+ * outside the universe changes nothing.  A column's output depends on that column's values at the universe alone, bit for bit.
+ * Kernels: a key pass writes the descending keys ~order_key(x) (rank_keys.h) [nc][M] into the workspace and |x| into w_out; then one
+ * workgroup per column sorts chunks of 4,096 (key, place) pairs in LDS and every place adds, per chunk, the number of pairs below its
+ * own to its word of pos_out -- quadratic in M / 4,096, hence the limit on M.  No atomics; every output word has one owner.
+ * workspace: the caller's, device, 8-byte aligned, at least gss_profile_order_workspace_bytes(M, nc) = 256 + nc M 8 bytes (0 for
+ * arguments outside the limits).  Nothing is allocated inside.  nc = 0 checks the universe and writes nothing.  Refuses (GSS_EINVAL, by
+ * name in gss_last_error, outputs untouched): n outside [1, 2^24], M outside [2, min(n, 65,536)], nc outside [0, 65,535], ld < 1, a null
+ * universe or workspace, a misaligned or too small workspace (naming the needed size), with nc > 0 a null x, pos_out or w_out, a
+ * misaligned pos_out or w_out, ld below nc where cols is null; a universe entry outside [0, n) or not above its predecessor and a cols
+ * entry outside [0, ld) (by position and value: one check launch and one synchronisation of the stream each). */
+size_t gss_profile_order_workspace_bytes(int32_t M, int32_t nc);
+int gss_profile_order(int32_t n, const double *x, int64_t ld, int32_t nc, const int32_t *cols, int32_t M, const int32_t *universe, int32_t *pos_out,
+                      double *w_out, void *workspace, size_t workspace_bytes, void *stream);
+/* The enrichment score of a set S of s distinct places, 1 <= s <= min(1024, M - 1), in a column (pos, w) of gss_profile_order: the members
+ * in ascending pos, p_0 < ... < p_{s-1}, with a_k = w of the k-th member (weighted) or 1.0 (unweighted); fp64, every operation rounded on
+ * its own (no fused multiply-add):
+ *   N = 0.0;  for k: N = N + a_k                         sequential, from +0.0;  N == 0.0: ES = NaN, peak = -1
+ *   c = 0.0;  hi = -inf, khi = -1;  lo = +inf, klo = -1
+ *   for k = 0 .. s - 1:  miss = (double)(p_k - k) / (double)(M - s);  l = c / N - miss;  c = c + a_k;  h = c / N - miss
+ *                        if h > hi: hi = h, khi = k;   if l < lo: lo = l, klo = k
+ *   ES = hi, peak = khi  if hi >= -lo,  else  ES = lo, peak = klo
+ * -- the extreme of the running sum over all M places (a peak lies just after a hit, a trough just before one).  A flagged column gives
+ * ES = NaN, peak = -1.  The bits of a (column, set) depend on the column and the set alone: not on the list's order, its position among the
+ * lists, nc, the grid, an earlier call or the entry point.  Nothing is accumulated with atomics; every output word has one owner.
+ * gss_enrich_lists: C sets in CSR form over places, device int32 ptr [C + 1] (ptr[0] = 0) and idx [ptr[C]]; weighted: 0 or 1 -> es_out:
+ * device fp64 [nc][C], peak_out: device int32 [nc][C].  One workgroup per (set, column): the members' (pos, place) pairs are sorted in LDS
+ * and one lane walks them.  C = 0 or nc = 0 is a no-op.  Refuses (GSS_EINVAL, by name, outputs untouched): M outside [2, 65,536], nc
+ * outside [0, 65,535], weighted outside {0, 1}, C < 0, a null pos, w, ptr, idx, es_out or peak_out, a ptr that is no CSR row pointer, a
+ * list of length 0, above 1024 or above M - 1 (by list), a place outside [0, M) or repeated within its list (by list, position and value:
+ * the first list, a range before a repeat, the first such position resp. the second position of the least repeated place; one check
+ * launch with a status word allocated and freed inside).  Reads ptr back and synchronises the stream. */
+int gss_enrich_lists(int32_t M, int32_t nc, const int32_t *pos, const double *w, int32_t weighted, int32_t C, const int32_t *ptr, const int32_t *idx,
+                     double *es_out, int32_t *peak_out, void *stream);
+/* gss_enrich_random: the same score over random sets.  For sample s = s0 .. s0 + P - 1: key_i = rng_key(seed, kRngEnrichPerm = 13, s, i, 0)
+ * (csrc/counter_rng.h) for the places i in [0, M), pi_s = the places sorted by (key, i) ascending -- a pure function of (seed, s, M),
+ * replayable in numpy (tests/enrich_mirror.py) -- and es_out[j][s - s0][k] = ES of the set pi_s[0 : sizes[k]] in column j: one permutation
+ * serves every size and every column.  sizes: device int32 [n_sizes], strictly ascending in [1, min(1024, M - 1)]; es_out: device fp64
+ * [nc][P][n_sizes]; perm_out: null, or device int32 [P][sizes[n_sizes - 1]], the prefix of pi_s.  One workgroup per sample: the kmax =
+ * sizes[n_sizes - 1] smallest keys are an exact selection -- the keys at or under a threshold are collected in LDS (the first threshold is
+ * floor(2^64 (kmax + kmax / 4 + 8) / M), every key where M <= 2048), the threshold is bisected while fewer than kmax or more than 2,048
+ * came, and the collected (key, i) pairs are sorted: the result does not depend on the thresholds tried.  Per column the prefix is sorted
+ * once by pos, each member keeping its rank rho in pi_s; size m is the subsequence with rho < m, walked by one lane per size in exactly the
+ * order of the definition: the bits of (column, sample, size) equal gss_enrich_lists on pi_s[0 : m].  Samples are numbered, not drawn: a
+ * call over [s0, s0 + P) equals the same samples in any split.  Refuses (GSS_EINVAL, by name, outputs untouched): M outside [2, 65,536],
+ * nc < 0, weighted outside {0, 1}, P < 1, s0 < 0 or s0 + P > 2^31, n_sizes outside [1, min(1024, M - 1)], a null sizes, with nc > 0 a
+ * null pos, w or es_out, a size outside [1, min(1024, M - 1)] or not above its predecessor.  Reads sizes back and synchronises the stream. */
+int gss_enrich_random(int32_t M, int32_t nc, const int32_t *pos, const double *w, int32_t weighted, uint64_t seed, int64_t s0, int32_t P,
+                      int32_t n_sizes, const int32_t *sizes, double *es_out, int32_t *perm_out, void *stream);
 
 /* ---- sums of a symmetric distance matrix over the pairs of a set: the coherence of a drug class and its null (drug_classes.py; the reference
  * ships data/drug_classification_df.tsv, multiscale/README.md dataset 7, and has no code that reads it)
