@@ -73,6 +73,9 @@ SIGNATURES = {
     "gss_csr_create": (C.c_int, [C.POINTER(_P), _I32, _I32, _I64, _P, _P, _P, _P]),
     "gss_csr_destroy": (None, [_P]),
     "gss_csr_set_hot": (C.c_int, [_P, _I32, _I32, _I32]),
+    "gss_csr_set_job_cols": (C.c_int, [_P, _I64]),
+    "gss_csr_job_cols": (C.c_int, [_P, C.POINTER(_I64)]),
+    "gss_spmm_auto_slices": (C.c_int, [_I32, _I64, C.POINTER(_I32), C.POINTER(_I32)]),
     "gss_spmm": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P]),
     "gss_spmm_add": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P]),
     "gss_spmm_bwd1": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P]),

@@ -17,6 +17,11 @@ struct gss_csr {
   int32_t max_row = 0;
   int32_t hot_own = -1, hot_halo0 = 0, hot_halo1 = 0;  // gss_csr_set_hot: operand rows [0, hot_own) and [hot_halo0, hot_halo1) are the hubs' (-1: no split)
   int32_t seg_edges = 32;         // entries per segment of the balanced SpMM (a view: its parent's)
+  // gss_csr_set_job_cols: the operand rows the JOB multiplies by (a shard: the global N); < 0 = this handle's own n_cols.  What the
+  // automatic feature-slice count is decided from (spmm.hip launch_balanced): the slice count fixes how a row's segment sums are
+  // grouped, so it must not depend on who owns the row.  A view: its parent's
+  int64_t job_cols = -1;
+  int64_t policy_cols() const { return job_cols >= 0 ? job_cols : (int64_t)n_cols; }
   std::vector<int32_t> h_rowptr;  // host copy, used to build segment descriptors lazily
   // a VIEW (spmm.hip GiantRows): the schedule covers the listed rows / entry ranges of the borrowed arrays instead of every row of rowptr
   bool by_items = false;

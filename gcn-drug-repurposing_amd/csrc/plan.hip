@@ -410,6 +410,15 @@ int plan_create_impl(gss_plan **out, const gss_plan_desc *desc, const gss_shard_
   }
   if (P > 1)
     if (int rc = check_job_knobs(comm, snap)) return rc;
+  if (shard) {
+    // The ONE place that declares the job's operand rows on a shard's matrices (gss_csr_set_job_cols): the SpMM's automatic slice
+    // count -- and with it how a row's segment sums are grouped -- then follows the job's N on every rank, not the rank's own rows +
+    // halo, and a node's row has the bits of the one-GPU plan whoever owns it.  (The handles are the caller's, created mutable by
+    // gss_csr_create; a_loc_t holds partial rows, no row of the one-GPU matrix, and keeps its own count.)
+    for (const gss_csr *h : {a, at, shard->a_own, shard->a_halo, shard->at_own, shard->at_halo})
+      if (h)
+        if (int rc = gss_csr_set_job_cols(const_cast<gss_csr *>(h), n_global)) return rc;
+  }
   gss_plan *p = new gss_plan();
   p->knobs = snap;
   KnobScope knob_scope(&p->knobs);

@@ -838,6 +838,22 @@ static int launch_balanced_t(const gss_csr *a, int d4_slice, int nslices, bool p
   return GSS_OK;
 }
 
+// The automatic feature-slice policy (knob spmm_slices = 0; gss_spmm_auto_slices is its public face).  The slice COUNT is decided from
+// `cols_job`, the operand rows of the whole job: it sets the lane-group width and with it the groups per wave, i.e. how a row's segment
+// sums are grouped (xor tree inside a wave, then in wave order) -- a shard that decided from its own, smaller operand would round a
+// hub row differently from the one-GPU run.  Whether the slices are pinned to XCDs or time-separated is cache policy, changes no bit
+// and follows the operand this launch really gathers from (`cols_local`).
+static void auto_slices(int d4, int64_t cols_job, int64_t cols_local, int *ns_out, bool *pin_out) {
+  *ns_out = 1;
+  *pin_out = false;
+  if (d4 >= 32 && d4 % 16 == 0 && 16.0 * d4 * (double)cols_job > 8.0 * 1024 * 1024) {
+    int ns = d4 / 16 > 8 ? 8 : d4 / 16;
+    while (d4 % ns != 0) --ns;
+    *ns_out = ns;
+    *pin_out = ns > 1 && 16.0 * d4 * (double)cols_local <= 64.0 * 1024 * 1024;
+  }
+}
+
 template <int MODE>
 static int launch_balanced(const gss_csr *a, int d4, const float *x, const SpmmEpi &ep, hipStream_t st, const SpmmSecond *second = nullptr) {
   int ns = K().spmm_slices;
@@ -851,14 +867,7 @@ static int launch_balanced(const gss_csr *a, int d4, const float *x, const SpmmE
     //  * larger operands (RMAT scale): time-separated slices -- grid.y is the slow dispatch dimension, so the caches
     //    hold one slice of the table at a time.  N = 250k: d = 128 319 -> 260 us, d = 256 768 -> 568 us; N = 1M:
     //    d = 128 1.74 -> 1.50 ms, d = 256 3.09 -> 2.76 ms; pinning is 2-7 % behind there.
-    const double table = 16.0 * d4 * (double)a->n_cols;
-    ns = 1;
-    pin = false;
-    if (d4 >= 32 && d4 % 16 == 0 && table > 8.0 * 1024 * 1024) {
-      ns = d4 / 16 > 8 ? 8 : d4 / 16;
-      while (d4 % ns != 0) --ns;
-      pin = table <= 64.0 * 1024 * 1024;
-    }
+    auto_slices(d4, a->policy_cols(), a->n_cols, &ns, &pin);
   }
   if (ns < 1 || d4 % ns != 0 || (d4 / ns) < 4 || MODE == SPMM_BWD1S) ns = 1;  // the sparse mode gathers few rows anyway
   pin = pin && ns > 1;
@@ -944,6 +953,7 @@ static void giant_view_init(gss_csr &v, const gss_csr *a, int32_t n_rows, int32_
   v.hot_halo0 = a->hot_halo0;
   v.hot_halo1 = a->hot_halo1;
   v.seg_edges = a->seg_edges;
+  v.job_cols = a->policy_cols();   // (the finish view too, whose own operand is the few chunk sums: a giant row's three launches group alike, on every owner)
   v.by_items = true;
   v.item_row.reserve(items.size());
   v.item_first.reserve(items.size());
@@ -1350,6 +1360,33 @@ int gss_csr_set_hot(gss_csr *a, int32_t own_hot, int32_t halo_begin, int32_t hal
       v->hot_halo0 = halo_begin;
       v->hot_halo1 = halo_end;
     }
+  return GSS_OK;
+}
+
+int gss_csr_set_job_cols(gss_csr *a, int64_t cols) {
+  GSS_REQUIRE(a, "csr_set_job_cols: null handle");
+  GSS_REQUIRE(cols >= (int64_t)a->n_cols && cols < (int64_t)INT32_MAX, "csr_set_job_cols: %lld operand rows in the job, this handle alone gathers from %d",
+              (long long)cols, a->n_cols);
+  a->job_cols = cols;
+  if (a->cache.giant)   // the views follow, the finish view included
+    for (gss_csr *v : {&a->cache.giant->chunks, &a->cache.giant->shortv, &a->cache.giant->finish}) v->job_cols = cols;
+  return GSS_OK;
+}
+
+int gss_csr_job_cols(const gss_csr *a, int64_t *cols_out) {
+  GSS_REQUIRE(a && cols_out, "csr_job_cols: null argument");
+  *cols_out = a->policy_cols();
+  return GSS_OK;
+}
+
+int gss_spmm_auto_slices(int32_t d, int64_t cols, int32_t *slices_out, int32_t *pinned_out) {
+  if (int rc = check_d(d)) return rc;
+  GSS_REQUIRE(cols >= 0 && slices_out && pinned_out, "spmm_auto_slices: bad argument");
+  int ns = 1;
+  bool pin = false;
+  auto_slices(d / 4, cols, cols, &ns, &pin);
+  *slices_out = ns;
+  *pinned_out = pin ? 1 : 0;
   return GSS_OK;
 }
 

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define GSS_ABI_VERSION 25  /* 25: the mean and the median of bootstrap resamples and sign flips of series, behind intervals and paired tests of the per-indication metrics -- gss_resample_stats; 24: sums of a distance matrix over the pairs of listed sets and of the prefixes of seeded random permutations, the statistic and the null of ATC class coherence -- gss_pair_sums_lists, gss_pair_sums_random; 23: entry points for tests of the halo bookkeeping and the batch preparation of a sharded plan -- gss_pack_rows, gss_unpack_rows, gss_halo_need_mark, gss_send_slot_bits, gss_bits_clear, gss_bits_set_list, gss_bits_compact, gss_bits_compact_scratch_bytes, gss_batch_prepare, gss_scatter_add_rows_ex, gss_spmm_prep_side; 22: two forward products in one launch and layer 1 one pass ahead -- gss_spmm_fwd_pair, gss_plan_l1_ahead, plan option "l1_ahead"; 21: entry points for tests of the dense half of a plan's step -- gss_dense_fwd_rows, gss_dense_fwd_first, gss_dense_fwd_split_available, gss_dense_fwd_norm, gss_rownorm_fwd_rows, gss_wgrad_slices, gss_wgrad_slices_max, gss_wgrad_partial, gss_wgrad_partial_pair, gss_wgrad_reduce, gss_wgrad_reduce_adam, gss_adam_step4, gss_transpose2; 20: entry points for tests of the loss stages of a plan's step -- gss_loss_step, gss_loss_slab_sweep, gss_loss_workspace_bytes_parts, gss_loss_gather_rows, gss_loss_gather_rows_mapped, gss_loss_gather_batch; loss_step refuses input-gradient weights at widths outside {64, 128, 256}; 19: exact typed top-k selection of listed profile columns and set overlap between selections -- gss_profile_topk, gss_profile_topk_workspace_bytes, gss_topk_overlap; 18: exact average-tie ranks of listed profile columns, the transform behind the spearman distance -- gss_profile_rank, gss_profile_rank_workspace_bytes; 17: gene knock-outs per column of the diffusion profiles -- gss_ppr_set_knockout; distances of listed column pairs of the profile matrix -- gss_profile_dist_pairs, gss_profile_dist_pairs_workspace_bytes; 16: ROC-AUC, average precision and hits@k per row in one launch -- gss_rank_metrics_rows, gss_rank_metrics_workspace_bytes; 15: entry points for tests of the row-sparse SpMM modes -- gss_spmm_bwd1_sparse_ex, gss_spmm_bwd2_sparse_res, gss_spmm_filtered, gss_mark_rows_and_neighbours, gss_batch_bits, gss_bits_fill; 14:indication x drug scores from the embedding tensor -- gss_embedding_scores; 13: pairwise distances between diffusion profiles -- gss_profile_dist; 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows.  gss_matrix_cross_sums, the permuted cross-product sum of two matrices behind Mantel's test, joined under 25 without a new number: an added export breaks no caller; so did gss_profile_order, gss_enrich_lists and gss_enrich_random, the preranked gene-set enrichment of profile columns */
+#define GSS_ABI_VERSION 25  /* 25: the mean and the median of bootstrap resamples and sign flips of series, behind intervals and paired tests of the per-indication metrics -- gss_resample_stats; 24: sums of a distance matrix over the pairs of listed sets and of the prefixes of seeded random permutations, the statistic and the null of ATC class coherence -- gss_pair_sums_lists, gss_pair_sums_random; 23: entry points for tests of the halo bookkeeping and the batch preparation of a sharded plan -- gss_pack_rows, gss_unpack_rows, gss_halo_need_mark, gss_send_slot_bits, gss_bits_clear, gss_bits_set_list, gss_bits_compact, gss_bits_compact_scratch_bytes, gss_batch_prepare, gss_scatter_add_rows_ex, gss_spmm_prep_side; 22: two forward products in one launch and layer 1 one pass ahead -- gss_spmm_fwd_pair, gss_plan_l1_ahead, plan option "l1_ahead"; 21: entry points for tests of the dense half of a plan's step -- gss_dense_fwd_rows, gss_dense_fwd_first, gss_dense_fwd_split_available, gss_dense_fwd_norm, gss_rownorm_fwd_rows, gss_wgrad_slices, gss_wgrad_slices_max, gss_wgrad_partial, gss_wgrad_partial_pair, gss_wgrad_reduce, gss_wgrad_reduce_adam, gss_adam_step4, gss_transpose2; 20: entry points for tests of the loss stages of a plan's step -- gss_loss_step, gss_loss_slab_sweep, gss_loss_workspace_bytes_parts, gss_loss_gather_rows, gss_loss_gather_rows_mapped, gss_loss_gather_batch; loss_step refuses input-gradient weights at widths outside {64, 128, 256}; 19: exact typed top-k selection of listed profile columns and set overlap between selections -- gss_profile_topk, gss_profile_topk_workspace_bytes, gss_topk_overlap; 18: exact average-tie ranks of listed profile columns, the transform behind the spearman distance -- gss_profile_rank, gss_profile_rank_workspace_bytes; 17: gene knock-outs per column of the diffusion profiles -- gss_ppr_set_knockout; distances of listed column pairs of the profile matrix -- gss_profile_dist_pairs, gss_profile_dist_pairs_workspace_bytes; 16: ROC-AUC, average precision and hits@k per row in one launch -- gss_rank_metrics_rows, gss_rank_metrics_workspace_bytes; 15: entry points for tests of the row-sparse SpMM modes -- gss_spmm_bwd1_sparse_ex, gss_spmm_bwd2_sparse_res, gss_spmm_filtered, gss_mark_rows_and_neighbours, gss_batch_bits, gss_bits_fill; 14:indication x drug scores from the embedding tensor -- gss_embedding_scores; 13: pairwise distances between diffusion profiles -- gss_profile_dist; 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows.  gss_matrix_cross_sums, the permuted cross-product sum of two matrices behind Mantel's test, joined under 25 without a new number: an added export breaks no caller; so did gss_profile_order, gss_enrich_lists and gss_enrich_random, the preranked gene-set enrichment of profile columns; and gss_csr_set_job_cols, gss_csr_job_cols and gss_spmm_auto_slices, the job-wide operand row count behind the SpMM's automatic slice count */
 
 #define GSS_OK 0
 #define GSS_EINVAL (-22)   /* bad argument (shape, null pointer, unsupported d) */
@@ -94,6 +94,22 @@ void gss_csr_destroy(gss_csr *a);
  * every other row with the non-temporal policy, so that once-read rows do not evict the hubs' rows.  own_hot = -1: no split
  * (the default).  Speed only: results are unchanged. */
 int gss_csr_set_hot(gss_csr *a, int32_t own_hot, int32_t halo_begin, int32_t halo_end);
+/* The operand rows the JOB multiplies by: the global N for the matrices of a node-range shard, whose own operand (n_cols) holds only
+ * its rows and the boundary rows it reads.  Default: the handle's own n_cols, so a handle nobody declares anything on behaves as
+ * before.  The balanced SpMM decides its automatic feature-slice count (knob "spmm_slices" = 0) from THIS count, not from n_cols: the
+ * slice count sets the lane-group width and so how the segment sums of a row of more than 64 entries are grouped, and a row must be
+ * rounded alike on every owner -- a shard's rows are bit-identical to the one-GPU product's rows only when both sides decide from the
+ * same count.  Everything that is cache policy (slices pinned to XCDs or time-separated, 32-bit gather offsets, the hot / cold
+ * split) changes no bit and still follows n_cols.  cols must be >= n_cols.  The giant-row views of the handle (gss_csr_giant_rows)
+ * carry the handle's count, the finish pass included.  gss_plan_create_sharded declares h_bounds[world] on every matrix it is given
+ * (a, at and the split halves), so callers of the plan need not; call it yourself for products you run on a shard's handle outside a
+ * plan.  gss_csr_job_cols reads the count in force back. */
+int gss_csr_set_job_cols(gss_csr *a, int64_t cols);
+int gss_csr_job_cols(const gss_csr *a, int64_t *cols_out);
+/* The automatic slice policy as a pure function (no handle, no device): what a dense-mode product of width d over a handle whose job
+ * count AND own operand are both `cols` rows picks under "spmm_slices" = 0 -- *slices_out feature slices (1 = unsliced), *pinned_out
+ * = 1 when they are pinned to XCDs, 0 when time-separated or unsliced.  (N = 29,960, d = 128: 2 slices, pinned.) */
+int gss_spmm_auto_slices(int32_t d, int64_t cols, int32_t *slices_out, int32_t *pinned_out);
 /* Rows with more stored entries than knob "spmm_giant" (default 32,768; 0 = never) are not one workgroup's job: the dense products cut
  * them into chunks of a quarter of that, sum the chunks in a pass of their own and add a row's chunks in order in a finish pass that runs
  * the product's epilogue (three launches of the same kernel; results agree with the unchunked sum to rounding, rows below the threshold
