@@ -352,3 +352,11 @@ def ptr(t) -> int:
 def current_stream() -> int:
     import torch
     return torch.cuda.current_stream().cuda_stream
+
+
+def seed64(seed) -> int:
+    return int(seed) & (2 ** 64 - 1)   # the uint64 word the kernels absorb (counter_rng.h): any Python int, modulo 2^64
+
+
+def row_stride(x) -> int:
+    return x.stride(0) if x.shape[0] > 1 else x.shape[1]   # one row: no row stride is ever applied (torch leaves it unspecified)

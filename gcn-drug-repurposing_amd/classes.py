@@ -17,54 +17,16 @@ import sys
 import numpy as np
 
 from . import _lib, predict
+from ._nulls import NULL_CHUNK_BYTES, benjamini_hochberg, chunked_null, device_lists, int32_array, square_matrix  # noqa: F401
 from .diffusion import ALL_METRICS as METRICS
 from .predict import PredictError, write_tsv
 
 MAX_POOL = 4096               # gss_pair_sums_random sorts a sample's permutation in LDS
-NULL_CHUNK_BYTES = 256 << 20  # the null comes back in calls of at most this many bytes of sums
 LEVELS = (1, 2, 3, 4)
 HEADER = ["level", "class", "class_name", "n_drugs", "n_pairs", "mean_distance", "null_mean", "null_std", "z", "p", "q"]
 
 
 # ---- the kernels ---------------------------------------------------------------------------------------------------------------------
-
-def _matrix(dist, who, labels=None):
-    """-> the device fp64 matrix [n][n] the kernels read: a device tensor in place, a host array uploaded.  A NaN distance (a zero profile
-    under cosine, a constant one under correlation) is refused with its row's label"""
-    import torch
-    if isinstance(dist, torch.Tensor):
-        d = dist
-        if (d.dim() != 2 or d.dtype != torch.float64 or not d.is_cuda or d.shape[0] != d.shape[1] or d.shape[0] < 1
-                or (d.shape[1] > 1 and d.stride(1) != 1) or (d.shape[0] > 1 and d.stride(0) < d.shape[1])):
-            raise ValueError(f"{who}: a distance tensor must be a square device fp64 matrix with unit column stride and a row stride of at "
-                             "least its width")
-    else:
-        host = np.ascontiguousarray(dist, dtype=np.float64)
-        if host.ndim != 2 or host.shape[0] != host.shape[1] or host.shape[0] < 1:
-            raise ValueError(f"{who}: a host distance array must be square, not {host.shape}")
-        if not torch.cuda.is_available():
-            raise _lib.GssError(f"{who}: the sums run on the GPU only (no CPU fallback)")
-        d = torch.from_numpy(host).cuda()
-    if labels is not None and len(labels) != d.shape[0]:
-        raise ValueError(f"{who}: {len(labels)} labels for {d.shape[0]} rows")
-    bad = torch.isnan(d).any(dim=1)
-    if bool(bad.any()):
-        i = int(torch.nonzero(bad)[0])
-        raise ValueError(f"{who}: a distance of {labels[i] if labels is not None else 'row ' + str(i)!r} is NaN (its diffusion profile is zero "
-                         "or constant); it cannot be scored")
-    return d
-
-
-def _ld(d):
-    return d.stride(0) if d.shape[0] > 1 else d.shape[1]
-
-
-def _int32(what, v, who):
-    a = np.asarray(v, dtype=np.int64).reshape(-1)
-    if len(a) and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
-        raise ValueError(f"{who}: {what} holds an entry outside int32")
-    return a.astype(np.int32)
-
 
 def pair_sums(dist, lists, labels=None):
     """the sum of dist over the pairs of each list -> device tensor fp64 [len(lists)]: for the ordered list a, T = r_1 + ... + r_{m-1} with
@@ -73,20 +35,15 @@ def pair_sums(dist, lists, labels=None):
     uploaded; assumed symmetric.  lists: sequences of row numbers in [0, n), any order and length; one shorter than 2 gives 0.0.  A NaN in
     dist is refused with the row's label (labels[i], else its number).  No CPU fallback."""
     import torch
-    d = _matrix(dist, "pair_sums", labels)
-    hl = [_int32(f"list {c}", l, "pair_sums") for c, l in enumerate(lists)]
+    d = square_matrix(dist, "pair_sums", labels)
+    hl = [int32_array(f"list {c}", l, "pair_sums") for c, l in enumerate(lists)]
     out = torch.empty(len(hl), dtype=torch.float64, device=d.device)
     if not hl:
         return out
-    ptr = np.zeros(len(hl) + 1, dtype=np.int64)
-    np.cumsum([len(l) for l in hl], out=ptr[1:])
-    if ptr[-1] >= 2 ** 31:
-        raise ValueError(f"pair_sums: the lists hold {int(ptr[-1])} entries, int32 offsets do not reach")
     with torch.cuda.device(d.device):
-        d_ptr = torch.from_numpy(ptr.astype(np.int32)).to(d.device)
-        d_idx = torch.from_numpy(np.concatenate(hl) if ptr[-1] else np.zeros(1, dtype=np.int32)).to(d.device)
-        _lib.check(_lib.load().gss_pair_sums_lists(d.shape[0], d.data_ptr(), _ld(d), len(hl), d_ptr.data_ptr(), d_idx.data_ptr(), out.data_ptr(),
-                                                   _lib.current_stream()), "gss_pair_sums_lists")
+        d_ptr, d_idx = device_lists(hl, "pair_sums", "lists", d.device)
+        _lib.check(_lib.load().gss_pair_sums_lists(d.shape[0], d.data_ptr(), _lib.row_stride(d), len(hl), d_ptr.data_ptr(), d_idx.data_ptr(),
+                                                   out.data_ptr(), _lib.current_stream()), "gss_pair_sums_lists")
     return out
 
 
@@ -97,23 +54,21 @@ def random_pair_sums(dist, sizes, samples, seed=0, first=0, perms=False, labels=
     and a size has the same bits alone and among others).  sizes: strictly ascending in [2, n]; n <= 4096.  perms=True also returns the
     permutations' prefixes, device int32 [samples][sizes[-1]].  dist and labels as in pair_sums.  No CPU fallback."""
     import torch
-    d = _matrix(dist, "random_pair_sums", labels)
-    hs = _int32("sizes", sizes, "random_pair_sums")
+    d = square_matrix(dist, "random_pair_sums", labels)
+    hs = int32_array("sizes", sizes, "random_pair_sums")
     P, ns = int(samples), len(hs)
     with torch.cuda.device(d.device):
         sums = torch.empty(max(P, 0), ns, dtype=torch.float64, device=d.device)
         d_sizes = torch.from_numpy(hs if ns else np.zeros(1, dtype=np.int32)).to(d.device)
         perm = torch.empty(max(P, 0), int(hs[-1]) if ns and hs[-1] > 0 else 0, dtype=torch.int32, device=d.device) if perms else None
-        _lib.check(_lib.load().gss_pair_sums_random(d.shape[0], d.data_ptr(), _ld(d), int(seed) & (2 ** 64 - 1), int(first), P, ns,
-                                                    d_sizes.data_ptr(), sums.data_ptr(), _lib.ptr(perm), _lib.current_stream()),
-                   "gss_pair_sums_random")
+        _lib.check(_lib.load().gss_pair_sums_random(d.shape[0], d.data_ptr(), _lib.row_stride(d), _lib.seed64(seed), int(first), P, ns, d_sizes.data_ptr(),
+                                                    sums.data_ptr(), _lib.ptr(perm), _lib.current_stream()), "gss_pair_sums_random")
     return (sums, perm) if perms else sums
 
 
 def null_sums(d, sizes, samples, seed=0):
     """random_pair_sums brought to the host -> fp64 [samples][len(sizes)], in calls of at most NULL_CHUNK_BYTES of sums each"""
-    step = max(1, NULL_CHUNK_BYTES // (8 * len(sizes)))
-    return np.concatenate([random_pair_sums(d, sizes, min(step, samples - f), seed, f).cpu().numpy() for f in range(0, samples, step)])
+    return chunked_null(lambda count, first: random_pair_sums(d, sizes, count, seed, first), samples, 8 * len(sizes))
 
 
 # ---- the statistics (host) -----------------------------------------------------------------------------------------------------------
@@ -137,17 +92,6 @@ def cohesion_stats(observed, n_drugs, sizes, null):
     return out
 
 
-def benjamini_hochberg(p):
-    """q[i] = min over the p-values p_(j) >= p[i] of p_(j) * n / j (j = the rank from 1, ascending, ties in the given order), at most 1"""
-    p = np.asarray(p, dtype=np.float64)
-    n = len(p)
-    order = np.argsort(p, kind="stable")
-    scaled = p[order] * n / np.arange(1, n + 1)
-    q = np.empty(n)
-    q[order] = np.minimum(1.0, np.minimum.accumulate(scaled[::-1])[::-1])
-    return q
-
-
 def class_cohesion(dist, classes, samples, seed=0, labels=None, return_null=False):
     """classes: {name: rows} or a sequence of row lists (rows of dist, each drug once, at least 2) -> one dict per class, in order: "class"
     (the name or the position), n_drugs, n_pairs, mean_distance, null_mean, null_std, z, p (cohesion_stats) from pair_sums of the classes
@@ -162,7 +106,7 @@ def class_cohesion(dist, classes, samples, seed=0, labels=None, return_null=Fals
         raise ValueError("class_cohesion: no class")
     if int(samples) < 1:
         raise ValueError(f"class_cohesion: samples={samples} must be at least 1")
-    d = _matrix(dist, "class_cohesion", labels)
+    d = square_matrix(dist, "class_cohesion", labels)
     sizes = sorted({len(l) for l in lists})
     observed = pair_sums(d, lists).cpu().numpy()
     null = null_sums(d, sizes, int(samples), seed)

@@ -3,22 +3,16 @@
 //
 // include/gssgcn.h has the contract, DESIGN.md section 9.12 the definitions, the cost model and the measurements.  One statement of the sum
 // serves both entry points (pair_prefix_sums): for an ordered list a[0 .. m) of rows of the symmetric fp64 matrix d,
-//   r_j  = sum over i < j of d[a[j]][a[i]]    one wave per row j: lane l adds the terms i = l, l + 64, ... in ascending order from +0.0, the
-//                                              64 partial sums meet in wave_sum_d's butterfly -- an order that depends on j alone;
+//   r_j  = sum over i < j of d[a[j]][a[i]]    one wave per row j, in perm_null.h's fixed order (wave_ordered_sum): it depends on j alone;
 //   T(m) = r_1 + r_2 + ... + r_{m-1}          added in that order by one thread that walks j and writes T at each requested size.
 // So T(m) is a function of the ordered list and d: its bits do not depend on the grid, on the other lists or samples of the call, on the
 // other sizes asked for, or on the chunks the rows are taken in.  Nothing is accumulated with atomics.
 //   cc_lists_kernel    one workgroup per list; the list is read from global memory, r_j goes through an LDS buffer of kCcRowChunk rows;
-//   cc_random_kernel   one workgroup per sample s: the keys rng_key(seed, kRngClassPerm, s, i, 0) of i = 0 .. n - 1 (counter_rng.h) are sorted
-//                      in LDS by (key, i) ascending -- rank_keys.h's sort_pairs, the bitonic network with the index as the second word of the comparison, so
-//                      that the permutation is a total order and equal keys cannot make it depend on the network -- and the first
-//                      sizes[n_sizes - 1] places are the list; r_j reuses the keys' LDS.
-// The first m places of a uniformly random permutation are a uniformly random m-subset for every m: one permutation per sample serves every size.
+//   cc_random_kernel   one workgroup per sample s: perm_null.h's permutation under the tag kRngClassPerm, sorted in LDS; its first
+//                      sizes[n_sizes - 1] places are the list, every shorter prefix a smaller set, and r_j reuses the keys' LDS.
 #include "profile_front.h"
 
-#include <memory>
-
-#include "counter_rng.h"
+#include "perm_null.h"
 
 namespace gss {
 namespace {
@@ -27,14 +21,6 @@ constexpr int kCcThreads = 256;
 constexpr int kCcWaves = kCcThreads / kWave;
 constexpr int kCcMaxN = 4096;       // the permutation of a sample is sorted in LDS: 4,096 x 12 B
 constexpr int kCcRowChunk = 1024;   // rows of a list whose sums wait in LDS for the walking thread
-
-// r_j of the list a (global memory or LDS); every lane of the wave must reach the call, and every lane returns the sum
-__device__ __forceinline__ double row_pair_sum(const double *__restrict__ d, int64_t ld, const int32_t *a, int32_t j, int lane) {
-  const double *__restrict__ row = d + (int64_t)a[j] * ld;
-  double v = 0.0;
-  for (int32_t i = lane; i < j; i += kWave) v += row[a[i]];
-  return wave_sum_d(v);
-}
 
 // T(sizes[k]) of the list a[0 .. m) -> out[k] for the n_sizes sizes (strictly ascending, in [2, m]); r: LDS, cap doubles.  Rows are taken cap
 // at a time; thread 0 carries T across the chunks.  Made of barriers: EVERY thread of the workgroup must reach the call, with the same m
@@ -46,7 +32,8 @@ __device__ __forceinline__ void pair_prefix_sums(const double *__restrict__ d, i
   for (int32_t j0 = 1; j0 < m; j0 += cap) {
     const int32_t j1 = j0 + cap < m ? j0 + cap : m;
     for (int32_t j = j0 + wave; j < j1; j += kCcWaves) {
-      const double v = row_pair_sum(d, ld, a, j, lane);
+      const double *__restrict__ row = d + (int64_t)a[j] * ld;
+      const double v = wave_ordered_sum<1>(j, lane, [&](int32_t i) { return row[a[i]]; });   // r_j; a: global memory or LDS
       if (lane == 0) r[j - j0] = v;
     }
     __syncthreads();
@@ -75,7 +62,7 @@ __global__ __launch_bounds__(kCcThreads) void cc_lists_kernel(const double *__re
   pair_prefix_sums(d, ld, idx + b, m, &len, 1, sum_out + c, r, kCcRowChunk, tid);
 }
 
-// sample s0 + blockIdx.x.  LDS: key [cpad] then idx [cpad]; the padding (kBehind, i >= n) sorts behind every (key, i < n)
+// sample s0 + blockIdx.x.  LDS: key [cpad] then idx [cpad]
 __global__ __launch_bounds__(kCcThreads) void cc_random_kernel(int32_t n, const double *__restrict__ d, int64_t ld, uint64_t seed, int64_t s0,
                                                                 int32_t cpad, int32_t n_sizes, const int32_t *__restrict__ sizes, int32_t m_max,
                                                                 double *__restrict__ sums_out, int32_t *__restrict__ perm_out) {
@@ -85,7 +72,7 @@ __global__ __launch_bounds__(kCcThreads) void cc_random_kernel(int32_t n, const 
   const int32_t tid = threadIdx.x;
   const uint64_t s = (uint64_t)(s0 + blockIdx.x);
   for (int32_t i = tid; i < cpad; i += kCcThreads) {
-    key[i] = i < n ? rng_key(seed, kRngClassPerm, s, (uint64_t)i, 0) : kBehind;
+    key[i] = i < n ? perm_key(seed, kRngClassPerm, s, i) : kBehind;
     idx[i] = i;
   }
   __syncthreads();
@@ -118,10 +105,7 @@ int gss_pair_sums_lists(int32_t n, const double *d, int64_t ld, int32_t C, const
   GSS_REQUIRE(sum_out != nullptr, "pair_sums_lists: sum_out is null");
   hipStream_t st = as_stream(stream);
   std::unique_ptr<int32_t[]> h;
-  if (int rc = host_copy(h, ptr, (size_t)C + 1, st, "pair_sums_lists: host copy of ptr, %d lists", C)) return rc;
-  GSS_REQUIRE(h[0] == 0, "pair_sums_lists: ptr[0] = %d must be 0", h[0]);
-  for (int32_t c = 0; c < C; ++c)
-    GSS_REQUIRE(h[c + 1] >= h[c], "pair_sums_lists: ptr[%d] = %d is below ptr[%d] = %d", c + 1, h[c + 1], c, h[c]);
+  if (int rc = check_list_offsets("pair_sums_lists", ptr, C, st, h)) return rc;
   const int32_t total = h[C];
   if (total > 0) {   // nothing reads d through a list before every entry of it is known to be a row; the status words are freed before the launch
     GSS_REQUIRE(idx != nullptr, "pair_sums_lists: idx is null");
@@ -140,19 +124,15 @@ int gss_pair_sums_random(int32_t n, const double *d, int64_t ld, uint64_t seed, 
   GSS_REQUIRE(n >= 2 && n <= kCcMaxN, "pair_sums_random: n=%d is outside [2, %d] (a sample's permutation is sorted in LDS)", n, kCcMaxN);
   if (int rc = check_matrix("pair_sums_random", n, d, ld)) return rc;
   GSS_REQUIRE(P >= 1, "pair_sums_random: P=%d samples must be >= 1", P);
-  GSS_REQUIRE(s0 >= 0 && s0 + (int64_t)P <= (int64_t)1 << 31, "pair_sums_random: samples s0=%lld .. s0 + P=%lld are outside [0, 2^31]", (long long)s0,
-              (long long)(s0 + (int64_t)P));
+  if (int rc = check_sample_window("pair_sums_random", s0, P)) return rc;
   GSS_REQUIRE(n_sizes >= 1 && n_sizes <= n - 1, "pair_sums_random: n_sizes=%d is outside [1, n - 1 = %d]", n_sizes, n - 1);
   GSS_REQUIRE(sizes != nullptr, "pair_sums_random: sizes is null");
   GSS_REQUIRE(sums_out != nullptr, "pair_sums_random: sums_out is null");
   hipStream_t st = as_stream(stream);
   std::unique_ptr<int32_t[]> h;
-  if (int rc = host_copy(h, sizes, (size_t)n_sizes, st, "pair_sums_random: host copy of %d sizes", n_sizes)) return rc;
-  for (int32_t k = 0; k < n_sizes; ++k) {
-    GSS_REQUIRE(h[k] >= 2 && h[k] <= n, "pair_sums_random: sizes[%d] = %d is outside [2, n=%d]", k, h[k], n);
-    GSS_REQUIRE(k == 0 || h[k] > h[k - 1], "pair_sums_random: sizes[%d] = %d is not above sizes[%d] = %d (strictly ascending)", k, h[k], k - 1,
-                h[k - 1]);
-  }
+  char hi_words[32];
+  snprintf(hi_words, sizeof(hi_words), "n=%d", n);
+  if (int rc = check_sizes("pair_sums_random", sizes, n_sizes, 2, n, hi_words, st, h)) return rc;
   const int32_t cpad = pow2_at_least(n);
   hipLaunchKernelGGL(cc_random_kernel, dim3(P), dim3(kCcThreads), (size_t)cpad * 12, st, n, d, ld, seed, s0, cpad, n_sizes, sizes, h[n_sizes - 1],
                      sums_out, perm_out);

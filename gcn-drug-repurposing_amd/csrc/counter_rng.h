@@ -1,5 +1,5 @@
 // counter_rng.h -- the counter-based generator of the node2vec kernels (walk.hip, sgns.hip), of proximity.hip's random sets, of
-// class_cohesion.hip's, matrix_mantel.hip's and enrich.hip's random permutations and of resample.hip's bootstrap draws and sign flips.
+// perm_null.h's seeded permutations (one tag per null) and of resample.hip's bootstrap draws and sign flips.
 //
 // Every random number is a pure function of (seed, stream tag, three 64-bit counters): no state is carried between draws, so
 // walks and SGNS are bitwise reproducible run to run, independent of the launch shape, and replayable by a numpy statement of

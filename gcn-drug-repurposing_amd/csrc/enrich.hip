@@ -11,7 +11,7 @@
 //                                           word of pos_out (the first chunk stores); a column with a NaN is rewritten as -1 / NaN.
 //   gss_enrich_lists    ES and its peak of listed sets: one workgroup per (set, column) sorts the members' (pos, place) pairs in LDS and
 //                       one lane walks them (es_walk, the one statement of the score).
-//   gss_enrich_random   the null: one workgroup per sample s selects the kmax smallest of the M keys rng_key(seed, kRngEnrichPerm, s, i, 0)
+//   gss_enrich_random   the null: one workgroup per sample s selects the kmax smallest of the M keys perm_key(seed, kRngEnrichPerm, s, i)
 //                       exactly -- the keys at or under a threshold are collected in LDS, the threshold is bisected when fewer than kmax or
 //                       more than the buffer holds came, and sort_pairs orders what came by (key, i): the result is the prefix of the
 //                       permutation whatever the thresholds were -- then per column sorts the prefix by pos, keeping each member's rank
@@ -21,9 +21,7 @@
 // integer counters and bitmaps in LDS and the refusal's status word), and every output word has one owner.
 #include "profile_front.h"
 
-#include <memory>
-
-#include "counter_rng.h"
+#include "perm_null.h"
 
 namespace gss {
 namespace {
@@ -247,7 +245,7 @@ __global__ __launch_bounds__(kEsThreads) void es_random_kernel(int32_t M, int32_
     if (tid == 0) count = 0;
     __syncthreads();
     for (int32_t i = tid; i < M; i += kEsThreads) {
-      const uint64_t k = rng_key(seed, kRngEnrichPerm, s, (uint64_t)i, 0);
+      const uint64_t k = perm_key(seed, kRngEnrichPerm, s, i);
       if (k <= T) {
         const int32_t slot = atomicAdd(&count, 1);
         if (slot < kSelCap) {
@@ -277,7 +275,7 @@ __global__ __launch_bounds__(kEsThreads) void es_random_kernel(int32_t M, int32_
   const int32_t spad = pow2_at_least(got);
   for (int32_t i = got + tid; i < spad; i += kEsThreads) {
     sel_key[i] = kBehind;
-    sel_idx[i] = M + i;    // behind a place whose key is all ones
+    sel_idx[i] = M + i;    // perm_null.h's padding: an index >= M sorts behind a place whose key is all ones
   }
   __syncthreads();
   sort_pairs<kEsThreads>(sel_key, sel_idx, spad, tid);   // the order it leaves does not depend on the slots the keys came in: (key, i) is total
@@ -398,11 +396,9 @@ int gss_enrich_lists(int32_t M, int32_t nc, const int32_t *pos, const double *w,
   GSS_REQUIRE(peak_out != nullptr, "enrich_lists: peak_out is null");
   hipStream_t st = as_stream(stream);
   std::unique_ptr<int32_t[]> h;
-  if (int rc = host_copy(h, ptr, (size_t)C + 1, st, "enrich_lists: host copy of ptr, %d lists", C)) return rc;
-  GSS_REQUIRE(h[0] == 0, "enrich_lists: ptr[0] = %d must be 0", h[0]);
+  if (int rc = check_list_offsets("enrich_lists", ptr, C, st, h)) return rc;
   const int32_t s_max = max_set(M);
   for (int32_t c = 0; c < C; ++c) {
-    GSS_REQUIRE(h[c + 1] >= h[c], "enrich_lists: ptr[%d] = %d is below ptr[%d] = %d", c + 1, h[c + 1], c, h[c]);
     const int32_t s = h[c + 1] - h[c];
     GSS_REQUIRE(s >= 1 && s <= s_max, "enrich_lists: list %d has %d places, outside [1, min(%d, M - 1) = %d]", c, s, kEsMaxSet, s_max);
   }
@@ -432,8 +428,7 @@ int gss_enrich_random(int32_t M, int32_t nc, const int32_t *pos, const double *w
   if (int rc = check_order("enrich_random", M, nc)) return rc;
   GSS_REQUIRE(weighted == 0 || weighted == 1, "enrich_random: weighted=%d must be 0 or 1", weighted);
   GSS_REQUIRE(P >= 1, "enrich_random: P=%d samples must be >= 1", P);
-  GSS_REQUIRE(s0 >= 0 && s0 + (int64_t)P <= (int64_t)1 << 31, "enrich_random: samples s0=%lld .. s0 + P=%lld are outside [0, 2^31]", (long long)s0,
-              (long long)(s0 + (int64_t)P));
+  if (int rc = check_sample_window("enrich_random", s0, P)) return rc;
   const int32_t s_max = max_set(M);
   GSS_REQUIRE(n_sizes >= 1 && n_sizes <= s_max, "enrich_random: n_sizes=%d is outside [1, min(%d, M - 1) = %d]", n_sizes, kEsMaxSet, s_max);
   GSS_REQUIRE(sizes != nullptr, "enrich_random: sizes is null");
@@ -444,12 +439,9 @@ int gss_enrich_random(int32_t M, int32_t nc, const int32_t *pos, const double *w
   }
   hipStream_t st = as_stream(stream);
   std::unique_ptr<int32_t[]> h;
-  if (int rc = host_copy(h, sizes, (size_t)n_sizes, st, "enrich_random: host copy of %d sizes", n_sizes)) return rc;
-  for (int32_t k = 0; k < n_sizes; ++k) {
-    GSS_REQUIRE(h[k] >= 1 && h[k] <= s_max, "enrich_random: sizes[%d] = %d is outside [1, min(%d, M - 1) = %d]", k, h[k], kEsMaxSet, s_max);
-    GSS_REQUIRE(k == 0 || h[k] > h[k - 1], "enrich_random: sizes[%d] = %d is not above sizes[%d] = %d (strictly ascending)", k, h[k], k - 1,
-                h[k - 1]);
-  }
+  char hi_words[48];
+  snprintf(hi_words, sizeof(hi_words), "min(%d, M - 1) = %d", kEsMaxSet, s_max);
+  if (int rc = check_sizes("enrich_random", sizes, n_sizes, 1, s_max, hi_words, st, h)) return rc;
   if (nc == 0 && !perm_out) return GSS_OK;
   const int32_t kmax = h[n_sizes - 1];
   // the first threshold expects kmax + kmax / 4 + 8 of the M keys under it (include/gssgcn.h states it: a test replays a sample that it fails)

@@ -5,23 +5,19 @@
 // fp64 matrices a, b [n][n]:
 //   out[s] = sum over 0 <= i < j < n of a[j][i] * b[pi_s(j)][pi_s(i)]
 //   mode 0  plain   pi = the identity: the observed statistic, with the arithmetic of the null (one replicate);
-//   mode 1  null    pi_s = 0 .. n - 1 sorted ascending by (rng_key(seed, kRngMantelPerm, s, i, 0), i) (counter_rng.h): rank_keys.h's
-//                   sort_pairs in LDS, the construction of class_cohesion.hip's samples under a tag of its own.
+//   mode 1  null    pi_s = perm_null.h's permutation under the tag kRngMantelPerm, sorted in LDS.
 // The order of the additions is fixed:
-//   r_j = sum over i < j of a[j][i] * b[pi(j)][pi(i)]   one wave per row j = 1 .. n - 1: lane l adds the terms i = l, l + 64, ... in ascending
-//                                                        order from +0.0, every product rounded on its own (the file is compiled with
-//                                                        contraction off: no fused multiply-add), and the 64 partial sums meet in
-//                                                        wave_sum_d's butterfly (a lane without a term brings its +0.0);
+//   r_j = sum over i < j of a[j][i] * b[pi(j)][pi(i)]   one wave per row j = 1 .. n - 1, in perm_null.h's fixed order (wave_ordered_sum),
+//                                                        every product rounded on its own (the file is compiled with contraction off: no
+//                                                        fused multiply-add);
 //   T   = r_1 + r_2 + ... + r_{n-1}                     added in that order by one thread.
 // So a replicate's bits are a function of (n, a, b, seed, s) alone: not of first / count, the grid or the other replicates of the call, and a
 // numpy statement of the same additions reproduces them (tests/mantel_mirror.py).  Nothing is accumulated with atomics.
-// One workgroup per replicate.  a is read along its rows (coalesced); b is gathered inside one row, pi(j), per wave: a lane's additions are a
-// dependent chain by definition, so the loads of kMtAhead strides are issued ahead of their additions, which stay in order.
-#include "rank_keys.h"
+// One workgroup per replicate.  a is read along its rows (coalesced); b is gathered inside one row, pi(j), per wave, kMtAhead strides ahead
+// of the additions.
+#include "perm_null.h"
 
-#include "counter_rng.h"
-
-#pragma clang fp contract(off)
+#pragma clang fp contract(off)   // the products of the row sum's terms
 
 namespace gss {
 namespace {
@@ -32,27 +28,7 @@ constexpr int kMtMaxN = 4096;         // pi is sorted in LDS: 4,096 x 12 B
 constexpr int kMtAhead = 4;           // strides of a row whose loads are in flight before the first of their additions
 constexpr int kMtMaxGrid = 1 << 20;   // replicates per launch
 
-// r_j; every lane of the wave must reach the call, and every lane returns the sum
-__device__ __forceinline__ double row_cross_sum(const double *__restrict__ arow, const double *__restrict__ brow, const int32_t *pi, int32_t j,
-                                                int lane) {
-  double v = 0.0;
-  int32_t i = lane;
-  for (; i + (kMtAhead - 1) * kWave < j; i += kMtAhead * kWave) {
-    double x[kMtAhead], y[kMtAhead];
-#pragma unroll
-    for (int u = 0; u < kMtAhead; ++u) {
-      x[u] = arow[i + u * kWave];
-      y[u] = brow[pi[i + u * kWave]];
-    }
-#pragma unroll
-    for (int u = 0; u < kMtAhead; ++u) v = v + x[u] * y[u];
-  }
-  for (; i < j; i += kWave) v = v + arow[i] * brow[pi[i]];
-  return wave_sum_d(v);
-}
-
-// replicate first + blockIdx.x.  LDS: key [cpad] then pi [cpad]; the padding (kBehind, i >= n) sorts behind every (key, i < n).  After the
-// sort the keys' LDS holds the row sums: n - 1 <= cpad of them
+// replicate first + blockIdx.x.  LDS: key [cpad] then pi [cpad].  After the sort the keys' LDS holds the row sums: n - 1 <= cpad of them
 __global__ __launch_bounds__(kMtThreads) void mantel_cross_kernel(int32_t n, const double *__restrict__ a, int64_t lda, const double *__restrict__ b,
                                                                    int64_t ldb, int32_t mode, uint64_t seed, int64_t first, int32_t cpad,
                                                                    double *__restrict__ out, int32_t *__restrict__ perm_out) {
@@ -62,8 +38,8 @@ __global__ __launch_bounds__(kMtThreads) void mantel_cross_kernel(int32_t n, con
   const int32_t tid = threadIdx.x;
   const int wave = tid / kWave, lane = tid % kWave;
   const uint64_t s = (uint64_t)(first + blockIdx.x);
-  for (int32_t i = tid; i < cpad; i += kMtThreads) {
-    key[i] = mode == 1 && i < n ? rng_key(seed, kRngMantelPerm, s, (uint64_t)i, 0) : kBehind;
+  for (int32_t i = tid; i < cpad; i += kMtThreads) {   // mode 0: every pair is padding and stays where it is
+    key[i] = mode == 1 && i < n ? perm_key(seed, kRngMantelPerm, s, i) : kBehind;
     pi[i] = i;
   }
   __syncthreads();
@@ -72,7 +48,8 @@ __global__ __launch_bounds__(kMtThreads) void mantel_cross_kernel(int32_t n, con
     for (int32_t i = tid; i < n; i += kMtThreads) perm_out[(int64_t)blockIdx.x * n + i] = pi[i];
   double *r = reinterpret_cast<double *>(key);
   for (int32_t j = 1 + wave; j < n; j += kMtWaves) {
-    const double v = row_cross_sum(a + (int64_t)j * lda, b + (int64_t)pi[j] * ldb, pi, j, lane);
+    const double *__restrict__ arow = a + (int64_t)j * lda, *__restrict__ brow = b + (int64_t)pi[j] * ldb;
+    const double v = wave_ordered_sum<kMtAhead>(j, lane, [&](int32_t i) { return arow[i] * brow[pi[i]]; });   // r_j
     if (lane == 0) r[j] = v;
   }
   __syncthreads();

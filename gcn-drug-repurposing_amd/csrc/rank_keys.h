@@ -61,8 +61,8 @@ __device__ __forceinline__ void sort_keys(uint64_t *key, int32_t cpad, int32_t t
 }
 
 // sort_keys over the pairs (key[i], idx[i]), ascending by key, then by index: with distinct indices the order is total, so equal keys cannot
-// make it depend on the network.  The seeded permutations of class_cohesion.hip and matrix_mantel.hip are idx after this sort of
-// counter-based keys.  Made of barriers, as sort_keys is
+// make it depend on the network.  perm_null.h's seeded permutations are idx after this sort of counter-based keys.  Made of barriers, as
+// sort_keys is
 template <int THREADS>
 __device__ __forceinline__ void sort_pairs(uint64_t *key, int32_t *idx, int32_t cpad, int32_t tid) {
   for (int32_t k = 2; k <= cpad; k <<= 1) {

@@ -199,10 +199,6 @@ def _column_list(what, sel, width, names=None, who="compare_profiles"):
     return idx.astype(np.int32)
 
 
-def _row_stride(x):
-    return x.stride(0) if x.shape[0] > 1 else x.shape[1]   # one row: no row stride is ever applied (torch leaves it unspecified)
-
-
 def _device_list(cols, dev):
     """a host column list -> what a kernel takes for it: None when it is 0, 1, ... len - 1 ("the first columns" needs no list, and no check
     of one), else a device int32 tensor"""
@@ -228,7 +224,7 @@ def _rank_columns(x, cols):
     with torch.cuda.device(x.device):
         need = int(lib.gss_profile_rank_workspace_bytes(n, nc))
         ws, lst = _workspace(need, x.device), _device_list(cols, x.device)
-        _lib.check(lib.gss_profile_rank(n, x.data_ptr(), _row_stride(x), nc, _lib.ptr(lst), r.data_ptr(), nc, ws.data_ptr(), need,
+        _lib.check(lib.gss_profile_rank(n, x.data_ptr(), _lib.row_stride(x), nc, _lib.ptr(lst), r.data_ptr(), nc, ws.data_ptr(), need,
                                         _lib.current_stream()), "gss_profile_rank")
     return r
 
@@ -356,7 +352,7 @@ def top_nodes(profiles, cols=None, k=20, groups=None, n_groups=None, device="cud
         need = int(lib.gss_profile_topk_workspace_bytes(n, nc, G, int(k)))
         ws, lst = _workspace(need, x.device), _device_list(c, x.device)
         d_grp = None if grp is None else grp.to(device=x.device, dtype=torch.int32).contiguous()
-        _lib.check(lib.gss_profile_topk(n, x.data_ptr(), _row_stride(x), nc, _lib.ptr(lst), G, _lib.ptr(d_grp), int(k), idx.data_ptr(),
+        _lib.check(lib.gss_profile_topk(n, x.data_ptr(), _lib.row_stride(x), nc, _lib.ptr(lst), G, _lib.ptr(d_grp), int(k), idx.data_ptr(),
                                         val.data_ptr(), cnt.data_ptr(), ws.data_ptr(), need, _lib.current_stream()), "gss_profile_topk")
     return idx, val, cnt
 
@@ -427,7 +423,7 @@ def compare_profiles(profiles, rows, cols, metric, device="cuda"):
         x, (ca, cb) = _rank_referenced(x, [ca, cb])
     with torch.cuda.device(x.device):
         la, lb = _device_list(ca, x.device), _device_list(cb, x.device)
-        _lib.check(_lib.load().gss_profile_dist(n, x.data_ptr(), _row_stride(x), len(ca), _lib.ptr(la), len(cb), _lib.ptr(lb), metric_id,
+        _lib.check(_lib.load().gss_profile_dist(n, x.data_ptr(), _lib.row_stride(x), len(ca), _lib.ptr(la), len(cb), _lib.ptr(lb), metric_id,
                                                 out.data_ptr(), len(cb), _lib.current_stream()), "gss_profile_dist")
     return out
 
@@ -461,7 +457,7 @@ def compare_profile_pairs(profiles, col_a, col_b, metric, device="cuda"):
         need = int(lib.gss_profile_dist_pairs_workspace_bytes(n, len(ca)))
         ws = _workspace(need, x.device)
         da, db = torch.from_numpy(ca).to(x.device), torch.from_numpy(cb).to(x.device)
-        _lib.check(lib.gss_profile_dist_pairs(n, x.data_ptr(), _row_stride(x), len(ca), da.data_ptr(), db.data_ptr(), metric_id,
+        _lib.check(lib.gss_profile_dist_pairs(n, x.data_ptr(), _lib.row_stride(x), len(ca), da.data_ptr(), db.data_ptr(), metric_id,
                                               out.data_ptr(), ws.data_ptr(), need, _lib.current_stream()), "gss_profile_dist_pairs")
     return out
 

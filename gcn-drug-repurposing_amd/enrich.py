@@ -17,13 +17,12 @@ import sys
 import numpy as np
 
 from . import _lib, predict
-from .classes import benjamini_hochberg
+from ._nulls import NULL_CHUNK_BYTES, benjamini_hochberg, chunked_null, device_lists, int32_array  # noqa: F401
 from .msi import DRUG, FUNCTIONAL_PATHWAY, INDICATION, PROTEIN
 from .predict import PredictError, write_tsv
 
 MAX_SET = 1024                # gss_enrich_lists sorts a set's members in LDS
 MAX_UNIVERSE = 65536          # gss_profile_order counts in chunks, quadratic in M / chunk
-NULL_CHUNK_BYTES = 256 << 20  # the null comes back in calls of at most this many bytes of scores
 BUILT_IN_SETS = {"functions": FUNCTIONAL_PATHWAY, "indications": INDICATION, "drugs": DRUG}
 HEADER = ["node", "node_name", "set", "set_name", "size", "es", "nes", "p", "q", "lead_size", "lead"]
 
@@ -32,13 +31,6 @@ Order = collections.namedtuple("Order", ["pos", "w", "universe"])
 
 
 # ---- the kernels ---------------------------------------------------------------------------------------------------------------------
-
-def _int32(what, v, who):
-    a = np.asarray(v, dtype=np.int64).reshape(-1)
-    if len(a) and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
-        raise ValueError(f"{who}: {what} holds an entry outside int32")
-    return a.astype(np.int32)
-
 
 def _check_order(order, who):
     import torch
@@ -59,14 +51,14 @@ def profile_order(profiles, cols, universe, device="cuda"):
     fallback."""
     import torch
 
-    from .diffusion import _device_list, _profile_source, _row_stride, _workspace
+    from .diffusion import _device_list, _profile_source, _workspace
     dev = torch.device(device)
     if dev.type != "cuda":
         raise _lib.GssError("the order of a profile is computed on the GPU only (no CPU fallback)")
     n, (c,), upload = _profile_source(profiles, (cols,), ("column",), "profile_order")
     if n < 1:
         raise ValueError("profile_order: the profiles are empty")
-    uni = _int32("universe", universe, "profile_order")
+    uni = int32_array("universe", universe, "profile_order")
     M, nc = len(uni), len(c)
     x = upload(dev)
     pos = torch.empty(nc, M, dtype=torch.int32, device=x.device)
@@ -76,7 +68,7 @@ def profile_order(profiles, cols, universe, device="cuda"):
         need = int(lib.gss_profile_order_workspace_bytes(M, nc))
         ws, lst = _workspace(max(need, 256), x.device), _device_list(c, x.device)
         d_uni = torch.from_numpy(uni if M else np.zeros(1, dtype=np.int32)).to(x.device)
-        _lib.check(lib.gss_profile_order(n, x.data_ptr(), _row_stride(x), nc, _lib.ptr(lst), M, d_uni.data_ptr(), pos.data_ptr(), w.data_ptr(),
+        _lib.check(lib.gss_profile_order(n, x.data_ptr(), _lib.row_stride(x), nc, _lib.ptr(lst), M, d_uni.data_ptr(), pos.data_ptr(), w.data_ptr(),
                                          ws.data_ptr(), max(need, 256), _lib.current_stream()), "gss_profile_order")
     return Order(pos, w, uni)
 
@@ -90,19 +82,14 @@ def enrichment_scores(order, sets, weighted=True):
     profile that holds a NaN, gives NaN and -1.  No CPU fallback."""
     import torch
     nc, M = _check_order(order, "enrichment_scores")
-    hl = [_int32(f"set {c}", l, "enrichment_scores") for c, l in enumerate(sets)]
+    hl = [int32_array(f"set {c}", l, "enrichment_scores") for c, l in enumerate(sets)]
     dev = order.pos.device
     es = torch.empty(nc, len(hl), dtype=torch.float64, device=dev)
     peak = torch.empty(nc, len(hl), dtype=torch.int32, device=dev)
     if not hl or nc == 0:
         return es, peak
-    ptr = np.zeros(len(hl) + 1, dtype=np.int64)
-    np.cumsum([len(l) for l in hl], out=ptr[1:])
-    if ptr[-1] >= 2 ** 31:
-        raise ValueError(f"enrichment_scores: the sets hold {int(ptr[-1])} entries, int32 offsets do not reach")
     with torch.cuda.device(dev):
-        d_ptr = torch.from_numpy(ptr.astype(np.int32)).to(dev)
-        d_idx = torch.from_numpy(np.concatenate(hl) if ptr[-1] else np.zeros(1, dtype=np.int32)).to(dev)
+        d_ptr, d_idx = device_lists(hl, "enrichment_scores", "sets", dev)
         _lib.check(_lib.load().gss_enrich_lists(M, nc, order.pos.data_ptr(), order.w.data_ptr(), int(bool(weighted)), len(hl), d_ptr.data_ptr(),
                                                 d_idx.data_ptr(), es.data_ptr(), peak.data_ptr(), _lib.current_stream()), "gss_enrich_lists")
     return es, peak
@@ -117,14 +104,14 @@ def random_enrichment_scores(order, sizes, samples, seed=0, first=0, perms=False
     fallback."""
     import torch
     nc, M = _check_order(order, "random_enrichment_scores")
-    hs = _int32("sizes", sizes, "random_enrichment_scores")
+    hs = int32_array("sizes", sizes, "random_enrichment_scores")
     P, ns = int(samples), len(hs)
     dev = order.pos.device
     with torch.cuda.device(dev):
         es = torch.empty(nc, max(P, 0), ns, dtype=torch.float64, device=dev)
         d_sizes = torch.from_numpy(hs if ns else np.zeros(1, dtype=np.int32)).to(dev)
         perm = torch.empty(max(P, 0), int(hs[-1]) if ns and hs[-1] > 0 else 0, dtype=torch.int32, device=dev) if perms else None
-        _lib.check(_lib.load().gss_enrich_random(M, nc, order.pos.data_ptr(), order.w.data_ptr(), int(bool(weighted)), int(seed) & (2 ** 64 - 1),
+        _lib.check(_lib.load().gss_enrich_random(M, nc, order.pos.data_ptr(), order.w.data_ptr(), int(bool(weighted)), _lib.seed64(seed),
                                                  int(first), P, ns, d_sizes.data_ptr(), es.data_ptr(), _lib.ptr(perm), _lib.current_stream()),
                    "gss_enrich_random")
     return (es, perm) if perms else es
@@ -132,9 +119,8 @@ def random_enrichment_scores(order, sizes, samples, seed=0, first=0, perms=False
 
 def null_scores(order, sizes, samples, seed=0, weighted=True):
     """random_enrichment_scores brought to the host -> fp64 [profiles][samples][len(sizes)], in calls of at most NULL_CHUNK_BYTES of scores"""
-    step = max(1, NULL_CHUNK_BYTES // (8 * len(sizes) * max(1, order.pos.shape[0])))
-    return np.concatenate([random_enrichment_scores(order, sizes, min(step, samples - f), seed, f, weighted=weighted).cpu().numpy()
-                           for f in range(0, samples, step)], axis=1)
+    return chunked_null(lambda count, first: random_enrichment_scores(order, sizes, count, seed, first, weighted=weighted), samples,
+                        8 * len(sizes) * max(1, order.pos.shape[0]), axis=1)
 
 
 # ---- the statistics (host) -----------------------------------------------------------------------------------------------------------
@@ -143,7 +129,7 @@ def enrichment_stats(es, peak, sets, pos, sizes, null):
     """one profile: es [C] and peak [C] of the sets (lists of places), the profile's pos [M], against the null scores [P][len(sizes)] -> a
     list of dicts.  Per set, with t = column sizes.index(len(set)) of the null and "same sign" = t >= 0 for ES >= 0, t < 0 otherwise (a NaN
     never counts): n_same, p = (1 + #{same-sign t with |t| >= |ES|}) / (1 + n_same), nes = ES / np.mean(|same-sign t|) (nan when
-    n_same = 0), q = classes.benjamini_hochberg over the profile's sets with a finite ES, and lead = the leading edge: the members in the
+    n_same = 0), q = benjamini_hochberg over the profile's sets with a finite ES, and lead = the leading edge: the members in the
     profile's order up to and including the peak for ES >= 0, from the peak on otherwise.  A set whose ES is NaN has n_same = 0, p = nes
     = q = nan and no leading edge."""
     col = {int(m): k for k, m in enumerate(sizes)}

@@ -15,7 +15,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
-from .classes import NULL_CHUNK_BYTES, _ld, _matrix
+from ._nulls import chunked_null, square_matrix
 
 MAX_N = 4096                  # gss_matrix_cross_sums sorts a replicate's permutation in LDS
 METHODS = ("pearson", "spearman")
@@ -24,9 +24,9 @@ METHODS = ("pearson", "spearman")
 # ---- the kernel ----------------------------------------------------------------------------------------------------------------------
 
 def _symmetric(m, who, name, labels=None):
-    """classes._matrix plus exact symmetry: the kernel reads both triangles of the permuted matrix"""
+    """square_matrix plus exact symmetry: the kernel reads both triangles of the permuted matrix"""
     import torch
-    d = _matrix(m, who, labels)
+    d = square_matrix(m, who, labels)
     if not torch.equal(d, d.T):
         raise ValueError(f"{who}: {name} is not symmetric (it must equal its transpose exactly)")
     return d
@@ -47,8 +47,9 @@ def _cross_sums(da, db, mode, seed, first, count, perms):
     with torch.cuda.device(da.device):
         out = torch.empty(max(count, 0), dtype=torch.float64, device=da.device)
         perm = torch.empty(max(count, 0), n, dtype=torch.int32, device=da.device) if perms else None
-        _lib.check(_lib.load().gss_matrix_cross_sums(n, da.data_ptr(), _ld(da), db.data_ptr(), _ld(db), mode, int(seed) & (2 ** 64 - 1), int(first),
-                                                     count, out.data_ptr(), _lib.ptr(perm), _lib.current_stream()), "gss_matrix_cross_sums")
+        _lib.check(_lib.load().gss_matrix_cross_sums(n, da.data_ptr(), _lib.row_stride(da), db.data_ptr(), _lib.row_stride(db), mode,
+                                                     _lib.seed64(seed), int(first), count, out.data_ptr(), _lib.ptr(perm), _lib.current_stream()),
+                   "gss_matrix_cross_sums")
     return (out, perm) if perms else out
 
 
@@ -71,8 +72,7 @@ def observed_cross_sum(a, b, labels=None):
 
 def null_cross_sums(a, b, samples, seed=0):
     """cross_sums brought to the host -> fp64 [samples], in calls of at most NULL_CHUNK_BYTES of sums each"""
-    step = max(1, NULL_CHUNK_BYTES // 8)
-    return np.concatenate([cross_sums(a, b, min(step, samples - f), seed, f).cpu().numpy() for f in range(0, samples, step)])
+    return chunked_null(lambda count, first: cross_sums(a, b, count, seed, first), samples, 8)
 
 
 # ---- the standardisation (device) ----------------------------------------------------------------------------------------------------

@@ -123,7 +123,7 @@ def random_walks(adj, num_walks, walk_length, p=1.0, q=1.0, seed=0, device="cuda
     if a.nnz:
         _lib.check(lib.gss_walk_prefix(n, _lib.ptr(rowptr), _lib.ptr(val), _lib.ptr(cum), stream), "gss_walk_prefix")
     _lib.check(lib.gss_node2vec_walks(n, _lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(val), _lib.ptr(cum), n_walks, _lib.ptr(starts),
-                                      int(walk_length), float(p), float(q), int(seed) & (2 ** 64 - 1), _lib.ptr(walks), _lib.ptr(lengths),
+                                      int(walk_length), float(p), float(q), _lib.seed64(seed), _lib.ptr(walks), _lib.ptr(lengths),
                                       stream), "gss_node2vec_walks")
     return walks, lengths
 
@@ -159,7 +159,7 @@ def train_sgns(walks, lengths, n, dim=128, window=10, epochs=5, negative=5, samp
     d_keep = torch.from_numpy(sample_int).to(dev)
     syn0 = torch.empty((n, dim), dtype=torch.float32, device=dev)
     syn1 = torch.empty((n, dim), dtype=torch.float32, device=dev)
-    _lib.check(lib.gss_sgns_init(n, dim, int(seed) & (2 ** 64 - 1), _lib.ptr(syn0), _lib.ptr(syn1), stream), "gss_sgns_init")
+    _lib.check(lib.gss_sgns_init(n, dim, _lib.seed64(seed), _lib.ptr(syn0), _lib.ptr(syn1), stream), "gss_sgns_init")
     if concurrency is None:
         concurrency = lib.gss_sgns_default_concurrency()
         if concurrency < 1:
@@ -167,7 +167,7 @@ def train_sgns(walks, lengths, n, dim=128, window=10, epochs=5, negative=5, samp
     desc = _lib.SgnsDesc(n=n, d=dim, walk_length=walks.shape[1], window=int(window), negative=int(negative), epochs=int(epochs),
                          n_walks=walks.shape[0], walks=_lib.ptr(walks), lengths=_lib.ptr(lengths), cum_table=_lib.ptr(d_cum),
                          sample_int=_lib.ptr(d_keep), cum_last=int(cum_table[-1]), alpha=float(alpha), min_alpha=float(min_alpha),
-                         seed=int(seed) & (2 ** 64 - 1), concurrency=int(concurrency))
+                         seed=_lib.seed64(seed), concurrency=int(concurrency))
     for ep in range(int(epochs)):
         _lib.check(lib.gss_sgns_epoch(desc, ep, _lib.ptr(syn0), _lib.ptr(syn1), stream), "gss_sgns_epoch")
     return syn0, syn1

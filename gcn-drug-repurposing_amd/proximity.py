@@ -209,7 +209,7 @@ class ProximityEngine:
         nodes = torch.full((len(sets), R, max_size), -1, dtype=torch.int32, device=self._dev)
         sizes = torch.empty((len(sets), R), dtype=torch.int32, device=self._dev)
         _lib.check(self.lib.gss_prox_random_sets(self._h, side, len(sets), _lib.ptr(d_ptr), _lib.ptr(d_flat), max_size, _lib.ptr(node_bin),
-                                                 _lib.ptr(bin_ptr), _lib.ptr(bin_nodes), n_random, seed & (2 ** 64 - 1), _lib.ptr(nodes),
+                                                 _lib.ptr(bin_ptr), _lib.ptr(bin_nodes), n_random, _lib.seed64(seed), _lib.ptr(nodes),
                                                  _lib.ptr(sizes), _lib.current_stream()), "gss_prox_random_sets")
         return nodes, sizes
 

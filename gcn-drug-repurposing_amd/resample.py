@@ -83,7 +83,7 @@ def resample_stats(values, mode, seed, count, first=0, device="cuda"):
         f = 0
         while True:      # at least one call: the refusals are the kernel's own, whatever the count
             c = min(step, count - f) if count >= 0 else count
-            _lib.check(lib.gss_resample_stats(v.data_ptr(), ld, S, n, mode, int(seed) & (2 ** 64 - 1), first + f, c, buf.data_ptr(),
+            _lib.check(lib.gss_resample_stats(v.data_ptr(), ld, S, n, mode, _lib.seed64(seed), first + f, c, buf.data_ptr(),
                                               _lib.current_stream()), "gss_resample_stats")
             if c > 0:
                 out[f:f + c] = buf[:c].cpu().numpy()

@@ -1,8 +1,7 @@
 """The host restatement of csrc/class_cohesion.hip (include/gssgcn.h), shared by test_class_cohesion.py (CPU) and the
 GPU tests.  Plain numpy:
-  permutation   pi_s = 0 .. n - 1 sorted by (rng_key(seed, 9, s, i, 0), i) -- the keys of counter_rng.h as node2vec_mirror.py states them;
   fsum_*        every sum formed with math.fsum (correctly rounded): what the kernels' sums are held to, within gamma(K - 1) * T;
-  ordered_*     the kernels' own order of additions, term by term in IEEE fp64: what their bits are.
+  ordered_*     the kernels' own order of additions (perm_null_mirror.ordered_row_sum per row), term by term in IEEE fp64: what their bits are.
 Distances are non-negative wherever these are used."""
 from __future__ import annotations
 
@@ -10,21 +9,13 @@ import math
 
 import numpy as np
 
-from node2vec_mirror import rng_key
+from perm_null_mirror import gamma, ordered_row_sum, permutation as tagged_permutation  # noqa: F401
 
 TAG_CLASS_PERM = 9
-U = 2.0 ** -53
-
-
-def gamma(k):
-    """Higham's gamma_k = k u / (1 - k u): the relative bound on a sum of k + 1 non-negative terms added in any order"""
-    return k * U / (1 - k * U)
 
 
 def permutation(seed, s, n):
-    i = np.arange(n, dtype=np.uint64)
-    key = rng_key(seed, TAG_CLASS_PERM, np.uint64(s), i, 0)
-    return np.lexsort((i, key)).astype(np.int32)
+    return tagged_permutation(seed, TAG_CLASS_PERM, s, n)
 
 
 def pair_terms(D, a, m=None):
@@ -41,19 +32,6 @@ def fsum_prefixes(D, a, sizes):
     """T(m) of the list's prefix for every m in sizes (ascending), each the correctly rounded sum of its terms"""
     terms = pair_terms(D, a, max(sizes))
     return np.array([math.fsum(terms[:m * (m - 1) // 2]) for m in sizes])
-
-
-def ordered_row_sum(row_terms):
-    """r_j in the kernel's order: lane l adds the terms l, l + 64, ... ascending from +0.0; the butterfly p[l] += p[l ^ o], o = 32 .. 1"""
-    t = np.zeros(-(-len(row_terms) // 64) * 64)
-    t[:len(row_terms)] = row_terms
-    p = np.zeros(64)
-    for chunk in t.reshape(-1, 64):
-        p = p + chunk            # a lane beyond the row's end adds nothing: + 0.0 leaves a non-negative partial sum as it is
-    lanes = np.arange(64)
-    for o in (32, 16, 8, 4, 2, 1):
-        p = p + p[lanes ^ o]
-    return float(p[0])
 
 
 def ordered_prefixes(D, a, sizes):

@@ -3,7 +3,6 @@ Plain numpy and Python floats (IEEE fp64, one rounding per operation):
   order         pos[u] = the place of u in np.argsort(-x[universe], kind="stable"), w = |x[universe]|; a NaN flags the column;
   es_peak       the enrichment score and its peak of a set of places, operation by operation as the header states it;
   exact_walk    the same score as the extreme of the running sum over all M places, in exact rationals: what es_peak is held to;
-  permutation   pi_s = the places sorted by (rng_key(seed, 13, s, i, 0), i) -- the keys of counter_rng.h as node2vec_mirror.py states them;
   stats         n_same, p, nes, q and the leading edge of enrich.enrichment_stats, restated."""
 from __future__ import annotations
 
@@ -11,6 +10,7 @@ from fractions import Fraction
 
 import numpy as np
 
+import perm_null_mirror
 from node2vec_mirror import rng_key
 
 TAG_ENRICH_PERM = 13
@@ -73,9 +73,7 @@ def exact_walk(pos, w, members, weighted=True):
 
 
 def permutation(seed, s, M):
-    i = np.arange(M, dtype=np.uint64)
-    key = rng_key(seed, TAG_ENRICH_PERM, np.uint64(s), i, 0)
-    return np.lexsort((i, key)).astype(np.int32)
+    return perm_null_mirror.permutation(seed, TAG_ENRICH_PERM, s, M)
 
 
 def first_threshold_count(seed, s, M, kmax):

@@ -1,7 +1,6 @@
 """The host restatement of csrc/matrix_mantel.hip and of mantel.standardise_pairs (include/gssgcn.h), shared by
 test_mantel.py (CPU) and the GPU tests.  Plain numpy:
-  permutation         pi_s = 0 .. n - 1 sorted by (rng_key(seed, 12, s, i, 0), i) -- the keys of counter_rng.h as node2vec_mirror.py states them;
-  ordered_cross_sum   the kernel's own additions, term by term in IEEE fp64: what its bits are.  Terms are signed;
+  ordered_cross_sum   the kernel's own additions (perm_null_mirror.ordered_row_sum per row), term by term in IEEE fp64; terms are signed;
   fsum_cross_sum      the correctly rounded sum (math.fsum) of the same rounded products;
   standardised        the pair values (or their average-tie ranks) centred and scaled to unit norm, as a symmetric matrix."""
 from __future__ import annotations
@@ -10,42 +9,19 @@ import math
 
 import numpy as np
 
-from node2vec_mirror import rng_key
+from perm_null_mirror import gamma, ordered_row_sum, permutation as tagged_permutation  # noqa: F401
 
 TAG_MANTEL_PERM = 12
-U = 2.0 ** -53
-
-
-def gamma(k):
-    """Higham's gamma_k = k u / (1 - k u): |computed sum - exact sum| <= gamma_{k-1} * sum |terms| for k terms added in any order"""
-    return k * U / (1 - k * U)
 
 
 def permutation(seed, s, n):
-    i = np.arange(n, dtype=np.uint64)
-    key = rng_key(seed, TAG_MANTEL_PERM, np.uint64(s), i, 0)
-    return np.lexsort((i, key)).astype(np.int32)
+    return tagged_permutation(seed, TAG_MANTEL_PERM, s, n)
 
 
 def row_terms(A, B, pi, j):
     """the rounded products a[j][i] * b[pi(j)][pi(i)], i < j"""
     pi = np.asarray(pi, dtype=np.int64)
     return A[j, :j] * B[pi[j], pi[:j]]
-
-
-def ordered_row_sum(terms):
-    """r_j in the kernel's order: lane l adds the terms l, l + 64, ... ascending from +0.0 -- a lane without a term keeps its +0.0 --, then
-    the butterfly p[l] = p[l] + p[l ^ o], o = 32 .. 1.  A partial sum that starts at +0.0 never becomes -0.0, so the padding's + 0.0 changes
-    no bit"""
-    t = np.zeros(-(-len(terms) // 64) * 64)
-    t[:len(terms)] = terms
-    p = np.zeros(64)
-    for chunk in t.reshape(-1, 64):
-        p = p + chunk
-    lanes = np.arange(64)
-    for o in (32, 16, 8, 4, 2, 1):
-        p = p + p[lanes ^ o]
-    return float(p[0])
 
 
 def ordered_cross_sum(A, B, pi=None):
