@@ -4,7 +4,8 @@
 //   apsp_kernel       all-pairs hop distances as a uint8 N x N matrix: one workgroup per source, the source's level bytes in
 //                     LDS, level-synchronous top-down BFS over the symmetric CSR (each frontier node's row is read once);
 //   random_sets       one thread per (set, sample): the degree-matched random set of the toolbox (a draw from each member's
-//                     degree bin, up to 20 redraws while the draw is already taken), compacted and sorted ascending;
+//                     degree bin, up to 20 redraws while the draw is already taken), compacted and sorted ascending; behind
+//                     gss_prox_random_sets and, without a handle, gss_random_sets (set_modules.py draws the same sets from it);
 //   set_stats         one wave per (set, sample): the inner closest mean (separation's d_AA) and the tied centres (center);
 //   score_kernel      one wave per (pair, sample): all five measures from one pass over the T' x S' block of D;
 //   stats_kernel      one thread per (pair, measure): mean / population sd over the samples in ascending order, z, pval.
@@ -299,6 +300,40 @@ int check_sets(const char *what, const gss_prox_sets *s, int32_t n_samples) {
   return GSS_OK;
 }
 
+// gss_prox_random_sets and gss_random_sets: the checks, the launch and the read-back of the status word `flag` (device), in `who`'s name
+int random_sets(const char *who, int32_t n, int32_t *flag, int32_t side, int32_t n_sets, const int32_t *set_ptr, const int32_t *set_nodes,
+                int32_t max_size, const int32_t *node_bin, const int32_t *bin_ptr, const int32_t *bin_nodes, int32_t n_random, uint64_t seed,
+                int32_t *out_nodes, int32_t *out_size, void *stream) {
+  GSS_REQUIRE(side == 0 || side == 1, "%s: side=%d must be 0 (from) or 1 (to)", who, side);
+  GSS_REQUIRE(n_sets >= 1 && max_size >= 1 && n_random >= 0, "%s: n_sets=%d max_size=%d n_random=%d", who, n_sets, max_size, n_random);
+  GSS_REQUIRE(set_ptr && set_nodes && node_bin && bin_ptr && bin_nodes && out_nodes && out_size, "%s: null pointer", who);
+  hipStream_t st = as_stream(stream);
+  RandArgs a;
+  a.n = n;
+  a.n_sets = n_sets;
+  a.n_samples = n_random + 1;
+  a.max_size = max_size;
+  a.set_ptr = set_ptr;
+  a.set_nodes = set_nodes;
+  a.node_bin = node_bin;
+  a.bin_ptr = bin_ptr;
+  a.bin_nodes = bin_nodes;
+  a.seed = seed;
+  a.tag = side == 0 ? kRngProxFrom : kRngProxTo;
+  a.out_nodes = out_nodes;
+  a.out_size = out_size;
+  a.flag = flag;
+  GSS_HIP(hipMemsetAsync(a.flag, 0, sizeof(int32_t), st));
+  const int64_t units = (int64_t)n_sets * a.n_samples;
+  random_sets_kernel<<<ceil_div(units, 256), 256, 0, st>>>(a);
+  GSS_LAUNCH_CHECK("random_sets_kernel");
+  int32_t h = 0;
+  if (int rc = read_back(&h, a.flag, sizeof(int32_t), st)) return rc;
+  GSS_REQUIRE(!(h & 1), "%s: a set member is not a node index in [0, %d)", who, n);
+  GSS_REQUIRE(!(h & 2), "%s: a set has more than max_size=%d members", who, max_size);
+  return GSS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -336,35 +371,18 @@ int gss_prox_random_sets(gss_prox *p, int32_t side, int32_t n_sets, const int32_
                          const int32_t *node_bin, const int32_t *bin_ptr, const int32_t *bin_nodes, int32_t n_random, uint64_t seed,
                          int32_t *out_nodes, int32_t *out_size, void *stream) {
   GSS_REQUIRE(p, "prox_random_sets: null handle");
-  GSS_REQUIRE(side == 0 || side == 1, "prox_random_sets: side=%d must be 0 (from) or 1 (to)", side);
-  GSS_REQUIRE(n_sets >= 1 && max_size >= 1 && n_random >= 0, "prox_random_sets: n_sets=%d max_size=%d n_random=%d", n_sets, max_size,
-              n_random);
-  GSS_REQUIRE(set_ptr && set_nodes && node_bin && bin_ptr && bin_nodes && out_nodes && out_size, "prox_random_sets: null pointer");
-  hipStream_t st = as_stream(stream);
-  RandArgs a;
-  a.n = p->n;
-  a.n_sets = n_sets;
-  a.n_samples = n_random + 1;
-  a.max_size = max_size;
-  a.set_ptr = set_ptr;
-  a.set_nodes = set_nodes;
-  a.node_bin = node_bin;
-  a.bin_ptr = bin_ptr;
-  a.bin_nodes = bin_nodes;
-  a.seed = seed;
-  a.tag = side == 0 ? kRngProxFrom : kRngProxTo;
-  a.out_nodes = out_nodes;
-  a.out_size = out_size;
-  a.flag = p->flag.p;
-  GSS_HIP(hipMemsetAsync(a.flag, 0, sizeof(int32_t), st));
-  const int64_t units = (int64_t)n_sets * a.n_samples;
-  random_sets_kernel<<<ceil_div(units, 256), 256, 0, st>>>(a);
-  GSS_LAUNCH_CHECK("random_sets_kernel");
-  int32_t flag = 0;
-  if (int rc = read_back(&flag, a.flag, sizeof(int32_t), st)) return rc;
-  GSS_REQUIRE(!(flag & 1), "prox_random_sets: a set member is not a node index in [0, %d)", p->n);
-  GSS_REQUIRE(!(flag & 2), "prox_random_sets: a set has more than max_size=%d members", max_size);
-  return GSS_OK;
+  return random_sets("prox_random_sets", p->n, p->flag.p, side, n_sets, set_ptr, set_nodes, max_size, node_bin, bin_ptr, bin_nodes, n_random,
+                     seed, out_nodes, out_size, stream);
+}
+
+int gss_random_sets(int32_t n, int32_t side, int32_t n_sets, const int32_t *set_ptr, const int32_t *set_nodes, int32_t max_size,
+                    const int32_t *node_bin, const int32_t *bin_ptr, const int32_t *bin_nodes, int32_t n_random, uint64_t seed,
+                    int32_t *out_nodes, int32_t *out_size, void *stream) {
+  GSS_REQUIRE(n >= 1, "random_sets: n=%d must be >= 1", n);
+  DeviceBuf<int32_t> flag;
+  if (int rc = flag.alloc("random_sets", sizeof(int32_t))) return rc;
+  return random_sets("random_sets", n, flag.p, side, n_sets, set_ptr, set_nodes, max_size, node_bin, bin_ptr, bin_nodes, n_random, seed,
+                     out_nodes, out_size, stream);
 }
 
 int gss_prox_set_stats(gss_prox *p, int32_t n_sets, int32_t n_samples, int32_t max_size, const int32_t *nodes, const int32_t *sizes,

@@ -152,6 +152,27 @@ def bin_tables(bins, n):
     return node_bin, bin_ptr, np.concatenate(bins).astype(np.int32)
 
 
+def random_set_table(call, what, n, dev, node_sets, side, n_random, seed, bins):
+    """the set table of `node_sets` (sample 0 = the set, samples 1.. its degree-matched random sets) on device `dev`, by `call`:
+    gss_prox_random_sets behind its handle or gss_random_sets behind n, both taking (side, n_sets, set_ptr, ...) from there on
+    -> (nodes [n_sets, R, max_size], sizes [n_sets, R]) device int32"""
+    import torch
+    from . import _lib
+    sets = [np.asarray(s, np.int32) for s in node_sets]
+    max_size = max(1, max(len(s) for s in sets))
+    ptr = np.zeros(len(sets) + 1, np.int32)
+    ptr[1:] = np.cumsum([len(s) for s in sets])
+    flat = np.concatenate(sets + [np.zeros(1, np.int32)]).astype(np.int32)
+    node_bin, bin_ptr, bin_nodes = (torch.from_numpy(x).to(dev) for x in bin_tables(bins, n))
+    d_ptr, d_flat = torch.from_numpy(ptr).to(dev), torch.from_numpy(flat).to(dev)
+    R = n_random + 1
+    nodes = torch.full((len(sets), R, max_size), -1, dtype=torch.int32, device=dev)
+    sizes = torch.empty((len(sets), R), dtype=torch.int32, device=dev)
+    _lib.check(call(side, len(sets), _lib.ptr(d_ptr), _lib.ptr(d_flat), max_size, _lib.ptr(node_bin), _lib.ptr(bin_ptr), _lib.ptr(bin_nodes),
+                    n_random, _lib.seed64(seed), _lib.ptr(nodes), _lib.ptr(sizes), _lib.current_stream()), what)
+    return nodes, sizes
+
+
 # ---- the device engine --------------------------------------------------------------------------------------------------------------
 
 class ProximityEngine:
@@ -196,22 +217,8 @@ class ProximityEngine:
 
     def set_table(self, node_sets, side, n_random, seed, bins):
         """random sets of every set (sample 0 = the set) -> (nodes [n_sets, R, max_size], sizes [n_sets, R]) device int32"""
-        from . import _lib
-        torch = self._torch
-        sets = [np.asarray(s, np.int32) for s in node_sets]
-        max_size = max(1, max(len(s) for s in sets))
-        ptr = np.zeros(len(sets) + 1, np.int32)
-        ptr[1:] = np.cumsum([len(s) for s in sets])
-        flat = np.concatenate(sets + [np.zeros(1, np.int32)]).astype(np.int32)
-        node_bin, bin_ptr, bin_nodes = (torch.from_numpy(x).to(self._dev) for x in bin_tables(bins, self.net.n))
-        d_ptr, d_flat = torch.from_numpy(ptr).to(self._dev), torch.from_numpy(flat).to(self._dev)
-        R = n_random + 1
-        nodes = torch.full((len(sets), R, max_size), -1, dtype=torch.int32, device=self._dev)
-        sizes = torch.empty((len(sets), R), dtype=torch.int32, device=self._dev)
-        _lib.check(self.lib.gss_prox_random_sets(self._h, side, len(sets), _lib.ptr(d_ptr), _lib.ptr(d_flat), max_size, _lib.ptr(node_bin),
-                                                 _lib.ptr(bin_ptr), _lib.ptr(bin_nodes), n_random, _lib.seed64(seed), _lib.ptr(nodes),
-                                                 _lib.ptr(sizes), _lib.current_stream()), "gss_prox_random_sets")
-        return nodes, sizes
+        return random_set_table(lambda *args: self.lib.gss_prox_random_sets(self._h, *args), "gss_prox_random_sets", self.net.n, self._dev,
+                                node_sets, side, n_random, seed, bins)
 
     def set_stats(self, nodes, sizes, centres=True):
         from . import _lib

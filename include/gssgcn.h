@@ -428,6 +428,28 @@ int gss_prox_set_stats(gss_prox *p, int32_t n_sets, int32_t n_samples, int32_t m
 int gss_prox_score(gss_prox *p, const gss_prox_sets *from, const gss_prox_sets *to, int32_t n_samples, int64_t n_pairs,
                    const int32_t *pair_from, const int32_t *pair_to, int32_t measures, double *out, void *stream);
 
+/* ---- module significance of node sets: the largest connected component of the induced subgraph against degree-matched random sets
+ * (Menche et al. 2015; the check behind the *.lcc companion of a disease-gene file).  DESIGN.md section 9.17.
+ * gss_random_sets: gss_prox_random_sets without a handle -- the same kernel, keys, table and bits for the same arguments, n being the
+ * number of nodes (>= 1); its status word is allocated for the call.  Refusals as there, in the name random_sets.  Synchronises the stream.
+ * gss_set_components: a unit is one row of a set table (nodes [n_units][max_size], sizes [n_units], device): its members are
+ * nodes[u * max_size .. + sizes[u]), strictly ascending node indices in [0, n); entries past the size are never read.  Two members are
+ * adjacent when one appears in the other's row of the CSR (rowptr [n + 1], col, device, columns ascending; the CSR gss_prox_create takes:
+ * symmetric, which the caller guarantees and nothing checks).  A stored self loop is ignored.  Per unit: lcc = the size of the largest
+ * component of the induced subgraph (0 for an empty unit), n_comp = the number of components, n_edges = the number of hits (i, j) with
+ * j > i found in row i (the induced edges of a symmetric CSR) and, when label is not NULL ([n_units][max_size]), label[u][i] = the
+ * position within the unit of the smallest member of i's component; entries past the size are left as the caller had them.  All
+ * integers, exact: the same between runs and for any split of the units into calls.  n >= 1, n_units >= 1, 1 <= max_size <= 4096 (a
+ * unit's members and parents live in LDS), n_units * max_size < 2^40.  Refused by name (GSS_EINVAL): a null pointer, a size outside
+ * [0, max_size], a member outside [0, n), members not strictly ascending -- the last three found on the device (no row of such a unit
+ * is read; the outputs are then undefined).  Synchronises the stream (reads the status word back). */
+int gss_random_sets(int32_t n, int32_t side, int32_t n_sets, const int32_t *set_ptr, const int32_t *set_nodes, int32_t max_size,
+                    const int32_t *node_bin, const int32_t *bin_ptr, const int32_t *bin_nodes, int32_t n_random, uint64_t seed,
+                    int32_t *out_nodes, int32_t *out_size, void *stream);
+int gss_set_components(int32_t n, const int32_t *rowptr, const int32_t *col, int64_t n_units, int32_t max_size,
+                       const int32_t *nodes, const int32_t *sizes, int32_t *lcc, int32_t *n_comp, int32_t *n_edges,
+                       int32_t *label /* NULL or [n_units][max_size] */, void *stream);
+
 /* ---- shortest-path trees toward up to 64 targets per pass (predict_drug.py:268-273, run_covid.py:310-319: one networkx
  * shortest_path per table row; here one search toward each target answers every row) ------------------------------------------
  * Directed graph as a CSR: rowptr [n + 1], col [nnz], the columns of every row ascending (MsiGraph.to_csr, embio's edgelist reader).
