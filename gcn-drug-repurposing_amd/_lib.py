@@ -231,6 +231,8 @@ SIGNATURES = {
     "gss_wgrad_reduce_adam": (C.c_int, [_I32, _P, _I32, _I32, _P * 4, _P * 4, _P * 4, _P * 4, _I32, _F, _F, _F, _F, _P, _P, _P, _P, _I32, _P]),
     "gss_adam_step4": (C.c_int, [_P * 4, _P * 4, _P * 4, _P * 4, _I64 * 4, _I32, _F, _F, _F, _F, _P, _P, _I32, _P, _P, _I32, _P]),
     "gss_transpose2": (C.c_int, [_I32, _P, _P, _P, _P, _P]),
+    # for tests: the row-norm backward with the batch-position map's side write (tests/test_gpu_rownorm.py)
+    "gss_rownorm_elu_bwd_ex": (C.c_int, [_I32, _P, _P, _I32, _P, _P, _P, _F, _P, _P, _P, _P]),
     # for tests: the halo bookkeeping and the batch preparation of a sharded plan (tests/test_gpu_halo_ops.py)
     "gss_pack_rows": (C.c_int, [_I32, _P, _P, _I64, _P, _P]),
     "gss_unpack_rows": (C.c_int, [_I32, _P, _P, _I64, _P, _P]),

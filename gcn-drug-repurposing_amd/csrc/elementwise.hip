@@ -660,6 +660,11 @@ int gss_adam_step4(float *const param[4], const float *const grad[4], float *con
 int gss_transpose2(int32_t dim, const float *a, const float *b, float *at, float *bt, void *stream) {
   return transpose2(dim, a, b, at, bt, stream);
 }
+// for tests (tests/test_gpu_rownorm.py): the row-norm backward with the batch-position map's side write, as the plan calls it
+int gss_rownorm_elu_bwd_ex(int32_t d, const float *de_b, const int32_t *idx, int32_t b, const float *e, const float *inv_den,
+                           const float *p, float c, float *dx_b, float *dp_b, int32_t *pos_set, void *stream) {
+  return rownorm_elu_bwd(d, de_b, idx, b, e, inv_den, p, c, dx_b, dp_b, pos_set, stream);
+}
 // for tests (tests/test_gpu_halo_ops.py): the halo bookkeeping and the batch preparation of a sharded plan, as the plan calls them
 int gss_pack_rows(int32_t d, const float *src, const int32_t *rows, int64_t n, float *out, void *stream) {
   return pack_rows(d, src, rows, n, out, stream);

@@ -145,6 +145,8 @@ int dense_fwd_norm(int32_t n, int32_t d, const float *ax, const float *am, const
                                                              // where that is >= 0 (the batch-position map: E_B without a gather launch)
                    bool acc_in_p = false);                   // as dense_fwd
 float *loss_workspace_e_b(int32_t d, int32_t b, void *ws);   // where loss_gather_rows* would put E_B for a batch of b rows
+// rows (nullable): tile row r is written to output row rows[r].  Entries must be unique, valid row indices: rows[r] is used unchecked and
+// a negative entry is NOT skipped (the plan passes clamped rows -- rloc -- or the ids of a one-GPU plan)
 int dense_bwd_input(int32_t n, int32_t d, const float *dp, const float *w1t, const float *w2t, const int32_t *rows,
                     float *g_ax, float *g_am, void *stream);
 size_t wgrad_workspace_bytes(int32_t n, int32_t d);

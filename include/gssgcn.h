@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define GSS_ABI_VERSION 25  /* 25: the mean and the median of bootstrap resamples and sign flips of series, behind intervals and paired tests of the per-indication metrics -- gss_resample_stats; 24: sums of a distance matrix over the pairs of listed sets and of the prefixes of seeded random permutations, the statistic and the null of ATC class coherence -- gss_pair_sums_lists, gss_pair_sums_random; 23: entry points for tests of the halo bookkeeping and the batch preparation of a sharded plan -- gss_pack_rows, gss_unpack_rows, gss_halo_need_mark, gss_send_slot_bits, gss_bits_clear, gss_bits_set_list, gss_bits_compact, gss_bits_compact_scratch_bytes, gss_batch_prepare, gss_scatter_add_rows_ex, gss_spmm_prep_side; 22: two forward products in one launch and layer 1 one pass ahead -- gss_spmm_fwd_pair, gss_plan_l1_ahead, plan option "l1_ahead"; 21: entry points for tests of the dense half of a plan's step -- gss_dense_fwd_rows, gss_dense_fwd_first, gss_dense_fwd_split_available, gss_dense_fwd_norm, gss_rownorm_fwd_rows, gss_wgrad_slices, gss_wgrad_slices_max, gss_wgrad_partial, gss_wgrad_partial_pair, gss_wgrad_reduce, gss_wgrad_reduce_adam, gss_adam_step4, gss_transpose2; 20: entry points for tests of the loss stages of a plan's step -- gss_loss_step, gss_loss_slab_sweep, gss_loss_workspace_bytes_parts, gss_loss_gather_rows, gss_loss_gather_rows_mapped, gss_loss_gather_batch; loss_step refuses input-gradient weights at widths outside {64, 128, 256}; 19: exact typed top-k selection of listed profile columns and set overlap between selections -- gss_profile_topk, gss_profile_topk_workspace_bytes, gss_topk_overlap; 18: exact average-tie ranks of listed profile columns, the transform behind the spearman distance -- gss_profile_rank, gss_profile_rank_workspace_bytes; 17: gene knock-outs per column of the diffusion profiles -- gss_ppr_set_knockout; distances of listed column pairs of the profile matrix -- gss_profile_dist_pairs, gss_profile_dist_pairs_workspace_bytes; 16: ROC-AUC, average precision and hits@k per row in one launch -- gss_rank_metrics_rows, gss_rank_metrics_workspace_bytes; 15: entry points for tests of the row-sparse SpMM modes -- gss_spmm_bwd1_sparse_ex, gss_spmm_bwd2_sparse_res, gss_spmm_filtered, gss_mark_rows_and_neighbours, gss_batch_bits, gss_bits_fill; 14:indication x drug scores from the embedding tensor -- gss_embedding_scores; 13: pairwise distances between diffusion profiles -- gss_profile_dist; 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows.  gss_matrix_cross_sums, the permuted cross-product sum of two matrices behind Mantel's test, joined under 25 without a new number: an added export breaks no caller; so did gss_profile_order, gss_enrich_lists and gss_enrich_random, the preranked gene-set enrichment of profile columns; and gss_csr_set_job_cols, gss_csr_job_cols and gss_spmm_auto_slices, the job-wide operand row count behind the SpMM's automatic slice count */
+#define GSS_ABI_VERSION 25  /* 25: the mean and the median of bootstrap resamples and sign flips of series, behind intervals and paired tests of the per-indication metrics -- gss_resample_stats; 24: sums of a distance matrix over the pairs of listed sets and of the prefixes of seeded random permutations, the statistic and the null of ATC class coherence -- gss_pair_sums_lists, gss_pair_sums_random; 23: entry points for tests of the halo bookkeeping and the batch preparation of a sharded plan -- gss_pack_rows, gss_unpack_rows, gss_halo_need_mark, gss_send_slot_bits, gss_bits_clear, gss_bits_set_list, gss_bits_compact, gss_bits_compact_scratch_bytes, gss_batch_prepare, gss_scatter_add_rows_ex, gss_spmm_prep_side; 22: two forward products in one launch and layer 1 one pass ahead -- gss_spmm_fwd_pair, gss_plan_l1_ahead, plan option "l1_ahead"; 21: entry points for tests of the dense half of a plan's step -- gss_dense_fwd_rows, gss_dense_fwd_first, gss_dense_fwd_split_available, gss_dense_fwd_norm, gss_rownorm_fwd_rows, gss_wgrad_slices, gss_wgrad_slices_max, gss_wgrad_partial, gss_wgrad_partial_pair, gss_wgrad_reduce, gss_wgrad_reduce_adam, gss_adam_step4, gss_transpose2; 20: entry points for tests of the loss stages of a plan's step -- gss_loss_step, gss_loss_slab_sweep, gss_loss_workspace_bytes_parts, gss_loss_gather_rows, gss_loss_gather_rows_mapped, gss_loss_gather_batch; loss_step refuses input-gradient weights at widths outside {64, 128, 256}; 19: exact typed top-k selection of listed profile columns and set overlap between selections -- gss_profile_topk, gss_profile_topk_workspace_bytes, gss_topk_overlap; 18: exact average-tie ranks of listed profile columns, the transform behind the spearman distance -- gss_profile_rank, gss_profile_rank_workspace_bytes; 17: gene knock-outs per column of the diffusion profiles -- gss_ppr_set_knockout; distances of listed column pairs of the profile matrix -- gss_profile_dist_pairs, gss_profile_dist_pairs_workspace_bytes; 16: ROC-AUC, average precision and hits@k per row in one launch -- gss_rank_metrics_rows, gss_rank_metrics_workspace_bytes; 15: entry points for tests of the row-sparse SpMM modes -- gss_spmm_bwd1_sparse_ex, gss_spmm_bwd2_sparse_res, gss_spmm_filtered, gss_mark_rows_and_neighbours, gss_batch_bits, gss_bits_fill; 14:indication x drug scores from the embedding tensor -- gss_embedding_scores; 13: pairwise distances between diffusion profiles -- gss_profile_dist; 12: shortest-path counts, best paths and the nodes between pairs -- gss_paths_count, gss_paths_between, gss_paths_between_fill; 11: batched ROC-AUC per row -- gss_auc_rows; 10: shortest-path trees toward up to 64 targets per pass -- gss_paths_*; 9: drug-disease network proximity -- gss_prox_*; 8: the debug entry point that set a wall-clock stamp buffer for the projection kernels is gone; 7: node2vec input embeddings -- gss_walk_prefix, gss_node2vec_walks, gss_sgns_*; 6 (round 6): gss_source_hash; the access-shape knobs whose sweeps said "default holds" twice are gone; 5 (round 5): gss_rowsum_check, gss_plan_sync_stats, gss_comm_local_mode / gss_comm_local_log, gss_csr_giant_rows; 4 (round 4): gss_shard_desc gained a_loc_t, gss_plan_comm_stats, gss_knn_topk_rows.  gss_matrix_cross_sums, the permuted cross-product sum of two matrices behind Mantel's test, joined under 25 without a new number: an added export breaks no caller; so did gss_profile_order, gss_enrich_lists and gss_enrich_random, the preranked gene-set enrichment of profile columns; and gss_csr_set_job_cols, gss_csr_job_cols and gss_spmm_auto_slices, the job-wide operand row count behind the SpMM's automatic slice count; and gss_rownorm_elu_bwd_ex, the row-norm backward with its pos_set side write, for tests */
 
 #define GSS_OK 0
 #define GSS_EINVAL (-22)   /* bad argument (shape, null pointer, unsupported d) */
@@ -150,7 +150,10 @@ int gss_dense_fwd(int32_t n, int32_t d, const float *ax, const float *am, const 
 
 /* input gradients of the two Linear layers: g_ax = dp W1, g_am = dp W2 (w1t/w2t are the TRANSPOSED
  * weights, [in][out]).  If rows != NULL, row r of the compact [n][d] input is written to row rows[r]
- * of the outputs (scatter of batch-row gradients into zeroed [N][d] buffers). */
+ * of the outputs (scatter of batch-row gradients into zeroed [N][d] buffers).  rows[0..n) must be UNIQUE,
+ * VALID row indices of g_ax / g_am: the kernel uses rows[r] unchecked, and a negative entry is NOT skipped
+ * (unlike gss_scatter_add_rows and the forward row lists) -- it would be written in front of the buffers.
+ * Rows that are not listed, and rows behind n without a list, are not written. */
 int gss_dense_bwd_input(int32_t n, int32_t d, const float *dp, const float *w1t, const float *w2t,
                         const int32_t *rows, float *g_ax, float *g_am, void *stream);
 
@@ -179,7 +182,8 @@ int gss_loss_fwd_bwd(int32_t n, int32_t d, const float *e, const int32_t *idx, i
                      float alpha, float *loss_out, float *de_b, void *ws, void *stream);
 
 /* backward of K5 + K4 on the batch rows: dx_b = (de_b - e_b (e_b . de_b)) * inv_den[idx];
- * dp_b = c * dx_b (.) elu'(p[idx]).  All [B][d] compact. */
+ * dp_b = c * dx_b (.) elu'(p[idx]).  All [B][d] compact.  idx[0..b) must be valid node rows of e / inv_den /
+ * p: idx[r] is read unchecked, a negative entry is NOT skipped. */
 int gss_rownorm_elu_bwd(int32_t d, const float *de_b, const int32_t *idx, int32_t b, const float *e,
                         const float *inv_den, const float *p, float c, float *dx_b, float *dp_b, void *stream);
 
@@ -1187,6 +1191,13 @@ int gss_adam_step4(float *const param[4], const float *const grad[4], float *con
                    int32_t step, float lr, float beta1, float beta2, float eps, float *w1t, float *w2t, int32_t dim, int32_t *pos_clear,
                    const int32_t *ids, int32_t b, void *stream);
 int gss_transpose2(int32_t dim, const float *a, const float *b, float *at, float *bt, void *stream);
+
+/* ---- FOR TESTS: the row-norm backward as a plan calls it (tests/test_gpu_rownorm.py) ---------------------------------------------
+ * gss_rownorm_elu_bwd with the side write of the batch-sparse backward hop's key: pos_set (nullable, int32 per node row) gets
+ * pos_set[idx[r]] = r for every r < b and is written nowhere else; dx_b and dp_b get the bits of gss_rownorm_elu_bwd.  idx as there:
+ * unique, valid node rows, read unchecked.  Nothing in the product calls it. */
+int gss_rownorm_elu_bwd_ex(int32_t d, const float *de_b, const int32_t *idx, int32_t b, const float *e, const float *inv_den,
+                           const float *p, float c, float *dx_b, float *dp_b, int32_t *pos_set, void *stream);
 
 /* ---- FOR TESTS: the halo bookkeeping and the batch preparation of a sharded plan, launcher by launcher ---------------------------
  * A sharded plan's lazy halo and its batch preparation are integers, bitmaps and row copies in csrc/elementwise.hip (and one copy of the

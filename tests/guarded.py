@@ -1,6 +1,9 @@
-"""Guarded outputs of the op-by-op GPU tests (tests/test_gpu_loss_step.py, tests/test_gpu_dense_step.py) -- TEST INFRASTRUCTURE.  Every
+"""Guarded outputs of the op-by-op GPU tests (tests/test_gpu_loss_step.py, tests/test_gpu_dense_step.py,
+tests/test_gpu_input_grad.py, tests/test_gpu_rownorm.py) -- TEST INFRASTRUCTURE.  Every
 output of a launch sits between canary elements and starts as a NaN of a recognisable payload, so that a test can tell "written",
 "not written" and "written outside the buffer" apart; a workspace is exactly as long as the library says, in front of canary bytes."""
+import contextlib
+
 import numpy as np
 import torch
 
@@ -9,6 +12,19 @@ CANARY = 0x7FC0BEEF                  # around every output
 PAD = 64                             # canary elements on each side (256 bytes: the output keeps its 16-byte alignment)
 WS_BYTE = 0xA5
 WS_TAIL = 4096
+KNOB_DEFAULTS = {"gemm_variant": 2, "gemm_ws": -1, "wgrad_wgs": 256}     # the kernel-selection knobs of csrc/dense.hip
+
+
+@contextlib.contextmanager
+def knobs(G, **values):
+    """kernel-selection knobs for the launches inside; back to their defaults whatever happens"""
+    try:
+        for k, v in values.items():
+            G._lib.check(G.lib.gss_debug_set_option(k.encode(), v))
+        yield
+    finally:
+        for k in values:
+            G._lib.check(G.lib.gss_debug_set_option(k.encode(), KNOB_DEFAULTS[k]))
 
 
 def cu(a):

@@ -14,7 +14,6 @@ Every output sits between canary elements and starts as a NaN of a recognisable 
 says so and keep the pre-fill where it says it is not written (rows beyond n, unlisted rows, rows whose list entry is negative, E_B slots
 no member maps to, slices outside [slice0, slice0 + ns)).  No test provokes a fault: every launch that runs gets valid arguments, the
 refusals are refused on the host before any launch."""
-import contextlib
 import ctypes as C
 
 import numpy as np
@@ -23,7 +22,7 @@ import pytest
 import dense_step_cases as K
 import dense_step_mirror as M
 import tolerances as T
-from guarded import PREFILL, Out, bits, close, cu, ptr, written
+from guarded import PREFILL, Out, bits, close, cu, knobs, ptr, written
 
 pytestmark = pytest.mark.gpu
 
@@ -31,7 +30,6 @@ torch = pytest.importorskip("torch")
 
 EINVAL = -22
 POS_FREE = -7                        # a batch-position map entry nobody wrote
-KNOB_DEFAULTS = {"gemm_variant": 2, "gemm_ws": -1, "wgrad_wgs": 256}
 PLAIN = T.DENSE_STEP_PLAIN
 NAMES = ("W1", "b1", "W2", "b2")
 # Adam's default betas AS THE LIBRARY RECEIVES THEM: the ABI carries them as float, and the kernels form 1 - beta from that float, as torch
@@ -55,18 +53,6 @@ def G():
     ns.st = lambda: _lib.current_stream()
     ns.dev = {}
     return ns
-
-
-@contextlib.contextmanager
-def knobs(G, **values):
-    """kernel-selection knobs for the launches inside; back to their defaults whatever happens"""
-    try:
-        for k, v in values.items():
-            G._lib.check(G.lib.gss_debug_set_option(k.encode(), v))
-        yield
-    finally:
-        for k in values:
-            G._lib.check(G.lib.gss_debug_set_option(k.encode(), KNOB_DEFAULTS[k]))
 
 
 def last_error(G):
