@@ -454,6 +454,35 @@ int gss_set_components(int32_t n, const int32_t *rowptr, const int32_t *col, int
                        const int32_t *nodes, const int32_t *sizes, int32_t *lcc, int32_t *n_comp, int32_t *n_edges,
                        int32_t *label /* NULL or [n_units][max_size] */, void *stream);
 
+/* ---- growing a module from seed nodes: DIAMOnD (Ghiassian, Menche and Barabasi 2015), DESIGN.md section 9.18 --------------------------
+ * gss_diamond_grow: a unit is one row of a seed table (seeds [n_units][max_size], sizes [n_units], device): its seed set S is
+ * seeds[u * max_size .. + sizes[u]), strictly ascending node indices in [0, n); entries past the size are never read.  The CSR (rowptr
+ * [n + 1], col, device) is the one gss_set_components takes: symmetric, no self loops, which the caller guarantees; max_deg is the
+ * caller's bound on a row's length, checked on the device.  A unit adds n_add nodes, one per step.  With A the nodes added so far, every
+ * node v outside S and A has ks / ka neighbours in S / A and, all integers, kb' = alpha ks + ka, k' = deg(v) + (alpha - 1) ks,
+ * s' = alpha |S| + |A|, N' = n + (alpha - 1) |S| (the paper's seed weight alpha, kept in s' for every step).  Candidates are the v with
+ * kb' > 0.  Stage 1: of the candidates with the same kb', the one with the smallest (k', v).  Stage 2: of those, the one with the
+ * smallest logp, of two equal the larger kb'; it joins A.  logp = lt0 + log(S) is the log of the hypergeometric tail P(X >= kb'):
+ *   lt0 = (LC(s', kb') + LC(N' - s', k' - kb')) - LC(N', k'),  LC(a, b) = lg[a + 1] - (lg[a - b + 1] + lg[b + 1]),
+ *   S = 1 + sum of term_i, term = 1, for i = kb' .. min(k', s') - 1: term *= double((s' - i)(k' - i)) / double((i + 1)(N' - s' - k' + i + 1)),
+ * in exactly that order: the products in int64, one fp64 division, one multiplication and one addition per i, nothing contracted, no
+ * early exit.  lg (device, fp64 [n_lg]) is the caller's table lg[i] = lgamma(i), n_lg >= n + (alpha - 1) max_size + 2; lg[0] is never
+ * read.  So lt0 and S are the same bits on any IEEE-754 machine and only the one log is the device's.  Where two candidates' logp are
+ * closer than that log's error (different (k', kb') can have tails equal as rationals), the winner is the same between runs but
+ * implementation-defined.
+ * Per unit and step t (all outputs [n_units][n_add], device): node, k = k', kb = kb' (int32) and lt0, S, logp (fp64) of the node
+ * added.  When no candidate is left, this and every later step of the unit are node = -1, k = kb = 0, lt0 = S = logp = 0.
+ * The same bits between runs and for any split of the units into calls; no global atomic but the status word's.
+ * n in [1, 30720] (per node a 32-bit word of counts and a membership bit live in LDS, beside a 4,096-slot table of stage 1's keys: 156 KiB
+ * of the CU's 160), n_units >= 1, 1 <= max_size <= 4096, n_add >= 1, alpha >= 1, alpha max_deg <= 65535 (the counts are 16 bits),
+ * min(alpha max_deg, alpha max_size + n_add - 1) <= 4095 (the largest kb' a step can see has a slot).  Refused by name (GSS_EINVAL): a
+ * null pointer, any of these bounds, a size outside [0, max_size], a seed outside [0, n), seeds not strictly ascending, a row longer
+ * than max_deg -- the last four found on the device (no row of such a unit is walked; the outputs are then undefined).  Synchronises
+ * the stream (reads the status word back). */
+int gss_diamond_grow(int32_t n, const int32_t *rowptr, const int32_t *col, int32_t max_deg, const double *lg, int64_t n_lg,
+                     int64_t n_units, int32_t max_size, const int32_t *seeds, const int32_t *sizes, int32_t n_add, int32_t alpha,
+                     int32_t *node, int32_t *k, int32_t *kb, double *lt0, double *S, double *logp, void *stream);
+
 /* ---- shortest-path trees toward up to 64 targets per pass (predict_drug.py:268-273, run_covid.py:310-319: one networkx
  * shortest_path per table row; here one search toward each target answers every row) ------------------------------------------
  * Directed graph as a CSR: rowptr [n + 1], col [nnz], the columns of every row ascending (MsiGraph.to_csr, embio's edgelist reader).
