@@ -14,6 +14,7 @@
 #include <algorithm>
 
 #include "device_scope.h"
+#include "lds_union_find.h"
 
 namespace gss {
 namespace {
@@ -28,29 +29,6 @@ struct CompArgs {
   const int32_t *rowptr, *col, *nodes, *sizes;
   int32_t *lcc, *n_comp, *n_edges, *label, *flag;
 };
-
-__device__ __forceinline__ int32_t uf_find(volatile int32_t *parent, int32_t x) {
-  // path halving: a non-root's parent is only ever replaced by one of its ancestors, and ancestors stay ancestors (only roots get
-  // hooked), so a racing plain store never detaches anything; parents only decrease, so there are no cycles
-  for (;;) {
-    const int32_t p = parent[x];
-    if (p == x) return x;
-    const int32_t g = parent[p];
-    if (g == p) return p;
-    parent[x] = g;
-    x = g;
-  }
-}
-
-__device__ __forceinline__ void uf_union(int32_t *parent, int32_t a, int32_t b) {
-  for (;;) {
-    a = uf_find(parent, a);
-    b = uf_find(parent, b);
-    if (a == b) return;
-    const int32_t hi = max(a, b), lo = min(a, b);
-    if (atomicCAS(&parent[hi], hi, lo) == hi) return;   // lost: hi was hooked by another lane meanwhile; look again
-  }
-}
 
 __device__ __forceinline__ int ilog2_ceil(int32_t x) { return x <= 1 ? 1 : 32 - __clz(x - 1); }
 

@@ -18,13 +18,15 @@ MAX_SET = 4096                   # members of one set the component kernel holds
 STAT_FIELDS = ("mean", "sd", "z", "p", "q")
 
 
-def null_stats(obs, null, empty=None):
+def null_stats(obs, null, empty=None, real=False):
     """obs [n_sets] and null [n_sets, n_random] integers -> {"mean", "sd", "z", "p", "q": fp64 [n_sets]}: the null's mean (computed once:
     the integer sum divided once) and population sd (ddof = 0) about it, z = (obs - mean) / sd (NaN when sd = 0), the one-sided
     p = (1 + #{r: null_r >= obs}) / (n_random + 1), and Benjamini-Hochberg q over the sets that are not `empty` (bool [n_sets]; those get
-    NaN everywhere and take no part in q)"""
-    obs = np.asarray(obs, np.int64)
-    null = np.asarray(null, np.int64).reshape(len(obs), -1)
+    NaN everywhere and take no part in q).  With `real` the statistic is a ratio of integers (connectors.py's fraction of a set joined)
+    and is taken as fp64 instead"""
+    kind = np.float64 if real else np.int64
+    obs = np.asarray(obs, kind)
+    null = np.asarray(null, kind).reshape(len(obs), -1)
     k = null.shape[1]
     if k < 1:
         raise ValueError("null_stats: the null holds no sample")

@@ -483,6 +483,35 @@ int gss_diamond_grow(int32_t n, const int32_t *rowptr, const int32_t *col, int32
                      int64_t n_units, int32_t max_size, const int32_t *seeds, const int32_t *sizes, int32_t n_add, int32_t alpha,
                      int32_t *node, int32_t *k, int32_t *kb, double *lt0, double *S, double *logp, void *stream);
 
+/* ---- joining a seed set's fragments: the seed connector algorithm (Wang and Loscalzo 2018), DESIGN.md section 9.19 -----------------
+ * gss_seed_connectors: a unit is one row of a seed table (seeds [n_units][max_size], sizes [n_units], device), as gss_diamond_grow
+ * takes it: strictly ascending node indices in [0, n), entries past the size never read.  The CSR (rowptr [n + 1], col, device) is the
+ * one gss_set_components takes: symmetric, no self loops, which the caller guarantees; max_deg is the caller's bound on a row's length,
+ * checked on the device.  With M the seeds and the nodes added so far, and L the size of the largest connected component of the
+ * subgraph M induces, a candidate is a node v outside M with a neighbour in M; tot(v) = 1 + the sum of the sizes of the DISTINCT
+ * components of M that hold a neighbour of v, L'(v) = max(L, tot(v)).  A step adds the candidate with the smallest key
+ * (-L'(v), deg(v), v), deg the length of v's row: the largest new LCC, then the smaller degree, then the smaller node index (the
+ * published algorithm breaks ties at random; this rule stands in for it).  A unit stops when there is no candidate, when the best
+ * L' < L + 2 (a node that adds only itself joins nothing) or after n_add steps.  The new largest component need not contain the old
+ * one.
+ * Per unit and step t (int32 [n_units][n_add], device): node, lcc = L' after the step, merged = the number of components the node
+ * joined, deg = deg(node); steps not taken are node = -1, lcc = merged = deg = 0.  Per unit (int32 [n_units], device): steps = the steps
+ * taken, first_lcc = L of the seeds alone, final_lcc = L at the end (both 0 for an empty unit), seeds_in / added_in = the seeds / added nodes in the final largest component
+ * (of two as large, the one whose smallest member comes first in M).  When label is not NULL ([n_units][max_size + n_add]):
+ * label[u][i], i < size + steps, = the position in M of the smallest member of i's component, M being the seeds in their order and then
+ * the added nodes in the order added (gss_set_components' labels, extended); entries past size + steps are left as the caller had them.
+ * All integers, exact: the same between runs and for any split of the units into calls; no global atomic but the status word's.
+ * n in [1, 30720], n_units >= 1, 1 <= max_size <= 4096, n_add >= 1, max_size + n_add <= 8192, 0 <= max_deg <= 1048575,
+ * n_units * (max_size + n_add) < 2^40.  A unit's state lives in LDS: 4 bytes per node, 4 bytes per member of M and a 4 KiB list,
+ * 4 (n + max_size + n_add) + 4096 bytes per workgroup -- 156 KiB of the CU's 160 at the limits, 75 KiB for n = 13,329, max_size 4,096,
+ * n_add 500.  Refused by name (GSS_EINVAL): a null pointer (but label), any of these bounds, a size outside
+ * [0, max_size], a seed outside [0, n), seeds not strictly ascending, a row longer than max_deg -- the last four found on the device
+ * (no row of such a unit is walked; the outputs are then undefined).  Synchronises the stream (reads the status word back). */
+int gss_seed_connectors(int32_t n, const int32_t *rowptr, const int32_t *col, int32_t max_deg, int64_t n_units, int32_t max_size,
+                        const int32_t *seeds, const int32_t *sizes, int32_t n_add, int32_t *node, int32_t *lcc, int32_t *merged,
+                        int32_t *deg, int32_t *steps, int32_t *first_lcc, int32_t *final_lcc, int32_t *seeds_in, int32_t *added_in,
+                        int32_t *label /* NULL or [n_units][max_size + n_add] */, void *stream);
+
 /* ---- shortest-path trees toward up to 64 targets per pass (predict_drug.py:268-273, run_covid.py:310-319: one networkx
  * shortest_path per table row; here one search toward each target answers every row) ------------------------------------------
  * Directed graph as a CSR: rowptr [n + 1], col [nnz], the columns of every row ascending (MsiGraph.to_csr, embio's edgelist reader).
