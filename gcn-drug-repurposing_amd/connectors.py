@@ -13,7 +13,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from .proximity import ProximityError, degree_bins, random_set_table
+from ._network_engine import NetworkEngine
+from .proximity import ProximityError, degree_bins
 from .set_modules import null_stats
 
 MAX_NODES = 30720                # per node a 32-bit label in LDS
@@ -47,33 +48,12 @@ def table_stats(n, sizes, steps, final_lcc, seeds_in):
             "short": (sizes[:, 1:] < sizes[:, :1]).sum(axis=1)}
 
 
-class ConnectorEngine:
-    """owns the device CSR of `network` (a proximity.Network) and nothing else"""
-
-    def __init__(self, network):
-        import torch
-        from . import _lib
-        self.lib = _lib.load()
-        self.net = network
-        self._torch = torch
-        self._dev = torch.device("cuda")
-        self.max_deg = int(np.diff(network.rowptr).max()) if network.n else 0
-        self._rowptr = torch.from_numpy(network.rowptr).to(self._dev)
-        self._col = torch.from_numpy(network.col if len(network.col) else np.zeros(1, np.int32)).to(self._dev)
-
-    def close(self):
-        self._rowptr = self._col = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
+class ConnectorEngine(NetworkEngine):
+    """the network's device CSR and nothing else"""
 
     def check(self, max_size, n_add):
         """the refusals that need no device, in the engine's words"""
-        if self._rowptr is None:
-            raise ProximityError("grow: the engine is closed")
+        self._open("grow")
         if int(n_add) < 1:
             raise ProximityError(f"n_add={n_add} must be >= 1")
         if not 1 <= self.net.n <= MAX_NODES:
@@ -120,24 +100,15 @@ class ConnectorEngine:
         return out
 
     def seed_table(self, node_sets):
-        """(seeds [n_sets, max_size], sizes [n_sets]) device int32 of a list of node-index arrays (strictly ascending)"""
-        torch = self._torch
-        sets = [np.asarray(s, np.int32).reshape(-1) for s in node_sets]
-        if not sets:
-            raise ProximityError("grow: node_sets must not be empty")
-        max_size = max(1, max(len(s) for s in sets))
-        seeds = np.full((len(sets), max_size), -1, np.int32)
-        for i, s in enumerate(sets):
-            seeds[i, :len(s)] = s
-        return torch.from_numpy(seeds).to(self._dev), torch.from_numpy(np.array([len(s) for s in sets], np.int32)).to(self._dev), sets
+        """(seeds [n_sets, max_size], sizes [n_sets]) device int32 of a list of node-index arrays (strictly ascending), and the arrays"""
+        return self.pack(node_sets)
 
     def grow(self, node_sets, n_add=500):
         """node_sets: a list of node-index arrays (strictly ascending, as Network.node_set returns them) -> {"node", "lcc", "merged", "deg":
         int32 [n_sets, n_add]: per step the connector added, the LCC after it, the components it joined and its degree (node = -1 and
         zeros once a set stopped); "steps", "first_lcc", "final_lcc", "seeds_in", "added_in": int32 [n_sets] (the LCC before and after); "members": per set the seeds and then the
         connectors in the order added; "label": per member the position of the smallest member of its component}"""
-        if self._rowptr is None:
-            raise ProximityError("grow: the engine is closed")
+        self._open("grow")
         seeds, sizes, sets = self.seed_table(node_sets)
         out = self.run(seeds, sizes, n_add, steps_of=np.arange(len(sets)), labels=True)
         label = out.pop("label")
@@ -149,25 +120,14 @@ class ConnectorEngine:
         """gene_sets: a list of gene-id collections (intersected with the LCC here); side: 0 the drugs' random sets, 1 the diseases'.
         Every set and its n_random degree-matched random sets grow -> {"n": genes on the LCC, "grow": grow()'s return for the sets themselves, "sizes", "steps", "final_lcc", "seeds_in": int32 [n_sets, n_random + 1]
         (sample 0 the set), and table_stats' entries (absent with n_random = 0)}"""
-        n_random = int(n_random)
-        if n_random != 0 and n_random < 2:
-            raise ProximityError(f"n_random={n_random}: need at least 2 random samples for a standard deviation (or 0 for no null)")
-        if int(min_bin_size) < 1:
-            raise ProximityError(f"min_bin_size={min_bin_size} must be >= 1")
-        if side not in (0, 1):
-            raise ProximityError(f"side={side} must be 0 (drugs) or 1 (diseases)")
-        if not gene_sets:
-            raise ProximityError("connector_table: gene_sets must not be empty")
-        if self._rowptr is None:
-            raise ProximityError("connector_table: the engine is closed")
+        n_random = self.null_arguments("connector_table", gene_sets, side, n_random, min_bin_size, or_zero=True)
+        self._open("connector_table")
         sets = [self.net.node_set(s) for s in gene_sets]
         self.check(max(1, max(len(s) for s in sets)), n_add)
         n = np.array([len(s) for s in sets], np.int64)
         own = self.grow(sets, n_add)
         out = {"n": n, "grow": own}
-        net_n = self.net.n
-        nodes, sizes = random_set_table(lambda *args: self.lib.gss_random_sets(net_n, *args), "gss_random_sets", net_n, self._dev, sets, side,
-                                        n_random, seed, degree_bins(self.net.degree, min_bin_size))
+        nodes, sizes = self.set_table(sets, side, n_random, seed, degree_bins(self.net.degree, min_bin_size))
         R, max_size = n_random + 1, nodes.shape[2]
         res = self.run(nodes.reshape(-1, max_size), sizes.reshape(-1), n_add)
         out["sizes"] = sizes.cpu().numpy()

@@ -8,8 +8,8 @@ import time
 
 import numpy as np
 
-from .diamond_cli import load_seed_sets
-from .proximity import ProximityError, disease_key
+from ._sets_cli import add_null_arguments, add_set_source, check_null_arguments, read_sets, write_null
+from .proximity import ProximityError
 from .proximity_cli import _fmt
 from .set_modules import STAT_FIELDS, largest_component
 
@@ -22,15 +22,9 @@ SUMMARY_HEADER = (["set", "n", "lcc.before", "lcc.after", "seeds.joined", "conne
 def parse_args(argv=None):
     p = argparse.ArgumentParser(prog="seed_connectors.py", description="seed connector algorithm: join a gene set's fragments on the GPU")
     p.add_argument("--network", required=True, help="gene network .sif (gene rel gene), read as undirected; its LCC is used")
-    which = p.add_mutually_exclusive_group(required=True)
-    which.add_argument("--diseases", default=None, help="disease gene table (disease_genes.tsv): the to-side random sets of proximity.py")
-    which.add_argument("--drugs", default=None, help="drug target pickle (drug_to_geneids.pcl.all): the from-side random sets of proximity.py")
-    which.add_argument("--seeds", default=None, help="a seeds file: one set per line, `name<TAB>gene<TAB>gene...` (random sets as for diseases)")
-    p.add_argument("--set", action="append", default=None, metavar="NAME", help="grow only this set (may be repeated)")
+    add_set_source(p, seeds=True, null=True)
     p.add_argument("--max-add", default=500, type=int, help="connectors to add to a set at the most")
-    p.add_argument("--n-random", default=1000, type=int, help="degree-matched random samples per set; 0 skips the null")
-    p.add_argument("--seed", default=452456, type=int, help="seed of the counter-based generator of the random sets")
-    p.add_argument("--min-bin-size", default=100, type=int, help="smallest degree bin")
+    add_null_arguments(p, or_zero=True)
     p.add_argument("--out", default="modules.tsv", help="the connectors, one row per set and rank (the layout of diamond.py --out)")
     p.add_argument("--connectors", default=None, help="also write every step: the LCC before and after, the components joined")
     p.add_argument("--summary", default=None, help="also write one row per set: the LCC before and after, seeds joined, connectors, the null")
@@ -40,10 +34,7 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     if args.max_add < 1:
         p.error(f"--max-add {args.max_add} must be >= 1")
-    if args.n_random != 0 and args.n_random < 2:
-        p.error(f"--n-random {args.n_random}: need at least 2 random samples for a standard deviation, or 0 for no null")
-    if args.min_bin_size < 1:
-        p.error(f"--min-bin-size {args.min_bin_size} must be >= 1")
+    check_null_arguments(p, args, or_zero=True)
     if args.null and args.n_random == 0:
         p.error("--null needs --n-random >= 2")
     return args
@@ -104,22 +95,7 @@ def main(argv=None):
     args = parse_args(argv)
     t0 = time.time()
     try:
-        if args.diseases:
-            sets = P.load_disease_genes(args.diseases)
-        elif args.drugs:
-            sets = P.load_drug_targets(args.drugs)
-        else:
-            sets = load_seed_sets(args.seeds)
-        path = args.diseases or args.drugs or args.seeds
-        if not sets:
-            raise ProximityError(f"{path}: no gene set")
-        names = sorted(sets)
-        if args.set:
-            wanted = [disease_key(s) if args.diseases else s for s in args.set]
-            unknown = [s for s in wanted if s not in sets]
-            if unknown:
-                raise ProximityError(f"{path}: no set named {unknown[0]!r}")
-            names = sorted(set(wanted))
+        sets, names, _ = read_sets(args)
         net = P.read_network(args.network)
     except (OSError, ValueError) as e:
         sys.exit(f"seed_connectors: {e}")
@@ -142,8 +118,7 @@ def main(argv=None):
         write_summary(args.summary, names, res)
         print(f"wrote {args.summary}")
     if args.null:
-        with open(args.null, "wb") as f:         # np.save on a name would append .npy
-            np.save(f, np.stack([res[k][:, 1:] for k in ("steps", "final_lcc", "seeds_in")], axis=1).astype(np.int32))
+        write_null(args.null, [res[k][:, 1:] for k in ("steps", "final_lcc", "seeds_in")])
         print(f"wrote {args.null}")
     print(f"seed_connectors: {len(names)} sets, max_add={args.max_add}, n_random={args.n_random}, LCC {net.n} nodes, "
           f"{int(grown['steps'].sum())} connectors, {time.time() - t0:.1f} s")

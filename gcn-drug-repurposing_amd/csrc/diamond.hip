@@ -2,7 +2,8 @@
 // links into the module are the most significant under the hypergeometric null.  include/gssgcn.h has the contract and the statistic,
 // DESIGN.md section 9.18 the LDS budget and the cost model.
 //
-// One kernel, one unit (one row of a seed table) per workgroup at a time.  The unit's state lives in LDS for all its steps:
+// One kernel, one unit (one row of a seed table, admitted as seed_units.h states) per workgroup at a time.  The unit's state lives in LDS
+// for all its steps:
 //   cnt[v]   one 32-bit word per node: ks (neighbours among the seeds) in the low half, ka (neighbours among the added nodes) in the high
 //            half, kept by LDS integer adds while a row is walked (a wave per seed row, the whole workgroup on a winner's row: a hub row
 //            is never walked by one lane);
@@ -14,7 +15,7 @@
 // status word's atomicOr.
 #include <algorithm>
 
-#include "device_scope.h"
+#include "seed_units.h"
 
 // the contract's S and lt0 are sequences of single IEEE operations: no multiply-add may be formed of term * q and S + term
 #pragma clang fp contract(off)
@@ -57,26 +58,17 @@ __global__ __launch_bounds__(kThreads) void diamond_grow_kernel(GrowArgs a) {
   const int32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int32_t n = a.n, alpha = a.alpha, words = (n + 31) >> 5;
   for (int64_t u = blockIdx.x; u < a.n_units; u += gridDim.x) {
-    const int32_t m = a.sizes[u];
-    if (m < 0 || m > a.max_size) {                       // the same word for every thread: the whole block moves on
-      if (tid == 0) atomicOr(a.flag, 1);
-      continue;
-    }
+    const int32_t m = unit_size(a.sizes, u, a.max_size, a.flag);
+    if (m < 0) continue;
     const int32_t *x = a.seeds + u * a.max_size;
     int bad = 0;
     for (int32_t v = tid; v < n; v += kThreads) {
       cnt[v] = 0;
-      const int32_t deg = a.rowptr[v + 1] - a.rowptr[v];
-      if (deg < 0 || deg > a.max_deg) bad |= 8;
+      bad |= unit_row_bits(a.rowptr, v, a.max_deg);
     }
     for (int32_t i = tid; i < words; i += kThreads) in[i] = 0;
-    for (int32_t i = tid; i < m; i += kThreads) {
-      const int32_t v = x[i];
-      if (v < 0 || v >= n) bad |= 2;
-      else if (i > 0 && x[i - 1] >= v) bad |= 4;
-    }
-    if (bad) atomicOr(a.flag, bad);
-    if (__syncthreads_or(bad)) continue;                 // no row of a refused unit is walked
+    for (int32_t i = tid; i < m; i += kThreads) bad |= unit_member_bits(x, i, n);
+    if (unit_refused(bad, a.flag)) continue;             // no row of a refused unit is walked
     for (int32_t i = tid; i < m; i += kThreads) atomicOr(&in[x[i] >> 5], 1u << (x[i] & 31));
     for (int32_t i = w; i < m; i += kWaves) {            // a wave per seed row
       const int32_t v = x[i], hi = a.rowptr[v + 1];
@@ -203,9 +195,8 @@ int gss_diamond_grow(int32_t n, const int32_t *rowptr, const int32_t *col, int32
   GSS_REQUIRE(n_units <= ((int64_t(1) << 40) - 1) / std::max(max_size, n_add),
               "diamond_grow: the tables are too large (n_units=%lld x max_size=%d, n_add=%d)", (long long)n_units, max_size, n_add);
   hipStream_t st = as_stream(stream);
-  DeviceBuf<int32_t> flag;
-  if (int rc = flag.alloc("diamond_grow", sizeof(int32_t))) return rc;
-  GSS_HIP(hipMemsetAsync(flag.p, 0, sizeof(int32_t), st));
+  UnitStatus status;
+  if (int rc = status.begin("diamond_grow", st)) return rc;
   GrowArgs a;
   a.n = n;
   a.max_deg = max_deg;
@@ -221,7 +212,7 @@ int gss_diamond_grow(int32_t n, const int32_t *rowptr, const int32_t *col, int32
   a.node = node;
   a.k = k;
   a.kb = kb;
-  a.flag = flag.p;
+  a.flag = status.flag.p;
   a.lt0 = lt0;
   a.S = S;
   a.logp = logp;
@@ -229,13 +220,7 @@ int gss_diamond_grow(int32_t n, const int32_t *rowptr, const int32_t *col, int32
   const int blocks = (int)std::min<int64_t>(n_units, kMaxBlocks);
   diamond_grow_kernel<<<blocks, kThreads, lds_request(diamond_grow_kernel, lds), st>>>(a);
   GSS_LAUNCH_CHECK("diamond_grow_kernel");
-  int32_t h = 0;
-  if (int rc = read_back(&h, flag.p, sizeof(int32_t), st)) return rc;
-  GSS_REQUIRE(!(h & 1), "diamond_grow: a unit's size is outside [0, max_size=%d]", max_size);
-  GSS_REQUIRE(!(h & 2), "diamond_grow: a seed is not a node index in [0, %d)", n);
-  GSS_REQUIRE(!(h & 4), "diamond_grow: a unit's seeds are not strictly ascending");
-  GSS_REQUIRE(!(h & 8), "diamond_grow: a row of the CSR is longer than max_deg=%d", max_deg);
-  return GSS_OK;
+  return status.end("diamond_grow", "seed", n, max_size, max_deg, st);
 }
 
 }  // extern "C"

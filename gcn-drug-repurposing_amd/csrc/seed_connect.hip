@@ -2,7 +2,8 @@
 // step the node outside the module that most enlarges the largest connected component of the subgraph the module induces.
 // include/gssgcn.h has the contract and the tie rule, DESIGN.md section 9.19 the LDS budget and the cost model.
 //
-// One kernel, one unit (one row of a seed table) per workgroup at a time.  The unit's state lives in LDS for all its steps:
+// One kernel, one unit (one row of a seed table, admitted as seed_units.h states) per workgroup at a time.  The unit's state lives in LDS
+// for all its steps:
 //   lab[v]   one 32-bit word per node: for a member of the module kMember | its position in the module (seeds in their order, then
 //            the added nodes in the order added); otherwise kTouch when a neighbour is a member (a candidate), 0 when none is;
 //   ps[i]    one 32-bit word per member position: the position of its component's root in the low 15 bits (always the root itself:
@@ -18,8 +19,8 @@
 // All integers: the outputs do not depend on the schedule.  The only global atomic is the status word's atomicOr.
 #include <algorithm>
 
-#include "device_scope.h"
 #include "lds_union_find.h"
+#include "seed_units.h"
 
 namespace gss {
 namespace {
@@ -99,25 +100,16 @@ __global__ __launch_bounds__(kThreads) void seed_connect_kernel(ConnectArgs a) {
   const int32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int32_t n = a.n, width = a.max_size + a.n_add;
   for (int64_t u = blockIdx.x; u < a.n_units; u += gridDim.x) {
-    const int32_t m = a.sizes[u];
-    if (m < 0 || m > a.max_size) {                       // the same word for every thread: the whole block moves on
-      if (tid == 0) atomicOr(a.flag, 1);
-      continue;
-    }
+    const int32_t m = unit_size(a.sizes, u, a.max_size, a.flag);
+    if (m < 0) continue;
     const int32_t *x = a.seeds + u * a.max_size;
     int bad = 0;
     for (int32_t v = tid; v < n; v += kThreads) {
       lab[v] = 0;
-      const int32_t deg = a.rowptr[v + 1] - a.rowptr[v];
-      if (deg < 0 || deg > a.max_deg) bad |= 8;
+      bad |= unit_row_bits(a.rowptr, v, a.max_deg);
     }
-    for (int32_t i = tid; i < m; i += kThreads) {
-      const int32_t v = x[i];
-      if (v < 0 || v >= n) bad |= 2;
-      else if (i > 0 && x[i - 1] >= v) bad |= 4;
-    }
-    if (bad) atomicOr(a.flag, bad);
-    if (__syncthreads_or(bad)) continue;                 // no row of a refused unit is walked
+    for (int32_t i = tid; i < m; i += kThreads) bad |= unit_member_bits(x, i, n);
+    if (unit_refused(bad, a.flag)) continue;             // no row of a refused unit is walked
     for (int32_t i = tid; i < m; i += kThreads) {
       lab[x[i]] = kMember | (uint32_t)i;
       ps[i] = (uint32_t)i;
@@ -135,17 +127,7 @@ __global__ __launch_bounds__(kThreads) void seed_connect_kernel(ConnectArgs a) {
       }
     }
     __syncthreads();
-    for (;;) {                                           // pointer jumping; a racing read sees an ancestor either way
-      int moved = 0;
-      for (int32_t i = tid; i < m; i += kThreads) {
-        const uint32_t p = ps[i], g = ((volatile uint32_t *)ps)[p];
-        if (g != p) {
-          ((volatile uint32_t *)ps)[i] = g;
-          moved = 1;
-        }
-      }
-      if (!__syncthreads_or(moved)) break;
-    }
+    uf_flatten(reinterpret_cast<int32_t *>(ps), m, tid, kThreads);
     for (int32_t i = tid; i < m; i += kThreads) atomicAdd(&ps[ps[i] & kParent], 1u << 16);   // sizes onto the roots' high halves
     __syncthreads();
     int32_t big = 0;
@@ -307,9 +289,8 @@ int gss_seed_connectors(int32_t n, const int32_t *rowptr, const int32_t *col, in
   GSS_REQUIRE(n_units <= ((int64_t(1) << 40) - 1) / (max_size + n_add),
               "seed_connectors: the tables are too large (n_units=%lld x (max_size=%d + n_add=%d))", (long long)n_units, max_size, n_add);
   hipStream_t st = as_stream(stream);
-  DeviceBuf<int32_t> flag;
-  if (int rc = flag.alloc("seed_connectors", sizeof(int32_t))) return rc;
-  GSS_HIP(hipMemsetAsync(flag.p, 0, sizeof(int32_t), st));
+  UnitStatus status;
+  if (int rc = status.begin("seed_connectors", st)) return rc;
   ConnectArgs a;
   a.n = n;
   a.max_deg = max_deg;
@@ -330,18 +311,12 @@ int gss_seed_connectors(int32_t n, const int32_t *rowptr, const int32_t *col, in
   a.seeds_in = seeds_in;
   a.added_in = added_in;
   a.label = label;
-  a.flag = flag.p;
+  a.flag = status.flag.p;
   const size_t lds = ((size_t)n + (size_t)max_size + (size_t)n_add + (size_t)kThreads) * sizeof(uint32_t);
   const int blocks = (int)std::min<int64_t>(n_units, kMaxBlocks);
   seed_connect_kernel<<<blocks, kThreads, lds_request(seed_connect_kernel, lds), st>>>(a);
   GSS_LAUNCH_CHECK("seed_connect_kernel");
-  int32_t h = 0;
-  if (int rc = read_back(&h, flag.p, sizeof(int32_t), st)) return rc;
-  GSS_REQUIRE(!(h & 1), "seed_connectors: a unit's size is outside [0, max_size=%d]", max_size);
-  GSS_REQUIRE(!(h & 2), "seed_connectors: a seed is not a node index in [0, %d)", n);
-  GSS_REQUIRE(!(h & 4), "seed_connectors: a unit's seeds are not strictly ascending");
-  GSS_REQUIRE(!(h & 8), "seed_connectors: a row of the CSR is longer than max_deg=%d", max_deg);
-  return GSS_OK;
+  return status.end("seed_connectors", "seed", n, max_size, max_deg, st);
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 // module on the interactome?) on the device.  include/gssgcn.h has the contract, DESIGN.md section 9.17 the cost model and the measurements.
 //
 // One kernel, one unit (one row of a set table, the layout gss_prox_random_sets writes) per workgroup at a time:
-//   1. the member list goes into LDS, checked on the way (size, range, strictly ascending); parent[i] = i beside it;
+//   1. the member list goes into LDS, checked on the way as seed_units.h states; parent[i] = i beside it;
 //   2. a wave per member probes the member's CSR row against the list in the cheaper direction -- lanes over the row's entries, each a
 //      binary search of the LDS list (deg * log2 m), or lanes over the members, each a binary search of the row (m * log2 deg) -- so a hub
 //      row is never walked by one lane.  Every hit (i, j) is a union in a lock-free union-find in LDS: the larger root is hooked under
@@ -13,8 +13,8 @@
 // All integers: the outputs do not depend on the schedule.  The only global atomic is the status word's atomicOr.
 #include <algorithm>
 
-#include "device_scope.h"
 #include "lds_union_find.h"
+#include "seed_units.h"
 
 namespace gss {
 namespace {
@@ -59,24 +59,16 @@ __global__ __launch_bounds__(256) void set_components_kernel(CompArgs a) {
   __shared__ int32_t red[3][4];
   const int32_t tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, w = tid >> 6, nw = nt >> 6;
   for (int64_t u = blockIdx.x; u < a.n_units; u += gridDim.x) {
-    const int32_t m = a.sizes[u];
-    if (m < 0 || m > a.max_size) {                       // the same word for every thread: the whole block moves on
-      if (tid == 0) atomicOr(a.flag, 1);
-      continue;
-    }
+    const int32_t m = unit_size(a.sizes, u, a.max_size, a.flag);
+    if (m < 0) continue;
     const int32_t *x = a.nodes + u * a.max_size;
     int bad = 0;
     for (int32_t i = tid; i < m; i += nt) {
-      const int32_t v = x[i];
-      mem[i] = v;
+      mem[i] = x[i];
       parent[i] = i;
-      if (v < 0 || v >= a.n) bad |= 2;
+      bad |= unit_member_bits(x, i, a.n);
     }
-    __syncthreads();
-    for (int32_t i = tid + 1; i < m; i += nt)
-      if (mem[i - 1] >= mem[i]) bad |= 4;
-    if (bad) atomicOr(a.flag, bad);
-    if (__syncthreads_or(bad)) continue;                 // no row of a refused unit is read
+    if (unit_refused(bad, a.flag)) continue;             // the barrier after the copy; no row of a refused unit is read
     int edges = 0;
     for (int32_t i = w; i < m; i += nw) {                // a wave per member
       const int32_t v = mem[i], lo = a.rowptr[v], deg = a.rowptr[v + 1] - lo;
@@ -100,17 +92,7 @@ __global__ __launch_bounds__(256) void set_components_kernel(CompArgs a) {
       }
     }
     __syncthreads();
-    for (;;) {                                           // pointer jumping; a racing read sees an ancestor either way
-      int moved = 0;
-      for (int32_t i = tid; i < m; i += nt) {
-        const int32_t p = parent[i], g = ((volatile int32_t *)parent)[p];
-        if (g != p) {
-          ((volatile int32_t *)parent)[i] = g;
-          moved = 1;
-        }
-      }
-      if (!__syncthreads_or(moved)) break;
-    }
+    uf_flatten(parent, m, tid, nt);
     for (int32_t i = tid; i < m; i += nt) mem[i] = 0;    // the members are not needed any more
     __syncthreads();
     int roots = 0;
@@ -160,9 +142,8 @@ int gss_set_components(int32_t n, const int32_t *rowptr, const int32_t *col, int
   GSS_REQUIRE(n_units <= ((int64_t(1) << 40) - 1) / max_size, "set_components: the set table is too large (n_units=%lld x max_size=%d)",
               (long long)n_units, max_size);
   hipStream_t st = as_stream(stream);
-  DeviceBuf<int32_t> flag;
-  if (int rc = flag.alloc("set_components", sizeof(int32_t))) return rc;
-  GSS_HIP(hipMemsetAsync(flag.p, 0, sizeof(int32_t), st));
+  UnitStatus status;
+  if (int rc = status.begin("set_components", st)) return rc;
   CompArgs a;
   a.n = n;
   a.max_size = max_size;
@@ -175,17 +156,12 @@ int gss_set_components(int32_t n, const int32_t *rowptr, const int32_t *col, int
   a.n_comp = n_comp;
   a.n_edges = n_edges;
   a.label = label;
-  a.flag = flag.p;
+  a.flag = status.flag.p;
   const int threads = max_size <= kSmallSet ? 64 : 256;
   const int blocks = (int)std::min<int64_t>(n_units, kMaxBlocks);
   set_components_kernel<<<blocks, threads, 2 * (size_t)max_size * sizeof(int32_t), st>>>(a);
   GSS_LAUNCH_CHECK("set_components_kernel");
-  int32_t h = 0;
-  if (int rc = read_back(&h, flag.p, sizeof(int32_t), st)) return rc;
-  GSS_REQUIRE(!(h & 1), "set_components: a unit's size is outside [0, max_size=%d]", max_size);
-  GSS_REQUIRE(!(h & 2), "set_components: a member is not a node index in [0, %d)", n);
-  GSS_REQUIRE(!(h & 4), "set_components: a unit's members are not strictly ascending");
-  return GSS_OK;
+  return status.end("set_components", "member", n, max_size, 0, st);   // max_deg: this kernel checks no row
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@ import math
 
 import numpy as np
 
+from ._network_engine import NetworkEngine
 from .proximity import ProximityError
 
 MAX_NODES = 30720                # per node a word of link counts and a membership bit in LDS, beside the 4,096-slot table
@@ -54,29 +55,16 @@ def holdout_draws(node_sets, holdout, repeats, seed):
     return out
 
 
-class DiamondEngine:
-    """owns the device CSR of `network` (a proximity.Network) and the lgamma table"""
+class DiamondEngine(NetworkEngine):
+    """the network's device CSR and the lgamma table"""
 
     def __init__(self, network):
-        import torch
-        from . import _lib
-        self.lib = _lib.load()
-        self.net = network
-        self._torch = torch
-        self._dev = torch.device("cuda")
-        self.max_deg = int(np.diff(network.rowptr).max()) if network.n else 0
-        self._rowptr = torch.from_numpy(network.rowptr).to(self._dev)
-        self._col = torch.from_numpy(network.col if len(network.col) else np.zeros(1, np.int32)).to(self._dev)
+        super().__init__(network)
         self._lg = None
 
     def close(self):
-        self._rowptr = self._col = self._lg = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
+        super().close()
+        self._lg = None
 
     def _table(self, n_lg):
         if self._lg is None or len(self._lg) < n_lg:
@@ -90,21 +78,19 @@ class DiamondEngine:
             raise ProximityError(f"n_add={n_add} must be >= 1")
         if alpha < 1:
             raise ProximityError(f"alpha={alpha} must be >= 1")
-        if not len(node_sets):
-            raise ProximityError("grow: node_sets must not be empty")
+        sets, max_size = self.node_arrays(node_sets)
         if not 1 <= self.net.n <= MAX_NODES:
             raise ProximityError(f"a network of {self.net.n} nodes; between 1 and {MAX_NODES} are supported")
-        sets = [np.asarray(s, np.int32).reshape(-1) for s in node_sets]
         big = max(len(s) for s in sets)
         if big > MAX_SEEDS:
             raise ProximityError(f"a set has {big} seeds; at most {MAX_SEEDS} are supported")
         if alpha * self.max_deg > MAX_COUNT:
             raise ProximityError(f"alpha={alpha} x the largest degree {self.max_deg} is over {MAX_COUNT}")
-        top = min(alpha * self.max_deg, alpha * max(big, 1) + n_add - 1)
+        top = min(alpha * self.max_deg, alpha * max_size + n_add - 1)
         if top >= SLOTS:
             raise ProximityError(f"a node can have {top} weighted links into a module (alpha={alpha}, largest degree {self.max_deg}, {big} seeds, "
                                  f"n_add={n_add}); at most {SLOTS - 1} are supported")
-        return sets, max(big, 1)
+        return sets, max_size
 
     def grow(self, node_sets, n_add=200, alpha=1):
         """node_sets: a list of node-index arrays (strictly ascending, as Network.node_set returns them) -> {"node", "k", "kb": int32,
@@ -113,16 +99,11 @@ class DiamondEngine:
         used up, node = -1 and p = NaN for the rest of its steps."""
         from . import _lib
         torch = self._torch
-        if self._rowptr is None:
-            raise ProximityError("grow: the engine is closed")
+        self._open("grow")
         n_add, alpha = int(n_add), int(alpha)
         sets, max_size = self.check(node_sets, n_add, alpha)
         U = len(sets)
-        seeds = np.full((U, max_size), -1, np.int32)
-        for i, s in enumerate(sets):
-            seeds[i, :len(s)] = s
-        d_seeds = torch.from_numpy(seeds).to(self._dev)
-        d_sizes = torch.from_numpy(np.array([len(s) for s in sets], np.int32)).to(self._dev)
+        d_seeds, d_sizes, _ = self.pack(sets)
         lg = self._table(self.net.n + (alpha - 1) * max_size + 2)
         ints = [torch.empty((U, n_add), dtype=torch.int32, device=self._dev) for _ in range(3)]
         reals = [torch.empty((U, n_add), dtype=torch.float64, device=self._dev) for _ in range(3)]

@@ -8,7 +8,8 @@ import time
 
 import numpy as np
 
-from .proximity import ProximityError, disease_key
+from ._sets_cli import add_set_source, load_seed_sets, read_sets  # noqa: F401  (load_seed_sets: this module's callers import it here)
+from .proximity import ProximityError
 from .proximity_cli import _fmt
 
 HEADER = ["set", "rank", "gene", "k", "kb", "logp", "p"]
@@ -19,11 +20,7 @@ RECOVERY_HEADER = ["set", "rank", "recovered", "held"]
 def parse_args(argv=None):
     p = argparse.ArgumentParser(prog="diamond.py", description="DIAMOnD: grow disease modules from seed genes on the GPU")
     p.add_argument("--network", required=True, help="gene network .sif (gene rel gene), read as undirected; its LCC is used")
-    which = p.add_mutually_exclusive_group(required=True)
-    which.add_argument("--diseases", default=None, help="disease gene table (disease_genes.tsv)")
-    which.add_argument("--drugs", default=None, help="drug target pickle (drug_to_geneids.pcl.all)")
-    which.add_argument("--seeds", default=None, help="a seeds file: one set per line, `name<TAB>gene<TAB>gene...`")
-    p.add_argument("--set", action="append", default=None, metavar="NAME", help="grow only this set (may be repeated)")
+    add_set_source(p, seeds=True, null=False)
     p.add_argument("--n-add", default=200, type=int, help="nodes to add to every set")
     p.add_argument("--alpha", default=1, type=int, help="the seeds' weight, an integer >= 1")
     p.add_argument("--out", default="modules.tsv", help="the added nodes, one row per set and rank")
@@ -42,19 +39,6 @@ def parse_args(argv=None):
     if args.repeats < 1:
         p.error(f"--repeats {args.repeats} must be >= 1")
     return args
-
-
-def load_seed_sets(path):
-    """{set name: set of gene ids (str)} from a seeds file (`name\\tgene\\tgene...`; empty lines and lines starting with # are skipped;
-    a name on several lines collects them all).  The name is kept as written"""
-    out = {}
-    with open(path) as f:
-        for line in f:
-            p = line.rstrip("\n").split("\t")
-            if not p[0] or p[0].startswith("#"):
-                continue
-            out.setdefault(p[0], set()).update(g for g in p[1:] if g)
-    return out
 
 
 def write_modules(path, names, genes, res):
@@ -85,25 +69,15 @@ def write_recovery(path, names, rec):
                 f.write(f"{name}\t{r + 1}\t{int(x)}\t{int(rec['held'][i])}\n")
 
 
-def module_lcc(net, sets, node):
-    """largest connected component of every seed set and of seeds + added nodes, by ModuleEngine.components -> two int64 [n_sets]"""
-    import torch
-    from .set_modules import MAX_SET, ModuleEngine
-    both = [[np.asarray(s, np.int32), np.unique(np.concatenate([s, row[row >= 0]])).astype(np.int32)] for s, row in zip(sets, node)]
-    width = max(1, max(len(u) for pair in both for u in pair))
+def module_lcc(eng, sets, node):
+    """largest connected component of every seed set and of seeds + added nodes, by the engine's components -> two int64 [n_sets]"""
+    from ._network_engine import MAX_SET
+    both = [u for s, row in zip(sets, node) for u in (s, np.unique(np.concatenate([s, row[row >= 0]])))]
+    width = max(1, max(len(u) for u in both))
     if width > MAX_SET:
         raise ProximityError(f"a module of {width} nodes; the component search takes at most {MAX_SET}")
-    nodes = np.full((len(both), 2, width), -1, np.int32)
-    sizes = np.zeros((len(both), 2), np.int32)
-    for i, pair in enumerate(both):
-        for j, u in enumerate(pair):
-            nodes[i, j, :len(u)] = u
-            sizes[i, j] = len(u)
-    eng = ModuleEngine(net)
-    try:
-        lcc = eng.components(torch.from_numpy(nodes).cuda(), torch.from_numpy(sizes).cuda())[0].cpu().numpy().astype(np.int64)
-    finally:
-        eng.close()
+    nodes, sizes, _ = eng.pack(both)
+    lcc = eng.components(nodes.reshape(len(sets), 2, -1), sizes.reshape(len(sets), 2))[0].cpu().numpy().astype(np.int64)
     return lcc[:, 0], lcc[:, 1]
 
 
@@ -113,22 +87,7 @@ def main(argv=None):
     args = parse_args(argv)
     t0 = time.time()
     try:
-        if args.diseases:
-            sets = P.load_disease_genes(args.diseases)
-        elif args.drugs:
-            sets = P.load_drug_targets(args.drugs)
-        else:
-            sets = load_seed_sets(args.seeds)
-        path = args.diseases or args.drugs or args.seeds
-        if not sets:
-            raise ProximityError(f"{path}: no gene set")
-        names = sorted(sets)
-        if args.set:
-            wanted = [disease_key(s) if args.diseases else s for s in args.set]
-            unknown = [s for s in wanted if s not in sets]
-            if unknown:
-                raise ProximityError(f"{path}: no set named {unknown[0]!r}")
-            names = sorted(set(wanted))
+        sets, names, _ = read_sets(args)
         net = P.read_network(args.network)
     except (OSError, ValueError) as e:
         sys.exit(f"diamond: {e}")
@@ -139,7 +98,7 @@ def main(argv=None):
         rec = None
         if args.holdout is not None:
             rec = eng.recovery(members, holdout=args.holdout, repeats=args.repeats, seed=args.seed, n_add=args.n_add, alpha=args.alpha)
-        lcc = module_lcc(net, members, res["node"]) if args.summary else None
+        lcc = module_lcc(eng, members, res["node"]) if args.summary else None
     except ProximityError as e:
         sys.exit(f"diamond: {e}")
     finally:

@@ -8,6 +8,7 @@ import time
 
 import numpy as np
 
+from ._sets_cli import add_null_arguments, add_set_source, check_null_arguments, read_sets, write_null
 from .proximity import ProximityError
 from .proximity_cli import _fmt
 from .set_modules import STAT_FIELDS, largest_component
@@ -21,20 +22,13 @@ def parse_args(argv=None):
     p = argparse.ArgumentParser(prog="disease_modules.py",
                                 description="module significance of gene sets: largest connected component vs degree-matched random sets, on the GPU")
     p.add_argument("--network", required=True, help="gene network .sif (gene rel gene), read as undirected; its LCC is used")
-    which = p.add_mutually_exclusive_group(required=True)
-    which.add_argument("--diseases", default=None, help="disease gene table (disease_genes.tsv): the to-side random sets of proximity.py")
-    which.add_argument("--drugs", default=None, help="drug target pickle (drug_to_geneids.pcl.all): the from-side random sets of proximity.py")
-    p.add_argument("--n-random", default=1000, type=int, help="degree-matched random samples per set")
-    p.add_argument("--seed", default=452456, type=int, help="seed of the counter-based generator of the random sets")
-    p.add_argument("--min-bin-size", default=100, type=int, help="smallest degree bin")
+    add_set_source(p, seeds=False, null=True)
+    add_null_arguments(p, or_zero=False)
     p.add_argument("--out", default="modules.tsv", help="the table, one row per set")
     p.add_argument("--members", default=None, help="also write every set's genes with their component")
     p.add_argument("--null", default=None, help="also write the integer nulls, int32 [n_sets][2][n_random] (lcc, edges), as .npy")
     args = p.parse_args(argv)
-    if args.n_random < 2:
-        p.error(f"--n-random {args.n_random}: need at least 2 random samples for a standard deviation")
-    if args.min_bin_size < 1:
-        p.error(f"--min-bin-size {args.min_bin_size} must be >= 1")
+    check_null_arguments(p, args, or_zero=False)
     return args
 
 
@@ -66,13 +60,10 @@ def main(argv=None):
     args = parse_args(argv)
     t0 = time.time()
     try:
-        sets = P.load_disease_genes(args.diseases) if args.diseases else P.load_drug_targets(args.drugs)
-        if not sets:
-            raise ProximityError(f"{args.diseases or args.drugs}: no gene set")
+        sets, names, _ = read_sets(args)
         net = P.read_network(args.network)
     except (OSError, ValueError) as e:
         sys.exit(f"disease_modules: {e}")
-    names = sorted(sets)
     eng = ModuleEngine(net)
     try:
         res = eng.module_table([sets[n] for n in names], 1 if args.diseases else 0, n_random=args.n_random, seed=args.seed,
@@ -87,8 +78,7 @@ def main(argv=None):
         write_members(args.members, names, net.names, res)
         print(f"wrote {args.members}")
     if args.null:
-        with open(args.null, "wb") as f:         # np.save on a name would append .npy
-            np.save(f, np.stack([res["null_lcc"], res["null_edges"]], axis=1).astype(np.int32))
+        write_null(args.null, [res["null_lcc"], res["null_edges"]])
         print(f"wrote {args.null}")
     q = res["lcc_stats"]["q"]
     print(f"disease_modules: {len(names)} sets, n_random={args.n_random}, LCC {net.n} nodes, {int(np.sum(q <= 0.05))} with lcc.q <= 0.05, "

@@ -12,9 +12,9 @@ from __future__ import annotations
 import numpy as np
 
 from ._nulls import benjamini_hochberg
-from .proximity import ProximityError, degree_bins, random_set_table
+from ._network_engine import MAX_SET, NetworkEngine
+from .proximity import ProximityError, degree_bins
 
-MAX_SET = 4096                   # members of one set the component kernel holds in LDS
 STAT_FIELDS = ("mean", "sd", "z", "p", "q")
 
 
@@ -55,51 +55,8 @@ def largest_component(label):
     return int(np.argmax(count))          # argmax returns the first, i.e. the smallest label, of equal counts
 
 
-class ModuleEngine:
-    """owns the device CSR of `network` (a proximity.Network) and nothing else: no distance matrix"""
-
-    def __init__(self, network):
-        import torch
-        from . import _lib
-        self.lib = _lib.load()
-        self.net = network
-        self._torch = torch
-        self._dev = torch.device("cuda")
-        self._rowptr = torch.from_numpy(network.rowptr).to(self._dev)
-        self._col = torch.from_numpy(network.col if len(network.col) else np.zeros(1, np.int32)).to(self._dev)
-
-    def close(self):
-        self._rowptr = self._col = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
-
-    def set_table(self, node_sets, side, n_random, seed, bins):
-        """random sets of every set (sample 0 = the set) -> (nodes [n_sets, R, max_size], sizes [n_sets, R]) device int32: what
-        ProximityEngine.set_table returns, bit for bit"""
-        n = self.net.n
-        return random_set_table(lambda *args: self.lib.gss_random_sets(n, *args), "gss_random_sets", n, self._dev, node_sets, side, n_random,
-                                seed, bins)
-
-    def components(self, nodes, sizes, labels=False):
-        """a set table -> device int32 lcc, n_comp, n_edges [n_sets, R] (and label [n_sets, R, max_size], -1 past every size, with labels)"""
-        from . import _lib
-        torch = self._torch
-        if self._rowptr is None:
-            raise ProximityError("components: the engine is closed")
-        n_sets, R, max_size = nodes.shape
-        if max_size > MAX_SET:
-            raise ProximityError(f"a set table of up to {max_size} nodes per set; at most {MAX_SET} are supported")
-        nodes, sizes = nodes.contiguous(), sizes.contiguous()
-        lcc, n_comp, n_edges = (torch.empty((n_sets, R), dtype=torch.int32, device=self._dev) for _ in range(3))
-        label = torch.full((n_sets, R, max_size), -1, dtype=torch.int32, device=self._dev) if labels else None
-        _lib.check(self.lib.gss_set_components(self.net.n, _lib.ptr(self._rowptr), _lib.ptr(self._col), n_sets * R, max_size, _lib.ptr(nodes),
-                                               _lib.ptr(sizes), _lib.ptr(lcc), _lib.ptr(n_comp), _lib.ptr(n_edges), _lib.ptr(label),
-                                               _lib.current_stream()), "gss_set_components")
-        return (lcc, n_comp, n_edges, label) if labels else (lcc, n_comp, n_edges)
+class ModuleEngine(NetworkEngine):
+    """the network's device CSR and nothing else: no distance matrix.  set_table and components are NetworkEngine's"""
 
     def module_table(self, gene_sets, side, n_random=1000, seed=452456, min_bin_size=100):
         """gene_sets: a list of gene-id collections (intersected with the LCC here); side: 0 the drugs' random sets, 1 the diseases'.
@@ -107,15 +64,7 @@ class ModuleEngine:
         short), "lcc_stats", "edges_stats": null_stats of the LCC size / the induced edge count, "null_lcc", "null_edges": int32
         [n_sets, n_random], "members": the LCC node indices of every set, ascending, "label": per member the position of the smallest
         member of its component}.  An empty set has NaN statistics and takes no part in q."""
-        if int(n_random) < 2:
-            raise ProximityError(f"n_random={n_random}: need at least 2 random samples for a standard deviation")
-        if int(min_bin_size) < 1:
-            raise ProximityError(f"min_bin_size={min_bin_size} must be >= 1")
-        if side not in (0, 1):
-            raise ProximityError(f"side={side} must be 0 (drugs) or 1 (diseases)")
-        if not gene_sets:
-            raise ProximityError("module_table: gene_sets must not be empty")
-        n_random = int(n_random)
+        n_random = self.null_arguments("module_table", gene_sets, side, n_random, min_bin_size)
         sets = [self.net.node_set(s) for s in gene_sets]
         big = max(len(s) for s in sets)
         if big > MAX_SET:

@@ -444,9 +444,10 @@ int gss_prox_score(gss_prox *p, const gss_prox_sets *from, const gss_prox_sets *
  * j > i found in row i (the induced edges of a symmetric CSR) and, when label is not NULL ([n_units][max_size]), label[u][i] = the
  * position within the unit of the smallest member of i's component; entries past the size are left as the caller had them.  All
  * integers, exact: the same between runs and for any split of the units into calls.  n >= 1, n_units >= 1, 1 <= max_size <= 4096 (a
- * unit's members and parents live in LDS), n_units * max_size < 2^40.  Refused by name (GSS_EINVAL): a null pointer, a size outside
- * [0, max_size], a member outside [0, n), members not strictly ascending -- the last three found on the device (no row of such a unit
- * is read; the outputs are then undefined).  Synchronises the stream (reads the status word back). */
+ * unit's members and parents live in LDS), n_units * max_size < 2^40.  Refused by name (GSS_EINVAL): a null pointer, these bounds, and
+ * a unit that breaks the table's contract -- its size, a member's range, the members' order: found on the device, defined and worded
+ * in csrc/seed_units.h for every op that takes such a table (no row of such a unit is read; the outputs are then undefined).
+ * Synchronises the stream (reads the status word back). */
 int gss_random_sets(int32_t n, int32_t side, int32_t n_sets, const int32_t *set_ptr, const int32_t *set_nodes, int32_t max_size,
                     const int32_t *node_bin, const int32_t *bin_ptr, const int32_t *bin_nodes, int32_t n_random, uint64_t seed,
                     int32_t *out_nodes, int32_t *out_size, void *stream);
@@ -476,9 +477,9 @@ int gss_set_components(int32_t n, const int32_t *rowptr, const int32_t *col, int
  * n in [1, 30720] (per node a 32-bit word of counts and a membership bit live in LDS, beside a 4,096-slot table of stage 1's keys: 156 KiB
  * of the CU's 160), n_units >= 1, 1 <= max_size <= 4096, n_add >= 1, alpha >= 1, alpha max_deg <= 65535 (the counts are 16 bits),
  * min(alpha max_deg, alpha max_size + n_add - 1) <= 4095 (the largest kb' a step can see has a slot).  Refused by name (GSS_EINVAL): a
- * null pointer, any of these bounds, a size outside [0, max_size], a seed outside [0, n), seeds not strictly ascending, a row longer
- * than max_deg -- the last four found on the device (no row of such a unit is walked; the outputs are then undefined).  Synchronises
- * the stream (reads the status word back). */
+ * null pointer, any of these bounds, and a unit that breaks the table's contract or a row longer than max_deg -- found on the device,
+ * defined and worded in csrc/seed_units.h (no row of such a unit is walked; the outputs are then undefined).  Synchronises the stream
+ * (reads the status word back). */
 int gss_diamond_grow(int32_t n, const int32_t *rowptr, const int32_t *col, int32_t max_deg, const double *lg, int64_t n_lg,
                      int64_t n_units, int32_t max_size, const int32_t *seeds, const int32_t *sizes, int32_t n_add, int32_t alpha,
                      int32_t *node, int32_t *k, int32_t *kb, double *lt0, double *S, double *logp, void *stream);
@@ -504,9 +505,9 @@ int gss_diamond_grow(int32_t n, const int32_t *rowptr, const int32_t *col, int32
  * n in [1, 30720], n_units >= 1, 1 <= max_size <= 4096, n_add >= 1, max_size + n_add <= 8192, 0 <= max_deg <= 1048575,
  * n_units * (max_size + n_add) < 2^40.  A unit's state lives in LDS: 4 bytes per node, 4 bytes per member of M and a 4 KiB list,
  * 4 (n + max_size + n_add) + 4096 bytes per workgroup -- 156 KiB of the CU's 160 at the limits, 75 KiB for n = 13,329, max_size 4,096,
- * n_add 500.  Refused by name (GSS_EINVAL): a null pointer (but label), any of these bounds, a size outside
- * [0, max_size], a seed outside [0, n), seeds not strictly ascending, a row longer than max_deg -- the last four found on the device
- * (no row of such a unit is walked; the outputs are then undefined).  Synchronises the stream (reads the status word back). */
+ * n_add 500.  Refused by name (GSS_EINVAL): a null pointer (but label), any of these bounds, and a unit that breaks the table's
+ * contract or a row longer than max_deg -- found on the device, defined and worded in csrc/seed_units.h (no row of such a unit is
+ * walked; the outputs are then undefined).  Synchronises the stream (reads the status word back). */
 int gss_seed_connectors(int32_t n, const int32_t *rowptr, const int32_t *col, int32_t max_deg, int64_t n_units, int32_t max_size,
                         const int32_t *seeds, const int32_t *sizes, int32_t n_add, int32_t *node, int32_t *lcc, int32_t *merged,
                         int32_t *deg, int32_t *steps, int32_t *first_lcc, int32_t *final_lcc, int32_t *seeds_in, int32_t *added_in,

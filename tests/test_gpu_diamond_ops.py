@@ -157,14 +157,17 @@ def test_refusals_by_name_leave_nothing_behind():
     rc, kept = grow(c)
     assert rc == 0, _error()
 
-    def with_unit(u, members=None, size=None):
-        s2, z2 = seeds.copy(), sizes.copy()
+    def with_unit(u, members=None, size=None, of=None):
+        """the table (or the table `of` an earlier with_unit) with unit u replaced"""
+        s2, z2 = (seeds.copy(), sizes.copy()) if of is None else (x.copy() for x in of.table)
         if members is not None:
             s2[u, :len(members)] = members
             z2[u] = len(members)
         if size is not None:
             z2[u] = size
-        return lambda: grow(c, s2, z2)[0]
+        call = lambda: grow(c, s2, z2)[0]  # noqa: E731
+        call.table = (s2, z2)
+        return call
 
     md = K.max_degree(c)
     refusals = [(lambda k=k: grow(c, null=k)[0], "diamond_grow: null pointer") for k in ("rowptr", "col", "lg", "seeds", "sizes") + OUT]
@@ -187,6 +190,10 @@ def test_refusals_by_name_leave_nothing_behind():
         (with_unit(1, members=[-1, 20, 30]), f"diamond_grow: a seed is not a node index in [0, {c.n})"),
         (with_unit(1, members=[10, 20, 20]), "diamond_grow: a unit's seeds are not strictly ascending"),
         (with_unit(2, members=[30, 20]), "diamond_grow: a unit's seeds are not strictly ascending"),
+        # several bad units in one call: the refusal is the lowest bit's, whichever unit set it
+        (with_unit(2, members=[0, 10, c.n], of=with_unit(0, members=[30, 20])), f"diamond_grow: a seed is not a node index in [0, {c.n})"),
+        (with_unit(2, size=6, of=with_unit(1, members=[30, 20], of=with_unit(0, members=[0, 10, c.n]))),
+         "diamond_grow: a unit's size is outside [0, max_size=5]"),
     ]
     for call, words in refusals:
         assert call() == EINVAL, words

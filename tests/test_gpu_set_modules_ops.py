@@ -158,15 +158,17 @@ def test_components_refusals_by_name_leave_nothing_behind():
         check(got, want("bounds"), "bounds")
         return got[1:]
 
-    def with_unit(u, members=None, size=None):
-        """the table with unit u replaced"""
-        n2, s2 = nodes.copy(), sizes.copy()
+    def with_unit(u, members=None, size=None, of=None):
+        """the table (or the table `of` an earlier with_unit) with unit u replaced"""
+        n2, s2 = (nodes.copy(), sizes.copy()) if of is None else (x.copy() for x in of.table)
         if members is not None:
             n2[u, :len(members)] = members
             s2[u] = len(members)
         if size is not None:
             s2[u] = size
-        return lambda: components(c, n2, s2)[0]
+        call = lambda: components(c, n2, s2)[0]  # noqa: E731
+        call.table = (n2, s2)
+        return call
 
     refusals = [(lambda k=k: components(c, nodes, sizes, null=k)[0], "set_components: null pointer")
                 for k in ("rowptr", "col", "nodes", "sizes", "lcc", "n_comp", "n_edges")]
@@ -182,6 +184,10 @@ def test_components_refusals_by_name_leave_nothing_behind():
         (with_unit(1, members=[-1, 20, 30]), f"set_components: a member is not a node index in [0, {c.n})"),
         (with_unit(1, members=[10, 20, 20]), "set_components: a unit's members are not strictly ascending"),
         (with_unit(2, members=[30, 20]), "set_components: a unit's members are not strictly ascending"),
+        # several bad units in one call: the refusal is the lowest bit's, whichever unit set it
+        (with_unit(2, members=[0, 100, c.n], of=with_unit(0, members=[30, 20])), f"set_components: a member is not a node index in [0, {c.n})"),
+        (with_unit(2, size=6, of=with_unit(1, members=[30, 20], of=with_unit(0, members=[0, 100, c.n]))),
+         "set_components: a unit's size is outside [0, max_size=5]"),
     ]
     _valid_refused_valid(valid, *refusals)
 

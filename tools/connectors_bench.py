@@ -28,7 +28,7 @@ import connectors_mirror as M  # noqa: E402
 import proximity_mirror as PM  # noqa: E402
 from gcn_drug_repurposing_amd import _lib  # noqa: E402
 from gcn_drug_repurposing_amd.connectors import STEP_FIELDS, UNIT_FIELDS, ConnectorEngine  # noqa: E402
-from gcn_drug_repurposing_amd.proximity import degree_bins, random_set_table  # noqa: E402
+from gcn_drug_repurposing_amd.proximity import degree_bins  # noqa: E402
 
 
 def timed(fn):
@@ -114,8 +114,7 @@ def main():
     # the null: every set and its random sets
     if args.n_random:
         table, whole = all_of(lambda: eng.connector_table(genes, 1, n_add=args.n_add, n_random=args.n_random, seed=args.seed), args.reps)
-        nodes, sizes = random_set_table(lambda *a: eng.lib.gss_random_sets(net.n, *a), "gss_random_sets", net.n, torch.device("cuda"), sets, 1,
-                                        args.n_random, args.seed, degree_bins(net.degree, 100))
+        nodes, sizes = eng.set_table(sets, 1, args.n_random, args.seed, degree_bins(net.degree, 100))
         flat_nodes, flat_sizes = nodes.reshape(-1, nodes.shape[2]).contiguous(), sizes.reshape(-1).contiguous()
         call, bufs = entry_point(eng, flat_nodes, flat_sizes, args.n_add)
         _, alone = all_of(call, args.reps)
@@ -141,7 +140,7 @@ def main():
     eng.close()
     out["device"] = torch.cuda.get_device_name(0)
     out["source_hashes"] = {k: v for k, v in _lib.source_hashes().items()
-                            if k in ("seed_connect.hip", "lds_union_find.h", "proximity.hip", "device_scope.h", "common.h", "*")}
+                            if k in ("seed_connect.hip", "seed_units.h", "lds_union_find.h", "proximity.hip", "device_scope.h", "common.h", "*")}
     text = json.dumps(out, indent=1)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:

@@ -65,10 +65,7 @@ def main():
            "reps": args.reps}
     res, whole = all_of(lambda: eng.grow(sets, n_add=args.n_add, alpha=args.alpha), args.reps)
     # the entry point alone, on device tables built once
-    seeds = np.full((U, width), -1, np.int32)
-    for i, s in enumerate(sets):
-        seeds[i, :len(s)] = s
-    d_seeds, d_sizes = torch.from_numpy(seeds).cuda(), torch.from_numpy(np.array([len(s) for s in sets], np.int32)).cuda()
+    d_seeds, d_sizes, _ = eng.pack(sets)
     lg = eng._table(net.n + (args.alpha - 1) * width + 2)
     ints = [torch.empty((U, args.n_add), dtype=torch.int32, device="cuda") for _ in range(3)]
     reals = [torch.empty((U, args.n_add), dtype=torch.float64, device="cuda") for _ in range(3)]
@@ -104,7 +101,7 @@ def main():
     if args.mirror_sets is None:
         out["speedup_engine_over_mirror"] = round(seconds * 1e3 / float(np.median(whole)), 1)
     out["device"] = torch.cuda.get_device_name(0)
-    out["source_hashes"] = {k: v for k, v in _lib.source_hashes().items() if k in ("diamond.hip", "device_scope.h", "common.h", "*")}
+    out["source_hashes"] = {k: v for k, v in _lib.source_hashes().items() if k in ("diamond.hip", "seed_units.h", "device_scope.h", "common.h", "*")}
     text = json.dumps(out, indent=1)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:

@@ -91,7 +91,7 @@ def main():
                          probes_per_s=model["probes"] / comp * 1e3, units_per_s=model["units"] / comp * 1e3)
     eng.close()
     out["device"] = torch.cuda.get_device_name(0)
-    out["source_hashes"] = {k: v for k, v in _lib.source_hashes().items() if k in ("set_modules.hip", "proximity.hip", "*")}
+    out["source_hashes"] = {k: v for k, v in _lib.source_hashes().items() if k in ("set_modules.hip", "seed_units.h", "lds_union_find.h", "proximity.hip", "*")}
     text = json.dumps(out, indent=1)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
