@@ -513,6 +513,37 @@ int gss_seed_connectors(int32_t n, const int32_t *rowptr, const int32_t *col, in
                         int32_t *deg, int32_t *steps, int32_t *first_lcc, int32_t *final_lcc, int32_t *seeds_in, int32_t *added_in,
                         int32_t *label /* NULL or [n_units][max_size + n_add] */, void *stream);
 
+/* ---- connecting a seed set: approximate Steiner trees (Kou, Markowsky and Berman 1981 in Mehlhorn's 1988 form), DESIGN.md section 9.20 --
+ * gss_steiner_trees: a unit is one row of a seed table (seeds [n_units][max_size], sizes [n_units], device), as gss_seed_connectors
+ * takes it; its T terminals are numbered by position p = 0 .. T - 1.  The CSR (rowptr [n + 1], col, device) is the one
+ * gss_set_components takes: symmetric, no self loops, columns ascending, any number of components; max_deg is the caller's bound on a
+ * row's length, checked on the device.  Edges have weight 1.
+ * 1. dist(v) = the hop distance from v to the nearest terminal, src(v) = the smallest position p with d(v, terminal p) = dist(v):
+ *    level by level, every node takes the minimum of (dist, src) over its neighbours.  A node no terminal reaches has neither.
+ * 2. An edge (u, v), u < v, both ends reached, src(u) != src(v), is a bridge of weight w = dist(u) + dist(v) + 1 between terminals
+ *    src(u) and src(v).  The tree's bridges are the minimum spanning forest of the terminals under the strict total order (w, u, v):
+ *    unique, so Kruskal on the sorted bridges and the Boruvka rounds of the kernel choose the same edges.
+ * 3. parent(x), x reached and no terminal, = the smallest neighbour y with dist(y) = dist(x) - 1 and src(y) = src(x).  The tree's nodes
+ *    are the terminals and every node on the parent chains from both ends of every chosen bridge; its edges those parent edges and the
+ *    bridges.  (A forest whose leaves are terminals: KMB's second spanning tree and its pruning change nothing.)
+ * Per unit (int32 [n_units], device, exact): n_comp = the trees of the forest (0 for an empty unit), length = the sum of w over the
+ * chosen bridges, n_steiner = the tree nodes that are no terminals, n_edges = T + n_steiner - n_comp, max_w = the largest w (0 without
+ * a bridge).  Lists, each NULL or given: steiner and parent [n_units][max_add] (both or neither): the Steiner nodes in ascending node
+ * order with their parents beside them, the first max_add when there are more (the counts stay exact); bridge
+ * [n_units][max_size - 1][2]: the chosen bridges (u, v) ascending.  Entries past the counts are left as the caller had them.
+ * All integers: the same between runs and for any split of the units into calls; no global atomic but the status word's.
+ * n in [1, 30720], n_units >= 1, 1 <= max_size <= 4096, max_add >= 0, 0 <= max_deg <= 1048575, n_units * max(max_size, max_add) < 2^40,
+ * and a unit's state must fit the LDS: 4 bytes per node (dist << 12 | src), 16 per terminal position (an 8-byte bridge key, a
+ * union-find parent, a chosen bridge): 4 n + 16 max_size <= 160 KiB - 512 bytes -- 116 KiB for n = 13,329 with max_size 4,096; n = 30,720
+ * leaves max_size <= 2,528.  Refused by name (GSS_EINVAL): a null pointer (but the lists), any of these bounds, the LDS budget, and a
+ * unit that breaks the table's contract or a row longer than max_deg -- found on the device, defined and worded in csrc/seed_units.h
+ * (no row of such a unit is walked; the outputs are then undefined).  Synchronises the stream (reads the status word back). */
+int gss_steiner_trees(int32_t n, const int32_t *rowptr, const int32_t *col, int32_t max_deg, int64_t n_units, int32_t max_size,
+                      const int32_t *seeds, const int32_t *sizes, int32_t max_add, int32_t *n_comp, int32_t *length, int32_t *n_steiner,
+                      int32_t *n_edges, int32_t *max_w, int32_t *steiner /* NULL or [n_units][max_add] */,
+                      int32_t *parent /* NULL or [n_units][max_add] */, int32_t *bridge /* NULL or [n_units][max_size - 1][2] */,
+                      void *stream);
+
 /* ---- shortest-path trees toward up to 64 targets per pass (predict_drug.py:268-273, run_covid.py:310-319: one networkx
  * shortest_path per table row; here one search toward each target answers every row) ------------------------------------------
  * Directed graph as a CSR: rowptr [n + 1], col [nnz], the columns of every row ascending (MsiGraph.to_csr, embio's edgelist reader).
