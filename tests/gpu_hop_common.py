@@ -1,4 +1,4 @@
-"""What the op-by-op GPU tests of the SpMM modes share (tests/test_gpu_sparse_ops.py, tests/test_gpu_dense_hops.py): the library
+"""What the op-by-op GPU tests of the SpMM modes share (tests/test_gpu_sparse_ops.py, tests/test_gpu_dense_hops.py, tests/test_gpu_spmm_ladder.py): the library
 fixture, the NaN pre-fill that tells a written element from a skipped one, the per-element check of a write set and of the mirror's
 derived bound (tests/sparse_hop_mirror.py), the knob context manager and the cache of device CSR handles.  No test lives here."""
 import contextlib
@@ -11,7 +11,7 @@ import sparse_hop_mirror as M
 torch = pytest.importorskip("torch")
 
 PREFILL = 0x7FC0DEAD                 # a quiet NaN with a payload no computation produces
-DEFAULTS = {"spmm_list_blocks": 2048, "spmm_giant": 32768, "spmm_variant": 2, "spmm_slices": 0, "spmm_pin": 0}
+DEFAULTS = {"spmm_list_blocks": 2048, "spmm_giant": 32768, "spmm_variant": 2, "spmm_slices": 0, "spmm_pin": 0, "spmm_hot_rows": -1}
 
 
 @pytest.fixture(scope="module")
