@@ -175,6 +175,8 @@ SIGNATURES = {
     "gss_diamond_grow": (C.c_int, [_I32, _P, _P, _I32, _P, _I64, _I64, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "gss_seed_connectors": (C.c_int, [_I32, _P, _P, _I32, _I64, _I32, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gss_steiner_trees": (C.c_int, [_I32, _P, _P, _I32, _I64, _I32, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gss_rwr_rank": (C.c_int, [_I32, _P, _P, _I32, _I64, _I32, _P, _P, _D, _D, _I32, _I32, _P, _P, _P, _P, _P]),
+    "gss_rwr_null_stats": (C.c_int, [_I32, _I32, _I32, _P, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     "gss_paths_create": (C.c_int, [C.POINTER(_P), _I32, _I64, _P, _P, _I32, _I64, _P]),
     "gss_paths_run": (C.c_int, [_P, _I32, _P, _P, _P, C.POINTER(_I32), _P]),
     "gss_paths_destroy": (None, [_P]),

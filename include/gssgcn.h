@@ -544,6 +544,53 @@ int gss_steiner_trees(int32_t n, const int32_t *rowptr, const int32_t *col, int3
                       int32_t *parent /* NULL or [n_units][max_add] */, int32_t *bridge /* NULL or [n_units][max_size - 1][2] */,
                       void *stream);
 
+/* ---- ranking nodes by random walk with restart from seed sets (network propagation; Koehler et al. 2008, the comparator of the
+ * DIAMOnD paper), DESIGN.md section 9.21 ----------------------------------------------------------------------------------------------
+ * gss_rwr_rank: a unit is one row of a seed table (nodes [n_units][max_size], sizes [n_units], device), as gss_diamond_grow takes it:
+ * strictly ascending node indices in [0, n), entries past the size never read.  The CSR (rowptr [n + 1], col, device) is the one
+ * gss_set_components takes: symmetric, no self loops, which the caller guarantees; every row has an entry and at most max_deg, checked
+ * on the device.  For a unit S of m >= 1 seeds, deg[j] = rowptr[j + 1] - rowptr[j], all in fp64, every product, quotient, sum and
+ * difference rounded on its own (nothing contracted into a multiply-add):
+ *   p0[i] = 1.0 / m on S (one division), 0 elsewhere; p = p0; then per iteration
+ *   q[j] = p[j] / deg[j];  s[i] = the sum of q[col[e]] over row i;  p'[i] = (1 - restart) * s[i] + restart * p0[i];
+ *   err = the sum over i of |p'[i] - p[i]|;  p <- p'.
+ * It stops after the iteration with err < tol (strict) or after max_iter of them; iters_out[u] is the number run, so tol = 0 runs
+ * exactly max_iter.  The order of the sums, T = 1024 threads in 16 waves of 64 lanes, node i owned by thread i % T:
+ *   s[i], a row of at most 32 entries (the row schedule changes class between 32 and 33): from 0.0, the entries added in ascending e;
+ *   s[i], a longer row: lane l starts from 0.0 and adds the entries e = rowptr[i] + l, + 64, + 128, ... in ascending e; then the
+ *     butterfly x[l] <- x[l] + x[l ^ o] for o = 32, 16, 8, 4, 2, 1 over the 64 lanes (every lane ends with the same bits);
+ *   err: thread t starts from 0.0 and adds |p'[i] - p[i]| for i = t, t + T, t + 2T, ... ascending; the same butterfly over each wave's
+ *     64 threads; then wave 0's sum plus wave 1's, ..., plus wave 15's, in that order.
+ * Candidates are the nodes outside S, ordered by (p descending, node ascending); the first n_add go to node_out (int32) and score_out
+ * (fp64), both [n_units][n_add], padded with -1 and NaN (both NULL: no ranking is made).  p_out (NULL or [n_units][n]) receives the whole
+ * vector.  An empty unit has iters = 0, -1 and NaN everywhere and a NaN row of p_out.  Every output is a function of (CSR, unit,
+ * parameters) alone: the same bits between runs, at every position of the table and beside any other units.
+ * n in [2, 20000]: q is 8 n bytes of LDS, 160,000 of the 163,840 a workgroup may declare (p stays in registers, at most 20 per thread);
+ * n_units >= 1, 1 <= max_size <= 4096, max_deg >= 1, 0 < restart < 1, tol >= 0 (not NaN), max_iter >= 1, 1 <= n_add <= 1024,
+ * n_units * max(max_size, n_add, n) < 2^40.  Refused by name (GSS_EINVAL): a null pointer (but p_out, or the two rankings), any of
+ * these bounds, an empty row, and a unit that breaks the table's contract or a row longer than max_deg -- found on the device, defined
+ * and worded in csrc/seed_units.h (no row of such a unit is walked; the outputs are then undefined).  GSS_ENOTCONV, after every output
+ * is written with the last iterates: with tol > 0 some unit ran max_iter iterations without err < tol; the message counts them.
+ * Synchronises the stream.
+ *
+ * gss_rwr_null_stats: p [n_sets][R][n] is gss_rwr_rank's p_out of a set table (nodes [n_sets][R][max_size], sizes [n_sets][R]) whose
+ * sample 0 is the set itself and samples 1 .. R - 1 its random sets.  Per (set, node), over k = 1 .. R - 1 in ascending order, all
+ * single fp64 operations: sum = 0.0 + p_1 + p_2 + ...; mean = sum / (R - 1); sq = 0.0 + d_1 d_1 + d_2 d_2 + ..., d_k = p_k - mean;
+ * sd = sqrt(sq / (R - 1)) (the population's); z = (p_0 - mean) / sd, 0 where sd = 0; ge (int32) = #{k >= 1: p_k >= p_0}.  The seeds
+ * of sample 0 have z = NaN and are no candidates.  node_out [n_sets][n_add]: the candidates by (p_0 descending, node ascending) with
+ * rank_by = 0, by (z descending, p_0 descending, node ascending) with rank_by = 1, padded with -1: the selection of gss_rwr_rank.  A set
+ * whose sample 0 is empty has NaN, ge = -1 and node_out = -1 everywhere.  mean, sd, z, ge: [n_sets][n], device.  Only sample 0's rows
+ * of the table are read.  The same bits for any split of the sets into calls.  n in [2, 20000], 1 <= n_sets <= 65535, 3 <= R <= 2^20,
+ * 1 <= max_size <= 4096, 1 <= n_add <= 1024; refused by name (GSS_EINVAL) beside a null pointer and what seed_units.h names of sample 0.
+ * Synchronises the stream. */
+int gss_rwr_rank(int32_t n, const int32_t *rowptr, const int32_t *col, int32_t max_deg, int64_t n_units, int32_t max_size,
+                 const int32_t *nodes, const int32_t *sizes, double restart, double tol, int32_t max_iter, int32_t n_add,
+                 int32_t *node_out /* NULL or [n_units][n_add] */, double *score_out /* as node_out */, int32_t *iters_out,
+                 double *p_out /* NULL or [n_units][n] */, void *stream);
+int gss_rwr_null_stats(int32_t n, int32_t n_sets, int32_t R, const double *p, int32_t max_size, const int32_t *nodes,
+                       const int32_t *sizes, int32_t n_add, int32_t rank_by, double *mean, double *sd, double *z, int32_t *ge,
+                       int32_t *node_out, void *stream);
+
 /* ---- shortest-path trees toward up to 64 targets per pass (predict_drug.py:268-273, run_covid.py:310-319: one networkx
  * shortest_path per table row; here one search toward each target answers every row) ------------------------------------------
  * Directed graph as a CSR: rowptr [n + 1], col [nnz], the columns of every row ascending (MsiGraph.to_csr, embio's edgelist reader).
